@@ -79,7 +79,48 @@ def parse_args():
                          "next: the double buffering of a production loop.  1: one context, every call waits for the one before it (also reported as "
                          "'one_context' when 2 is measured; --single-device rehearsals use 1)")
     ap.add_argument("--dump-shard", default=None, help="(tests) write this rank's outputs to <path>.rank<r>.npz")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's shard) as DIR/<name>.npy in float64 (rev: float32), "
+                         "at most 64 MB: see dump_outputs")
     return ap.parse_args()
+
+
+DUMP_ITEMS = 1_000_000  # entries kept of each output array by --dump-outputs; longer arrays are sampled (8 arrays: 60 MB at most)
+
+
+def sample_index(n, cap, seed):
+    """ascending indices into an array of n entries: all of them when n <= cap, else a fixed seeded sample of at most cap entries that
+    keeps the first and the last"""
+    import numpy as np
+
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.union1d(np.random.default_rng(seed).choice(n, size=cap - 2, replace=False), [0, n - 1]).astype(np.int64)
+
+
+def dump_outputs(path, outs, n_kminmers, cap=DUMP_ITEMS):
+    """--dump-outputs: the arrays a caller of s2k_extract_device receives (`outs`: torch tensors km_off int64, hash int64 holding a u64,
+    start / end int32 holding a u32, rev uint8) as <path>/<name>.npy, every value exact: km_off, start, end in float64, rev in float32,
+    and the 64-bit hash, which float64 cannot hold, as its two 32-bit halves hash_hi and hash_lo.  An array of more than `cap` entries
+    is replaced by a fixed seeded sample (sample_index); read_index (into km_off) and kminmer_index (into the others) name the entries
+    kept.  Returns the bytes written."""
+    import numpy as np
+    import torch
+
+    def take(t, idx):
+        return t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+
+    ri = sample_index(outs["km_off"].shape[0], cap, 1)
+    ki = sample_index(n_kminmers, cap, 2)
+    h = take(outs["hash"], ki).view(np.uint64)
+    arrays = {"read_index": ri.astype(np.float64), "km_off": take(outs["km_off"], ri).astype(np.float64),
+              "kminmer_index": ki.astype(np.float64), "hash_hi": (h >> np.uint64(32)).astype(np.float64),
+              "hash_lo": (h & np.uint64(0xFFFFFFFF)).astype(np.float64), "start": take(outs["start"], ki).view(np.uint32).astype(np.float64),
+              "end": take(outs["end"], ki).view(np.uint32).astype(np.float64), "rev": take(outs["rev"], ki).astype(np.float32)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
 
 
 def spawn_ranks(n):
@@ -251,10 +292,8 @@ def main():
     if world != args.gpus:
         sys.exit("bench.py: --gpus %d but WORLD_SIZE=%d (launch one rank per GPU, or let bench.py spawn them)" % (args.gpus, world))
 
-    if args.contexts == 2 and not args.single_device:
-        # two contexts = four streams of the library beside torch's own: every stream gets a hardware queue of its own (the runtime's default is
-        # four per process; two streams that share a queue serialise, and a wait in one holds up the other) -- read by the HIP runtime at start-up
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     import numpy as np
     import torch
     from s2k_loader import import_package
@@ -550,6 +589,10 @@ def main():
         np.savez(args.dump_shard + ".rank%d.npz" % rank, km_off=outs["km_off"].cpu().numpy().view(np.uint64),
                  hash=outs["hash"][:nk].cpu().numpy().view(np.uint64), start=outs["start"][:nk].cpu().numpy().view(np.uint32),
                  end=outs["end"][:nk].cpu().numpy().view(np.uint32), rev=outs["rev"][:nk].cpu().numpy(), first_base=first_base, n_bases=n_bases)
+    if args.dump_outputs and rank == 0:
+        # here, before the legs below reuse `outs`; with two contexts the last step may have written the other set of arrays, which
+        # the check above found equal to these
+        dump_outputs(args.dump_outputs, outs, counts["n_kminmers"])
     # the other scalar HashMode, for the record (not the headline)
     other_line = None
     if not args.no_other_mode:

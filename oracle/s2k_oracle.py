@@ -20,6 +20,21 @@ _u32p = C.POINTER(C.c_uint32)
 _u64p = C.POINTER(C.c_uint64)
 
 
+def _lazy_dir():
+    """Where the variants built on first use (-march=native, AVX-512) go: next to the sources, or, when this user cannot write
+    there (a checkout owned by another user), a private directory of this user's under the temporary directory."""
+    if os.access(_HERE, os.W_OK):
+        return _HERE
+    import tempfile
+
+    d = os.path.join(tempfile.gettempdir(), "s2k_oracle_%d" % os.getuid())
+    os.makedirs(d, mode=0o700, exist_ok=True)
+    st = os.lstat(d)
+    if not os.path.isdir(d) or os.path.islink(d) or st.st_uid != os.getuid() or st.st_mode & 0o022:
+        raise RuntimeError("%s is not a private directory of this user: the oracle will not load libraries from it" % d)
+    return d
+
+
 def build(native=False, out=None):
     """Compile the oracle. `native=True` adds -march=native (used for the timed CPU baseline,
     mirroring the reference's `-Ctarget-cpu=native`, .cargo/config:2)."""
@@ -57,7 +72,7 @@ class Oracle:
                         model = next((ln for ln in f if ln.startswith("model name")), "")
                 except OSError:
                     pass
-                out = os.path.join(_HERE, "libs2k_oracle_native_%s.so" % hashlib.md5(model.encode()).hexdigest()[:8])
+                out = os.path.join(_lazy_dir(), "libs2k_oracle_native_%s.so" % hashlib.md5(model.encode()).hexdigest()[:8])
             path = build(native=native, out=out)
         L = self.lib = C.CDLL(path)
         L.s2k_oracle_hash_bound.restype = C.c_uint32
@@ -278,10 +293,10 @@ class Oracle:
 
 
 def build_avx512(out=None):
-    """Compile the AVX-512 CPU baseline (oracle/s2k_oracle_avx512.c) next to the scalar oracle.  Returns the path,
+    """Compile the AVX-512 CPU baseline (oracle/s2k_oracle_avx512.c) next to the scalar oracle (see _lazy_dir).  Returns the path,
     or None when the compiler rejects the flags."""
     if out is None:
-        out = os.path.join(_HERE, "libs2k_oracle_avx512.so")
+        out = os.path.join(_lazy_dir(), "libs2k_oracle_avx512.so")
     srcs = [os.path.join(_HERE, "s2k_oracle_avx512.c"), os.path.join(_HERE, "s2k_oracle.c")]
     if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(x) for x in srcs):
         return out

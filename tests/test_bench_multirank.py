@@ -92,6 +92,27 @@ def test_rccl_that_cannot_come_up_does_not_cost_the_line(tmp_path):
     assert two["downstream_count"]["n_keys"] == two["counts"]["kminmers"]
 
 
+@pytest.mark.gpu
+def test_dump_outputs_are_the_timed_steps_results(tmp_path):
+    """--dump-outputs (two chained contexts, the default): every dumped entry equals the one the run wrote with --dump-shard; the
+    ~1.4 M k-min-mers exceed the cap, so the sample is exercised; a second run with other step counts dumps the same files"""
+    tmp = str(tmp_path)
+    a = run_bench(["--gpus", "1", "--reads", "12000", "--dump-outputs", os.path.join(tmp, "da")], tmp, "d1", workload="c2")
+    b = run_bench(["--gpus", "1", "--reads", "12000", "--steps", "3", "--warmup", "2", "--dump-outputs", os.path.join(tmp, "db")], tmp, "d2", workload="c2")
+    assert a["contexts"] == 2 and b["steps"] == 3 and a["counts"] == b["counts"] and a["ms_per_step"] > 0
+    ref = np.load(os.path.join(tmp, "d1.rank0.npz"))
+    d = {f[:-4]: np.load(os.path.join(tmp, "da", f)) for f in os.listdir(os.path.join(tmp, "da"))}
+    assert sum(x.nbytes for x in d.values()) <= 64_000_000
+    ri, ki = d["read_index"].astype(np.int64), d["kminmer_index"].astype(np.int64)
+    assert len(ri) == 12001 and len(ki) < a["counts"]["kminmers"] and ki[-1] == a["counts"]["kminmers"] - 1
+    assert (d["km_off"].astype(np.uint64) == ref["km_off"][ri]).all()
+    assert (((d["hash_hi"].astype(np.uint64) << np.uint64(32)) | d["hash_lo"].astype(np.uint64)) == ref["hash"][ki]).all()
+    for f in ("start", "end", "rev"):
+        assert (d[f] == ref[f][ki]).all(), f
+    for name, x in d.items():
+        assert np.array_equal(np.load(os.path.join(tmp, "db", name + ".npy")), x), name
+
+
 def test_more_ranks_than_gpus_fails_loudly():
     """no GPU (or fewer than --gpus) visible: every rank says so and exits non-zero before anything touches a device"""
     import torch
