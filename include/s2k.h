@@ -131,12 +131,15 @@ int s2k_device_count(void);
 /* Creates a context on HIP device `device`.  Fails with S2K_ERR_NO_DEVICE when no GPU is visible. */
 s2k_ctx *s2k_create(int device, s2k_status *status);
 void s2k_destroy(s2k_ctx *ctx);
-/* Use an existing hipStream_t (e.g. torch's current stream) instead of the context's own. */
+/* Use an existing hipStream_t (e.g. torch's current stream) instead of the device's shared k-min-mer stream: the k-min-mer stage, the totals
+ * and the counts copy of every call run on it (results are complete in its order), the minimizer kernels on the device's minimizer stream,
+ * which waits for this stream at the start of each call. */
 s2k_status s2k_set_stream(s2k_ctx *ctx, void *hip_stream);
-/* Double buffering with two contexts on one device (a loop over many device-resident batches): after s2k_chain_after(b, a) the minimizer
- * kernels of b's calls wait for the minimizer kernels of a's most recent call, nothing else does -- so the tail of a's call (its last
- * k-min-mer kernel, the totals, the host's look at the counts) runs beside the first chunk of b's, and two persistent kernels never compete
- * for the device.  Chain both ways (a after b, b after a) and alternate the calls from ONE host thread.  prev = NULL removes the link;
+/* Double buffering with two contexts on one device (a loop over many device-resident batches): the minimizer kernels of every context on a
+ * device run in call order on one stream of the library's, and the rest of a call on another (or the caller's), so the tail of a's call (its
+ * last k-min-mer kernel, the totals, the host's look at the counts) runs beside the first chunk of b's next one, and two persistent kernels
+ * never compete for the device.  s2k_chain_after(b, a) tells b that a call of a's follows each of its own (it sizes its chunks for that).
+ * Chain both ways (a after b, b after a) and alternate the calls from ONE host thread.  prev = NULL removes the link;
  * s2k_destroy(prev) removes every link to prev by itself (the survivor then runs unchained), from any thread: links are read and cut under one
  * lock.  A prev that is not a live context is refused (S2K_ERR_INVALID_ARG).  Results do not depend on it. */
 s2k_status s2k_chain_after(s2k_ctx *ctx, s2k_ctx *prev);

@@ -220,17 +220,22 @@ struct Call { // everything needed to (re-)enqueue one extraction
 
 struct s2k_ctx {
     int device = 0;
+    // stream: the k-min-mer stage, finalize, the counts copy and every other entry point's work -- the caller's (s2k_set_stream) or the device's K
     hipStream_t stream = nullptr;
-    bool own_stream = false;
+    bool user_stream = false;  // s2k_set_stream was called: results are complete in the order of the caller's stream
+    bool has_pipes = false;    // holds a reference to the device's pipeline pair (PipePair)
+    hipStream_t p = nullptr;   // the device's P: every minimizer kernel of every context on the device, in call order
+    hipEvent_t done_ev = nullptr; // recorded behind the context's last work on `stream`: host waits and the next call's workspace wait
+    bool done_valid = false;
+    hipEvent_t entry_ev = nullptr; // user_stream: recorded on the caller's stream at the start of a call, P waits on it
     DevBuf ws, in_bases, in_off, outbuf, realign; // realign: aligned copy of a caller's misaligned device stream
     DevBuf in_bases2, in_off2, outbuf2;           // second set: s2k_extract double-buffers its sub-batches
     DevBuf count_tab;                             // s2k_count_device: the hash table (grow-only, like ws)
     hipStream_t s_in = nullptr, s_out = nullptr;  // s2k_extract: H2D of the next / D2H of the previous sub-batch
-    hipStream_t s_km = nullptr;                   // descriptor path: scan + k-min-mer kernel of chunk c run here, beside the minimizer kernel of chunk c+1
-    std::vector<hipEvent_t> chunk_ev;             // fork / per-chunk / join events of that pipeline (no timing)
+    std::vector<hipEvent_t> chunk_ev;             // per-chunk events: P -> `stream` (no timing)
     uint32_t rec_per_tile_hint = 0;               // minimizers per tile of the last descriptor-path call (+ margin): Desc::spec_n
-    s2k_ctx *chain_prev = nullptr;                // s2k_chain_after: this context's minimizer kernels wait for tiles_done of that one
-    hipEvent_t tiles_done = nullptr;              // recorded behind the last minimizer kernel of a call (created on first use)
+    s2k_ctx *chain_prev = nullptr;                // s2k_chain_after: a call of that context follows this one's on P (chunk sizes, the last k-min-mer kernel)
+    hipEvent_t tiles_done = nullptr;              // recorded on P behind the last minimizer kernel of a call (created on first use)
     bool tiles_done_valid = false;
     uint32_t desc_chunks = 0;                     // chunks of tiles per call: 0 = default (6 for Hpc modes, 8 otherwise; S2K_DESC_CHUNKS overrides; 1 = no overlap)
     uint32_t lookback_giveups = 0;                // HpcSimd calls that were run again because a look-back gave up; two make the pre-pass the default of the context
@@ -261,12 +266,74 @@ struct s2k_ctx {
 namespace {
 std::mutex g_ctx_mu;
 std::vector<s2k_ctx *> g_live_ctx;
+
+// The device's pipeline pair, shared by its contexts and reference-counted by them ("Streams and hardware queues").  A process gets at
+// most GPU_MAX_HW_QUEUES hardware queues per device (two on shared machines), the runtime spreads every stream over them, and AQL packets on one
+// queue start in order: a barrier packet for one stream holds back every stream on its queue.  So all minimizer kernels of the device go on one
+// stream, P, and everything that waits on a minimizer kernel (tile-word scans, k-min-mer kernels, finalize, the counts copy) on another, K, or on
+// the caller's stream.  Nothing on P waits on a k-min-mer kernel except a context's own previous call (its workspace is reused).
+// The runtime gives a new stream the queue with the fewest streams on it, ties to the older queue.  In a process whose default stream already
+// holds the first queue (any PyTorch process) P and K created back to back would both land on the second; a short-lived spacer between them sends
+// K to the first (profiles/r07_queues_after.txt).
+struct PipePair {
+    hipStream_t p = nullptr, k = nullptr;
+    int refs = 0;
+};
+std::vector<PipePair> g_pipes; // by device, under g_ctx_mu
+} // namespace
+
+namespace {
+// Takes the context's reference to its device's pipeline pair, creating the pair on first use: P, a spacer, K (see PipePair).  A context that never
+// called s2k_set_stream works on K from here on.
+hipError_t ensure_pipes(s2k_ctx *ctx) {
+    if (ctx->has_pipes) return hipSuccess;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(g_ctx_mu);
+    if (g_pipes.size() <= (size_t)ctx->device) g_pipes.resize((size_t)ctx->device + 1);
+    PipePair &pp = g_pipes[ctx->device];
+    if (!pp.p) {
+        hipStream_t p = nullptr, spacer = nullptr, k = nullptr;
+        e = hipStreamCreateWithFlags(&p, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&spacer, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&k, hipStreamNonBlocking);
+        if (spacer) (void)hipStreamDestroy(spacer);
+        if (e != hipSuccess) {
+            if (p) (void)hipStreamDestroy(p);
+            if (k) (void)hipStreamDestroy(k);
+            return e;
+        }
+        pp.p = p;
+        pp.k = k;
+    }
+    pp.refs++;
+    ctx->has_pipes = true;
+    ctx->p = pp.p;
+    if (!ctx->user_stream) ctx->stream = pp.k;
+    return hipSuccess;
+}
+
+// done_ev marks the context's work on its stream so far: the next call's P waits on it (workspace, inputs staged on the stream), host waits use it
+hipError_t mark_done(s2k_ctx *ctx) {
+    hipError_t e = hipEventRecord(ctx->done_ev, ctx->stream);
+    if (e == hipSuccess) ctx->done_valid = true;
+    return e;
+}
 } // namespace
 
 // context internals for the other translation units of the library (declared in s2k_hostcopy.h)
 namespace s2k {
 HostStager &ctx_stager(s2k_ctx *c) { return c->stager; }
-hipStream_t ctx_stream(s2k_ctx *c) { return c->stream; }
+hipStream_t ctx_stream(s2k_ctx *c) {
+    (void)ensure_pipes(c); // (on failure the work goes to the null stream: ordered, only slower)
+    return c->stream;
+}
+hipError_t ctx_mark(s2k_ctx *c) { return mark_done(c); }
+// the host waits for the context's work so far: its own event, never a stream synchronize (P and K carry other contexts' work)
+hipError_t ctx_sync(s2k_ctx *c) {
+    hipError_t e = mark_done(c);
+    return e == hipSuccess ? hipEventSynchronize(c->done_ev) : e;
+}
 int ctx_device(s2k_ctx *c) { return c->device; }
 void ctx_set_error(s2k_ctx *c, const char *what) { c->err = what; }
 void *ctx_count_table(s2k_ctx *c, size_t bytes) { return c->count_tab.ensure(bytes) == hipSuccess ? c->count_tab.p : nullptr; }
@@ -385,7 +452,6 @@ s2k_status enqueue(s2k_ctx *ctx) {
     const uint64_t n_reads = c.n_reads, n_bases = c.n_bases;
     const uint64_t n_tiles = c.serial ? n_reads : (n_bases + TILE_BASES - 1) / TILE_BASES;
     const s2k_device_out &o = c.out;
-    hipStream_t st = ctx->stream;
 
     // ---- carve the workspace (first pass sizes, second pass pointers) --------------------------
     Arena a{nullptr, 0, 0};
@@ -398,7 +464,7 @@ s2k_status enqueue(s2k_ctx *ctx) {
     const bool use_desc = !c.serial && !c.legacy && n_tiles >= 1 && n_reads >= 1 && c.sem.k <= 32;
     c.desc_run = use_desc;
     // The call is cut into chunks of tiles: while the minimizer kernel works on chunk c+1, the scan and the k-min-mer kernel of
-    // chunk c run on a second stream (they need ~1/6 of the time and, being bound by latency, fit beside a kernel that leaves
+    // chunk c run on the k-min-mer stream (they need ~1/6 of the time and, being bound by latency, fit beside a kernel that leaves
     // a quarter of the issue slots and some LDS free).  A chunk is at least a few tiles per resident wave.
     uint32_t n_chunks = 1;
     bool chained = false; // this context's calls are chained behind another's (s2k_chain_after)
@@ -410,8 +476,9 @@ s2k_status enqueue(s2k_ctx *ctx) {
         // chained call does best with chunks of ~4 Gbp (10 Gbp: 2-3 chunks 6.10 ms, six 6.17-6.25; 25 Gbp: six 15.0, three 15.5), an unchained one with
         // ~1.7 Gbp (10 Gbp: six 6.35-6.41, three 6.48-6.51), either way between two and eight.  (Rounds 3-4 used fixed counts: 6, and 2 for chained calls.)
         // Regular family: its minimizer kernel runs 16 waves per CU and leaves the k-min-mer kernel no room beside it (s2k_tile_impl.h: tw()): one
-        // launch of each, the k-min-mer stage behind the minimizer kernel on the caller's stream
-        { // (the link is another context's to cut -- s2k_destroy(prev) on any thread --: looked at under the registry's lock, here and at the wait below)
+        // launch of each, the k-min-mer stage behind the minimizer kernel on the k-min-mer stream
+        // (These sizes were tuned when every context had streams of its own; profiles/r07_ab_chained_chunks.txt re-measures the chained rule.)
+        { // (the link is another context's to cut -- s2k_destroy(prev) on any thread --: looked at under the registry's lock)
             std::lock_guard<std::mutex> lk(g_ctx_mu);
             chained = ctx->chain_prev != nullptr;
         }
@@ -477,6 +544,15 @@ s2k_status enqueue(s2k_ctx *ctx) {
 
     const bool tm = ctx->timing;
     ctx->timed = tm;
+    S2K_TRY(ensure_pipes(ctx), "stream create");
+    // sp (the device's P): everything up to the minimizer kernels; sk (the caller's stream, or K): what waits on them
+    hipStream_t const sp = ctx->p, sk = ctx->stream;
+    while (ctx->chunk_ev.size() < (size_t)n_chunks) {
+        hipEvent_t e;
+        S2K_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), "event create");
+        ctx->chunk_ev.push_back(e);
+    }
+    if (!ctx->tiles_done) S2K_TRY(hipEventCreateWithFlags(&ctx->tiles_done, hipEventDisableTiming), "event create");
     if (tm) {
         if (ctx->evs.size() < (ctx->ev_used + 1) * 6) {
             for (int i = 0; i < 6; i++) {
@@ -487,38 +563,47 @@ s2k_status enqueue(s2k_ctx *ctx) {
         }
         ctx->ev = &ctx->evs[ctx->ev_used * 6];
         ctx->ev_used++;
-        S2K_TRY(hipEventRecord(ctx->ev[0], st), "event");
     }
-    S2K_TRY(hipMemsetAsync(ctx->d_counts, 0, CTRL_CURSORS_OFF + (size_t)CURSOR_WORDS * (use_desc ? n_chunks : 1) * sizeof(uint64_t), st),
+    // Entry.  P waits for the caller's stream (s2k_set_stream), or for this context's own previous work -- its workspace and outputs are reused, and
+    // inputs may have been staged on its stream -- and never for another context's k-min-mer kernels: the tail of one context's call runs beside
+    // the first minimizer kernel of the next context's.  (s2k_chain_after needs no wait: every minimizer kernel of the device is in P's order.)
+    if (ctx->user_stream) {
+        S2K_TRY(hipEventRecord(ctx->entry_ev, sk), "event");
+        S2K_TRY(hipStreamWaitEvent(sp, ctx->entry_ev, 0), "stream wait (entry)");
+    } else if (ctx->done_valid && hipEventQuery(ctx->done_ev) != hipSuccess) {
+        S2K_TRY(hipStreamWaitEvent(sp, ctx->done_ev, 0), "stream wait (previous call)");
+    }
+    if (tm) S2K_TRY(hipEventRecord(ctx->ev[0], sp), "event");
+    S2K_TRY(hipMemsetAsync(ctx->d_counts, 0, CTRL_CURSORS_OFF + (size_t)CURSOR_WORDS * (use_desc ? n_chunks : 1) * sizeof(uint64_t), sp),
             "memset counters, xor shards, cursors");
+    // P -> sk after the minimizer work of a whole call (serial and legacy paths)
+    auto hand_over = [&]() -> s2k_status {
+        S2K_TRY(hipEventRecord(ctx->tiles_done, sp), "event");
+        ctx->tiles_done_valid = true;
+        if (tm) S2K_TRY(hipEventRecord(ctx->ev[2], sp), "event");
+        S2K_TRY(hipEventRecord(ctx->chunk_ev[0], sp), "event");
+        S2K_TRY(hipStreamWaitEvent(sk, ctx->chunk_ev[0], 0), "stream wait");
+        return S2K_OK;
+    };
     // the read table is caller memory in HBM: checked on the device, first thing in the stream; the kernels below look at
     // the verdict (or clamp what they read from the table) and the host reports it in finish()
     if (c.serial) {
-        S2K_TRY(launch_validate_read_off(c.d_read_off, n_reads, n_bases, &ctx->d_counts->bad_input, st), "read table validation");
-        if (tm) S2K_TRY(hipEventRecord(ctx->ev[1], st), "event");
-        S2K_TRY(launch_serial_count(c.d_bases, c.d_read_off, n_reads, n_bases, c.sem, mn_cnt, st), "serial count kernel");
-        S2K_TRY(launch_scan_u32(mn_cnt, n_reads, mn_off, scan_tmp, 0, st), "scan");
-        S2K_TRY(launch_serial_write(c.d_bases, c.d_read_off, n_reads, n_bases, c.sem, mn_off, rec, ctx->d_counts, st), "serial write kernel");
-        if (tm) S2K_TRY(hipEventRecord(ctx->ev[2], st), "event");
+        S2K_TRY(launch_validate_read_off(c.d_read_off, n_reads, n_bases, &ctx->d_counts->bad_input, sp), "read table validation");
+        if (tm) S2K_TRY(hipEventRecord(ctx->ev[1], sp), "event");
+        S2K_TRY(launch_serial_count(c.d_bases, c.d_read_off, n_reads, n_bases, c.sem, mn_cnt, sp), "serial count kernel");
+        S2K_TRY(launch_scan_u32(mn_cnt, n_reads, mn_off, scan_tmp, 0, sp), "scan");
+        S2K_TRY(launch_serial_write(c.d_bases, c.d_read_off, n_reads, n_bases, c.sem, mn_off, rec, ctx->d_counts, sp), "serial write kernel");
+        s2k_status hs = hand_over();
+        if (hs != S2K_OK) return hs;
     } else {
-        if (!use_desc) S2K_TRY(hipMemsetAsync(mn_cnt, 0, (n_reads + 1) * sizeof(uint32_t), st), "memset mn_cnt"); // (per-read counts: legacy path only)
+        if (!use_desc) S2K_TRY(hipMemsetAsync(mn_cnt, 0, (n_reads + 1) * sizeof(uint32_t), sp), "memset mn_cnt"); // (per-read counts: legacy path only)
         // Descriptor path: every tile writes its word (dense_phase<DESC>); the array still starts as the IDENTITY of the scan -- dep and pass
         // set: "no minimizers, p handed on" (agg_identity, s2k_dev.h) -- so that a tile which left none would drop nothing.  (Zero is NOT the
         // identity: it unpacks to dep = pass = false, q = 0, i.e. "a read ends here", and would cut every window spanning the tile.)  The
         // read-table kernel writes it on its way: validation, tile index and this fill are one launch.
         S2K_TRY(launch_read_table(c.d_read_off, n_reads, n_bases, n_tiles, &ctx->d_counts->bad_input, tile_read0,
-                                  use_desc ? (unsigned long long *)d_agg : nullptr, agg_pack(0, 0, 0, 0, true, true), st),
+                                  use_desc ? (unsigned long long *)d_agg : nullptr, agg_pack(0, 0, 0, 0, true, true), sp),
                 "read table kernel");
-        // s2k_chain_after: this call's minimizer kernels start when those of the other context's call have ended (the launches above
-        // -- a memset, the read table -- need not wait)
-        // (under the registry's lock: s2k_destroy(prev) cuts the link under the same lock BEFORE it destroys the event, so the wait is either enqueued
-        // on a live event or not at all)
-        {
-            std::lock_guard<std::mutex> lk(g_ctx_mu);
-            s2k_ctx *const prev = ctx->chain_prev;
-            if (prev && prev->tiles_done_valid) S2K_TRY(hipStreamWaitEvent(st, prev->tiles_done, 0), "stream wait (chain)");
-        }
-        if (!ctx->tiles_done) S2K_TRY(hipEventCreateWithFlags(&ctx->tiles_done, hipEventDisableTiming), "event create");
         Sem sem = c.sem;
         sem.read_runs = nullptr;
         // HpcSimd: the tail rule needs the run count of the whole read.  Default: the tiles tell each other (Sem::tile_heads, a
@@ -527,11 +612,11 @@ s2k_status enqueue(s2k_ctx *ctx) {
         sem.tile_heads = nullptr;
         if (want_runs) {
             if (c.full_runs) {
-                S2K_TRY(launch_read_run_counts(c.d_bases, c.d_read_off, n_reads, n_bases, run_blk, run_off, run_tmp, read_runs, nullptr, st),
+                S2K_TRY(launch_read_run_counts(c.d_bases, c.d_read_off, n_reads, n_bases, run_blk, run_off, run_tmp, read_runs, nullptr, sp),
                         "run count kernels");
                 sem.read_runs = read_runs;
             } else {
-                S2K_TRY(hipMemsetAsync(tile_heads, 0, n_tiles * sizeof(uint32_t), st), "memset tile head words");
+                S2K_TRY(hipMemsetAsync(tile_heads, 0, n_tiles * sizeof(uint32_t), sp), "memset tile head words");
                 sem.tile_heads = tile_heads;
             }
         }
@@ -556,99 +641,77 @@ s2k_status enqueue(s2k_ctx *ctx) {
             dz.o_mn_jend = o.mn_jend;
             dz.o_mn_hash = o.mn_hash;
             dz.xor_shards = (unsigned long long *)ctx->d_xor;
-            if (tm) S2K_TRY(hipEventRecord(ctx->ev[1], st), "event");
-            if (n_chunks == 1) {
-                S2K_TRY(launch_tile_minimizers(c.d_bases, c.d_read_off, n_reads, n_bases, n_tiles, tile_read0, sem, rec, pool_cursor, nullptr,
-                                               nullptr, nullptr, ctx->d_counts, &dz, 0, st),
+            if (tm) S2K_TRY(hipEventRecord(ctx->ev[1], sp), "event");
+            if (tm && n_chunks > 1) S2K_TRY(hipEventRecord(ctx->ev[3], sk), "event");
+            // Every minimizer kernel on P; chunk c's scan and k-min-mer kernel on sk, beside the minimizer kernel of chunk c+1.  (A chunk boundary
+            // costs ~40 us -- the waves of a persistent launch run dry within a tile time or two of each other, then the launch and the first tile's
+            // unhidden load: 0.22 ms of 6.6 for six chunks, profiles/r04_chunk_boundaries.txt.  Alternating the chunks between two streams, so that
+            // the blocks of chunk c+1 take every CU its block of chunk c has left, was measured SLOWER, 7.30 vs 7.09 ms per step:
+            // profiles/r04_ab_tile_streams.txt.)
+            // (equal chunks: tapering the last ones -- their k-min-mer kernel is the one nothing runs beside -- measured no better)
+            for (uint32_t ch = 0; ch < n_chunks; ch++) {
+                // chunk boundaries: equal chunks, or (S2K_DESC_TAIL = fraction of the tiles in the LAST chunk, whose k-min-mer stage nothing
+                // runs beside) the chunks before it share the rest equally
+                auto cut = [&](uint32_t i) -> uint64_t {
+                    static const double tail = getenv("S2K_DESC_TAIL") ? atof(getenv("S2K_DESC_TAIL")) : 0.0;
+                    if (i >= n_chunks) return n_tiles;
+                    if (tail <= 0.0 || tail >= 1.0 || n_chunks < 2) return n_tiles * i / n_chunks;
+                    return (uint64_t)((double)n_tiles * (1.0 - tail) * (double)i / (double)(n_chunks - 1));
+                };
+                const uint64_t T0 = cut(ch), T1 = cut(ch + 1);
+                const bool last = ch + 1 == n_chunks;
+                S2K_TRY(launch_tile_minimizers(c.d_bases, c.d_read_off, n_reads, n_bases, T1, tile_read0, sem, rec,
+                                               pool_cursor + (size_t)CURSOR_WORDS * ch, nullptr, nullptr, nullptr, ctx->d_counts, &dz, T0, sp),
                         "tiled minimizer kernel");
-                S2K_TRY(hipEventRecord(ctx->tiles_done, st), "event");
-                ctx->tiles_done_valid = true;
-                if (tm) S2K_TRY(hipEventRecord(ctx->ev[2], st), "event");
-                if (tm) S2K_TRY(hipEventRecord(ctx->ev[3], st), "event");
-                S2K_TRY(launch_desc_scan(0, n_tiles, dz, d_scan, ctx->d_counts, st), "tile word scan");
-                // (alone: the Regular family's minimizer kernel -- this context's or a chained one's -- uses the whole LDS of a CU: none of its blocks is ever
-                // resident beside a block of this kernel, whatever that one's size)
-                S2K_TRY(launch_desc_kminmers(0, n_tiles, n_tiles, n_reads, dz, rec, ctx->d_counts, st, true), "k-min-mer kernel");
-                if (tm) S2K_TRY(hipEventRecord(ctx->ev[4], st), "event");
-            } else {
-                // fork: the second stream starts behind everything that is in the caller's stream so far
-                if (!ctx->s_km) S2K_TRY(hipStreamCreateWithFlags(&ctx->s_km, hipStreamNonBlocking), "stream create");
-                while (ctx->chunk_ev.size() < (size_t)n_chunks + 2) {
-                    hipEvent_t e;
-                    S2K_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), "event create");
-                    ctx->chunk_ev.push_back(e);
+                if (last) {
+                    S2K_TRY(hipEventRecord(ctx->tiles_done, sp), "event");
+                    ctx->tiles_done_valid = true;
+                    if (tm) S2K_TRY(hipEventRecord(ctx->ev[2], sp), "event");
                 }
-                hipStream_t s2 = ctx->s_km;
-                S2K_TRY(hipEventRecord(ctx->chunk_ev[n_chunks], st), "event");
-                S2K_TRY(hipStreamWaitEvent(s2, ctx->chunk_ev[n_chunks], 0), "stream wait");
-                if (tm) S2K_TRY(hipEventRecord(ctx->ev[3], s2), "event");
-                // (Every minimizer kernel on the caller's stream.  A chunk boundary costs ~40 us -- the waves of a persistent launch run dry
-                // within a tile time or two of each other, then the launch and the first tile's unhidden load: 0.22 ms of 6.6 for six chunks,
-                // profiles/r04_chunk_boundaries.txt.  Alternating the chunks between two streams, so that the blocks of chunk c+1 take every
-                // CU its block of chunk c has left, was measured SLOWER, 7.30 vs 7.09 ms per step: profiles/r04_ab_tile_streams.txt.)
-                // (equal chunks: tapering the last ones -- their k-min-mer kernel is the one nothing runs beside -- measured no better)
-                for (uint32_t ch = 0; ch < n_chunks; ch++) {
-                    // chunk boundaries: equal chunks, or (S2K_DESC_TAIL = fraction of the tiles in the LAST chunk, whose k-min-mer stage nothing
-                    // runs beside) the chunks before it share the rest equally
-                    auto cut = [&](uint32_t i) -> uint64_t {
-                        static const double tail = getenv("S2K_DESC_TAIL") ? atof(getenv("S2K_DESC_TAIL")) : 0.0;
-                        if (i >= n_chunks) return n_tiles;
-                        if (tail <= 0.0 || tail >= 1.0 || n_chunks < 2) return n_tiles * i / n_chunks;
-                        return (uint64_t)((double)n_tiles * (1.0 - tail) * (double)i / (double)(n_chunks - 1));
-                    };
-                    const uint64_t T0 = cut(ch), T1 = cut(ch + 1);
-                    hipStream_t ts = st;
-                    S2K_TRY(launch_tile_minimizers(c.d_bases, c.d_read_off, n_reads, n_bases, T1, tile_read0, sem, rec,
-                                                   pool_cursor + (size_t)CURSOR_WORDS * ch, nullptr, nullptr, nullptr, ctx->d_counts, &dz, T0, ts),
-                            "tiled minimizer kernel");
-                    S2K_TRY(hipEventRecord(ctx->chunk_ev[ch], ts), "event");
-                    S2K_TRY(hipStreamWaitEvent(s2, ctx->chunk_ev[ch], 0), "stream wait");
+                S2K_TRY(hipEventRecord(ctx->chunk_ev[ch], sp), "event");
+                S2K_TRY(hipStreamWaitEvent(sk, ctx->chunk_ev[ch], 0), "stream wait");
+                if (tm && n_chunks == 1) S2K_TRY(hipEventRecord(ctx->ev[3], sk), "event");
 #ifdef S2K_DEBUG_KNOBS // S2K_DEBUG_NOKM=1: the chunked minimizer kernels alone (what do the launch boundaries cost?); results are wrong
-                    static const bool nokm = getenv("S2K_DEBUG_NOKM") != nullptr;
-                    if (nokm) continue;
+                static const bool nokm = getenv("S2K_DEBUG_NOKM") != nullptr;
+                if (nokm) continue;
 #endif
-                    S2K_TRY(launch_desc_scan(T0, T1, dz, d_scan, ctx->d_counts, s2), "tile word scan");
-                    // (the last chunk's k-min-mer kernel has the device to itself unless a chained context's next call follows: staged stores,
-                    // +0.3 % for an unchained call, profiles/r06_chunks_prio_sweep.txt)
-                    S2K_TRY(launch_desc_kminmers(T0, T1, n_tiles, n_reads, dz, rec, ctx->d_counts, s2, ch + 1 == n_chunks && !chained), "k-min-mer kernel");
-                }
-                S2K_TRY(hipEventRecord(ctx->tiles_done, st), "event");
-                ctx->tiles_done_valid = true;
-                if (tm) S2K_TRY(hipEventRecord(ctx->ev[2], st), "event");
-                if (tm) S2K_TRY(hipEventRecord(ctx->ev[4], s2), "event");
-                // join: what follows in the caller's stream (finalize, the next call) comes after the last k-min-mer kernel
-                S2K_TRY(hipEventRecord(ctx->chunk_ev[n_chunks + 1], s2), "event");
-                S2K_TRY(hipStreamWaitEvent(st, ctx->chunk_ev[n_chunks + 1], 0), "stream wait");
+                S2K_TRY(launch_desc_scan(T0, T1, dz, d_scan, ctx->d_counts, sk), "tile word scan");
+                // (staged stores for the last chunk's k-min-mer kernel when nothing runs beside it: +0.3 % for an unchained call,
+                // profiles/r06_chunks_prio_sweep.txt.  A chained Hpc call's runs beside the next call's first minimizer kernel; the Regular family's
+                // minimizer kernel uses the whole LDS of a CU, so no block of this kernel is ever resident beside it, chained or not.)
+                S2K_TRY(launch_desc_kminmers(T0, T1, n_tiles, n_reads, dz, rec, ctx->d_counts, sk, last && !(chained && c.sem.hpc)), "k-min-mer kernel");
             }
+            if (tm) S2K_TRY(hipEventRecord(ctx->ev[4], sk), "event");
             S2K_TRY(launch_finalize(ctx->d_counts, ctx->d_xor, (const uint64_t *)&d_state[n_tiles].gmn, (const uint64_t *)&d_state[n_tiles].g,
-                                    o.km_capacity, o.mn_capacity, st),
+                                    o.km_capacity, o.mn_capacity, sk),
                     "finalize kernel");
-            S2K_TRY(hipMemcpyAsync(ctx->h_counts, ctx->d_counts, sizeof(Counts), hipMemcpyDeviceToHost, st), "counts copy");
-            if (tm) S2K_TRY(hipEventRecord(ctx->ev[5], st), "event");
+            S2K_TRY(hipMemcpyAsync(ctx->h_counts, ctx->d_counts, sizeof(Counts), hipMemcpyDeviceToHost, sk), "counts copy");
+            if (tm) S2K_TRY(hipEventRecord(ctx->ev[5], sk), "event");
+            S2K_TRY(mark_done(ctx), "event");
             ctx->pending = true;
             return S2K_OK;
         }
-        if (tm) S2K_TRY(hipEventRecord(ctx->ev[1], st), "event");
+        if (tm) S2K_TRY(hipEventRecord(ctx->ev[1], sp), "event");
         S2K_TRY(launch_tile_minimizers(c.d_bases, c.d_read_off, n_reads, n_bases, n_tiles, tile_read0, sem, rec, pool_cursor,
-                                       tile_rec_off, tile_cnt, mn_cnt, ctx->d_counts, nullptr, 0, st),
+                                       tile_rec_off, tile_cnt, mn_cnt, ctx->d_counts, nullptr, 0, sp),
                 "tiled minimizer kernel");
-        S2K_TRY(hipEventRecord(ctx->tiles_done, st), "event");
-        ctx->tiles_done_valid = true;
-        if (tm) S2K_TRY(hipEventRecord(ctx->ev[2], st), "event");
-        S2K_TRY(launch_scan_u32(tile_cnt, n_tiles, tile_goff, scan_tmp, 0, st), "scan");
-        S2K_TRY(launch_scan_u32(mn_cnt, n_reads, mn_off, scan_tmp, 0, st), "scan");
+        s2k_status hs = hand_over();
+        if (hs != S2K_OK) return hs;
+        S2K_TRY(launch_scan_u32(tile_cnt, n_tiles, tile_goff, scan_tmp, 0, sk), "scan");
+        S2K_TRY(launch_scan_u32(mn_cnt, n_reads, mn_off, scan_tmp, 0, sk), "scan");
     }
-    S2K_TRY(launch_scan_u32(mn_cnt, n_reads, o.km_off, scan_tmp, c.sem.k, st), "scan");
-    if (tm) S2K_TRY(hipEventRecord(ctx->ev[3], st), "event");
+    S2K_TRY(launch_scan_u32(mn_cnt, n_reads, o.km_off, scan_tmp, c.sem.k, sk), "scan");
+    if (tm) S2K_TRY(hipEventRecord(ctx->ev[3], sk), "event");
     S2K_TRY(launch_kminmers(n_tiles, tile_rec_off, tile_cnt, tile_goff, rec, mn_off, o.km_off, c.sem.k, o.km_capacity, o.hash,
                             o.start, o.end, o.rev, o.mn_capacity, o.mn_capacity ? o.mn_j : nullptr, o.mn_jend, o.mn_hash,
-                            ctx->d_xor, ctx->d_counts, st),
+                            ctx->d_xor, ctx->d_counts, sk),
             "k-min-mer kernel");
-    if (tm) S2K_TRY(hipEventRecord(ctx->ev[4], st), "event");
-    S2K_TRY(launch_finalize(ctx->d_counts, ctx->d_xor, mn_off + n_reads, o.km_off + n_reads, o.km_capacity, o.mn_capacity, st),
+    if (tm) S2K_TRY(hipEventRecord(ctx->ev[4], sk), "event");
+    S2K_TRY(launch_finalize(ctx->d_counts, ctx->d_xor, mn_off + n_reads, o.km_off + n_reads, o.km_capacity, o.mn_capacity, sk),
             "finalize kernel");
-    S2K_TRY(hipMemcpyAsync(ctx->h_counts, ctx->d_counts, sizeof(Counts), hipMemcpyDeviceToHost, st), "counts copy");
-    if (tm) S2K_TRY(hipEventRecord(ctx->ev[5], st), "event");
+    S2K_TRY(hipMemcpyAsync(ctx->h_counts, ctx->d_counts, sizeof(Counts), hipMemcpyDeviceToHost, sk), "counts copy");
+    if (tm) S2K_TRY(hipEventRecord(ctx->ev[5], sk), "event");
+    S2K_TRY(mark_done(ctx), "event");
     ctx->pending = true;
     return S2K_OK;
 }
@@ -659,7 +722,7 @@ s2k_status finish(s2k_ctx *ctx, s2k_counts *counts) {
         return ctx->pending_status;
     }
     for (int attempt = 0; attempt < 4; attempt++) {
-        S2K_TRY(hipStreamSynchronize(ctx->stream), "stream synchronize");
+        S2K_TRY(hipEventSynchronize(ctx->done_ev), "event synchronize"); // (the call's own event: never a wait on a stream other contexts share)
         ctx->pending = false;
         Counts *h = ctx->h_counts;
         Call &c = ctx->call;
@@ -800,8 +863,9 @@ s2k_ctx *s2k_create(int device, s2k_status *status) {
         return nullptr;
     }
     ctx->device = device;
-    bool ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess;
-    ctx->own_stream = ok;
+    // (no stream of its own: the device's pipeline pair is taken on first use, ensure_pipes)
+    bool ok = hipEventCreateWithFlags(&ctx->done_ev, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&ctx->entry_ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMalloc((void **)&ctx->d_counts, CTRL_CURSORS_OFF + (size_t)CURSOR_WORDS * MAX_DESC_CHUNKS * sizeof(uint64_t)) == hipSuccess;
     if (ok) {
         ctx->d_xor = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->d_counts) + CTRL_XOR_OFF);
@@ -841,7 +905,9 @@ void s2k_destroy(s2k_ctx *ctx) {
         }
     }
     (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    // the context's own last work, on P and on its stream (events: the pair may be busy with other contexts' calls)
+    if (ctx->tiles_done_valid) (void)hipEventSynchronize(ctx->tiles_done);
+    if (ctx->has_pipes) (void)s2k::ctx_sync(ctx);
     ctx->ws.release();
     ctx->in_bases.release();
     ctx->realign.release();
@@ -851,7 +917,6 @@ void s2k_destroy(s2k_ctx *ctx) {
     ctx->in_off2.release();
     ctx->outbuf2.release();
     ctx->count_tab.release();
-    if (ctx->s_km) (void)hipStreamDestroy(ctx->s_km);
     if (ctx->tiles_done) (void)hipEventDestroy(ctx->tiles_done);
     for (hipEvent_t e : ctx->chunk_ev) (void)hipEventDestroy(e);
     if (ctx->s_in) (void)hipStreamDestroy(ctx->s_in);
@@ -859,20 +924,32 @@ void s2k_destroy(s2k_ctx *ctx) {
     if (ctx->d_counts) (void)hipFree(ctx->d_counts); // (d_xor and d_cursors lie inside it)
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
     for (hipEvent_t e : ctx->evs) (void)hipEventDestroy(e);
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    if (ctx->done_ev) (void)hipEventDestroy(ctx->done_ev);
+    if (ctx->entry_ev) (void)hipEventDestroy(ctx->entry_ev);
+    if (ctx->has_pipes) { // the last context of the device takes the pair with it
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        PipePair &pp = g_pipes[ctx->device];
+        if (--pp.refs == 0) {
+            (void)hipStreamDestroy(pp.p);
+            (void)hipStreamDestroy(pp.k);
+            pp = PipePair();
+        }
+    }
     delete ctx;
 }
 
 s2k_status s2k_set_stream(s2k_ctx *ctx, void *hip_stream) {
-    // (the descriptor path's second stream forks from and joins this one with events, call by call)
+    // (the minimizer kernels stay on the device's P, which waits for this stream at the start of every call; the rest of a call runs here)
     if (!ctx) return S2K_ERR_INVALID_ARG;
     if (ctx->pending) {
         s2k_status st = finish(ctx, nullptr);
         (void)st;
     }
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    S2K_TRY(hipSetDevice(ctx->device), "set device");
+    if (ctx->has_pipes) S2K_TRY(s2k::ctx_sync(ctx), "event synchronize"); // (work left on the old stream, e.g. a synth kernel)
     ctx->stream = (hipStream_t)hip_stream;
-    ctx->own_stream = false;
+    ctx->user_stream = true;
+    ctx->done_valid = false;
     return S2K_OK;
 }
 
@@ -938,6 +1015,7 @@ s2k_status s2k_extract_device(s2k_ctx *ctx, const uint8_t *d_bases, const uint64
     if (n_reads >= 0xFFFFFFFFull) return fail(ctx, S2K_ERR_INVALID_ARG, "too many reads in one call");
     if (out->mn_capacity && !(out->mn_j && out->mn_jend && out->mn_hash)) return fail(ctx, S2K_ERR_INVALID_ARG, "mn_capacity set but minimizer arrays missing");
     S2K_TRY(hipSetDevice(ctx->device), "set device");
+    S2K_TRY(ensure_pipes(ctx), "stream create");
     Call &c = ctx->call;
     c = Call();
     s2k_status st = resolve_sem(ctx, params, &c.sem, &c.bound);
@@ -960,6 +1038,7 @@ s2k_status s2k_extract_device(s2k_ctx *ctx, const uint8_t *d_bases, const uint64
     if (!c.serial && n_bases && (((uintptr_t)d_bases) & 15u) != 0) {
         S2K_TRY(ctx->realign.ensure(n_bases + 256), "aligned copy of a misaligned input stream");
         S2K_TRY(hipMemcpyAsync(ctx->realign.p, d_bases, n_bases, hipMemcpyDeviceToDevice, ctx->stream), "realign copy");
+        S2K_TRY(mark_done(ctx), "event"); // (the minimizer kernels on P read the copy)
         c.d_bases = (const uint8_t *)ctx->realign.p;
     }
     c.pool_cap = c.serial ? pool_estimate(n_bases, n_reads, params->density, c.sem.hpc) : overflow_estimate(n_bases, params->density);
@@ -980,7 +1059,7 @@ s2k_status s2k_trim(s2k_ctx *ctx) {
     }
     (void)ctx->host_pool->trim();
     S2K_TRY(hipSetDevice(ctx->device), "set device");
-    S2K_TRY(hipStreamSynchronize(ctx->stream), "stream synchronize");
+    if (ctx->has_pipes) S2K_TRY(s2k::ctx_sync(ctx), "event synchronize");
     for (DevBuf *b : {&ctx->ws, &ctx->in_bases, &ctx->in_off, &ctx->outbuf, &ctx->realign, &ctx->in_bases2, &ctx->in_off2, &ctx->outbuf2, &ctx->count_tab})
         b->release();
     return S2K_OK;
@@ -988,6 +1067,8 @@ s2k_status s2k_trim(s2k_ctx *ctx) {
 
 s2k_status s2k_sync(s2k_ctx *ctx, s2k_counts *counts) {
     if (!ctx) return S2K_ERR_INVALID_ARG;
+    // (no call pending: the context's last work without results, e.g. a synth kernel -- its own event, not the stream it shares)
+    if (!ctx->pending && ctx->done_valid) S2K_TRY(hipEventSynchronize(ctx->done_ev), "event synchronize");
     return finish(ctx, counts);
 }
 
@@ -1184,6 +1265,7 @@ s2k_status s2k_extract(s2k_ctx *ctx, const uint8_t *bases, const uint64_t *read_
     const uint64_t first = read_off[0], n_bases = read_off[n_reads] - first;
     if (n_bases && !bases) return fail(ctx, S2K_ERR_INVALID_ARG, "bases is NULL");
     S2K_TRY(hipSetDevice(ctx->device), "set device");
+    S2K_TRY(ensure_pipes(ctx), "stream create");
     if (ctx->pending) (void)finish(ctx, nullptr);
 #ifdef S2K_DEBUG_KNOBS // wall time of this call on stderr (tools/pcie_trace.sh with a KNOBS build)
     const bool trace = getenv("S2K_TRACE_EXTRACT") != nullptr;
@@ -1203,11 +1285,10 @@ s2k_status s2k_extract(s2k_ctx *ctx, const uint8_t *bases, const uint64_t *read_
         cut.push_back(n_reads);
     }
     const size_t B = cut.size() - 1;
-    if (B > 1) {
-        if (!ctx->s_in) S2K_TRY(hipStreamCreateWithFlags(&ctx->s_in, hipStreamNonBlocking), "stream create");
-    }
+    // (the H2D always goes on s_in, which the host waits for: the context's stream may be the device's shared K)
+    if (!ctx->s_in) S2K_TRY(hipStreamCreateWithFlags(&ctx->s_in, hipStreamNonBlocking), "stream create");
     if (!ctx->s_out) S2K_TRY(hipStreamCreateWithFlags(&ctx->s_out, hipStreamNonBlocking), "stream create");
-    hipStream_t s_in = B > 1 ? ctx->s_in : ctx->stream;
+    hipStream_t s_in = ctx->s_in;
 
     // ---- the result arrays, sized by the estimate for the whole call (they grow if it was too small) -----------------
     const bool want_mn = params->flags & S2K_FLAG_WANT_MINIMIZERS;
@@ -1249,7 +1330,8 @@ s2k_status s2k_extract(s2k_ctx *ctx, const uint8_t *bases, const uint64_t *read_
             dr.close();
             consumer.join();
         }
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)s2k::ctx_sync(ctx);
+        if (ctx->tiles_done_valid) (void)hipEventSynchronize(ctx->tiles_done);
         ctx->pending = false;
         delete ow;
         memset(res, 0, sizeof *res);
@@ -1353,7 +1435,9 @@ void s2k_result_free(s2k_result *res) {
 s2k_status s2k_synth_bases_device(s2k_ctx *ctx, uint64_t seed, uint64_t first_base, uint64_t n, uint8_t *d_bases) {
     if (!ctx || (!d_bases && n)) return S2K_ERR_INVALID_ARG;
     S2K_TRY(hipSetDevice(ctx->device), "set device");
+    S2K_TRY(ensure_pipes(ctx), "stream create");
     S2K_TRY(launch_synth(seed, first_base, n, d_bases, ctx->stream), "synth kernel");
+    S2K_TRY(mark_done(ctx), "event"); // (a call of this context on P that reads the bases waits for it)
     return S2K_OK;
 }
 
@@ -1365,7 +1449,9 @@ void s2k_synth_hifi_lengths(uint64_t seed, uint64_t r0, uint64_t n_reads, uint64
 s2k_status s2k_synth_hifi_device(s2k_ctx *ctx, uint64_t seed, uint64_t r0, uint64_t n_reads, const uint64_t *d_read_off, uint8_t *d_bases) {
     if (!ctx || ((!d_read_off || !d_bases) && n_reads)) return S2K_ERR_INVALID_ARG;
     S2K_TRY(hipSetDevice(ctx->device), "set device");
+    S2K_TRY(ensure_pipes(ctx), "stream create");
     S2K_TRY(launch_synth_hifi(seed, r0, n_reads, d_read_off, d_bases, ctx->stream), "synth hifi kernel");
+    S2K_TRY(mark_done(ctx), "event");
     return S2K_OK;
 }
 
@@ -1382,6 +1468,7 @@ s2k_status s2k_hpc_device_ex(s2k_ctx *ctx, const uint8_t *d_bases, const uint64_
     if (flags & ~(uint32_t)S2K_HPC_RLE_ALPHABET) return fail(ctx, S2K_ERR_INVALID_ARG, "unknown s2k_hpc_device_ex flag");
     const bool rle = (flags & S2K_HPC_RLE_ALPHABET) != 0; // encode_rle: only ACTGactgNn collapse (src/hpc.rs:14)
     S2K_TRY(hipSetDevice(ctx->device), "set device");
+    S2K_TRY(ensure_pipes(ctx), "stream create");
     if (ctx->pending) (void)finish(ctx, nullptr);
     // segment-parallel path: 16-byte vector loads, so a misaligned stream is first copied to an aligned buffer
     if (n_reads && n_bases && ((uintptr_t)d_bases & 15) != 0) {
@@ -1394,7 +1481,7 @@ s2k_status s2k_hpc_device_ex(s2k_ctx *ctx, const uint8_t *d_bases, const uint64_
         S2K_TRY(launch_validate_read_off(d_read_off, n_reads, n_bases, &ctx->d_counts->bad_input, ctx->stream), "read table validation");
         uint32_t bad = 0;
         S2K_TRY(hipMemcpyAsync(&bad, &ctx->d_counts->bad_input, sizeof bad, hipMemcpyDeviceToHost, ctx->stream), "D2H");
-        S2K_TRY(hipStreamSynchronize(ctx->stream), "stream synchronize");
+        S2K_TRY(s2k::ctx_sync(ctx), "event synchronize");
         if (bad & ~(uint32_t)BAD_LONG) return fail(ctx, S2K_ERR_INVALID_ARG, "d_read_off must start at 0, be non-decreasing and end at n_bases");
         if (bad) return fail(ctx, S2K_ERR_READ_TOO_LONG, "a read is longer than 2^32-2 bases");
     }
@@ -1435,7 +1522,7 @@ s2k_status s2k_hpc_device_ex(s2k_ctx *ctx, const uint8_t *d_bases, const uint64_
         uint64_t total1 = 0;
         S2K_TRY(hipMemcpyAsync(&failed, fail_word, sizeof failed, hipMemcpyDeviceToHost, ctx->stream), "D2H");
         S2K_TRY(hipMemcpyAsync(&total1, d_hpc_off + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream), "D2H");
-        S2K_TRY(hipStreamSynchronize(ctx->stream), "sync");
+        S2K_TRY(s2k::ctx_sync(ctx), "event synchronize");
         if (!failed) {
             if (n_runs) *n_runs = total1;
             return total1 > capacity && (d_hpc || d_pos) ? S2K_ERR_CAPACITY : S2K_OK;
@@ -1456,7 +1543,7 @@ s2k_status s2k_hpc_device_ex(s2k_ctx *ctx, const uint8_t *d_bases, const uint64_
     }
     uint64_t total = 0;
     S2K_TRY(hipMemcpyAsync(&total, d_hpc_off + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream), "D2H");
-    S2K_TRY(hipStreamSynchronize(ctx->stream), "sync");
+    S2K_TRY(s2k::ctx_sync(ctx), "event synchronize");
     if (n_runs) *n_runs = total;
     return total > capacity && (d_hpc || d_pos) ? S2K_ERR_CAPACITY : S2K_OK;
 }

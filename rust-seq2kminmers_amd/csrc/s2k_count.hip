@@ -165,7 +165,7 @@ s2k_status s2k_count_device(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n, ui
     }
     unsigned long long total = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&total, cursor, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = ctx_sync(ctx);
     if (e != hipSuccess) {
         ctx_set_error(ctx, "s2k_count_device: HIP error");
         return S2K_ERR_DEVICE;
@@ -192,7 +192,7 @@ s2k_status s2k_partition_device(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n
         hipLaunchKernelGGL(part_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_hash, n, n_parts, ws + S2K_MAX_PARTS, d_out);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = ctx_sync(ctx);
     if (e != hipSuccess) {
         ctx_set_error(ctx, "s2k_partition_device: HIP error");
         return S2K_ERR_DEVICE;

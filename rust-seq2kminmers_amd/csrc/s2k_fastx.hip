@@ -310,7 +310,7 @@ s2k_status s2k_fastx_parse_device(s2k_ctx *ctx, const uint8_t *d_text, uint64_t 
         rc = S2K_ERR_NOMEM;
     if (rc == S2K_OK && (s2k::fx_parse_count(d_text, n_bytes, format == S2K_FASTQ, ws, d_tot, st) != hipSuccess ||
                          hipMemcpyAsync(h_tot, d_tot, sizeof h_tot, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipStreamSynchronize(st) != hipSuccess))
+                         s2k::ctx_sync(ctx) != hipSuccess))
         rc = S2K_ERR_DEVICE;
     if (rc == S2K_OK) {
         *n_reads = h_tot[0];
@@ -322,7 +322,7 @@ s2k_status s2k_fastx_parse_device(s2k_ctx *ctx, const uint8_t *d_text, uint64_t 
             rc = S2K_ERR_CAPACITY; // *n_reads / *n_bases hold what is needed
         } else if (s2k::fx_parse_write(d_text, n_bytes, format == S2K_FASTQ, ws, d_tot, d_bases, bases_capacity, d_read_off,
                                        off_capacity, st) != hipSuccess ||
-                   hipStreamSynchronize(st) != hipSuccess)
+                   s2k::ctx_sync(ctx) != hipSuccess)
             rc = S2K_ERR_DEVICE;
     }
     if (ws) (void)hipFree(ws);
@@ -506,7 +506,7 @@ s2k_status s2k_run_file(s2k_ctx *ctx, const char *path, const s2k_params *params
         }
         st = collect(); // previous batch done (its kernels ran while this one was staged and split)
         if (st != S2K_OK) break;
-        if (hipStreamWaitEvent(s2k::ctx_stream(ctx), parsed, 0) != hipSuccess) {
+        if (hipStreamWaitEvent(s2k::ctx_stream(ctx), parsed, 0) != hipSuccess || s2k::ctx_mark(ctx) != hipSuccess) {
             st = S2K_ERR_DEVICE;
             break;
         }

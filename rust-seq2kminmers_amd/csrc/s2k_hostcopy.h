@@ -87,6 +87,10 @@ struct s2k_ctx;
 namespace s2k { // context internals shared inside the library (defined in s2k_api.hip)
 HostStager &ctx_stager(s2k_ctx *c);
 hipStream_t ctx_stream(s2k_ctx *c);
+// records the context's done event behind what is on its stream so far (work on it that a later call's minimizer kernels must see)
+hipError_t ctx_mark(s2k_ctx *c);
+// ctx_mark, then the host waits for that event (never a synchronize of a stream other contexts share)
+hipError_t ctx_sync(s2k_ctx *c);
 int ctx_device(s2k_ctx *c);
 void ctx_set_error(s2k_ctx *c, const char *what);
 // grow-only device buffer of the context for s2k_count_device / s2k_partition_device (nullptr: allocation failed)

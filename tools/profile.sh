@@ -1,27 +1,29 @@
 #!/bin/bash
-# usage (on the GPU box, from the repo root): tools/profile.sh <tag>
+# usage (on a machine with the GPU): tools/profile.sh <tag>; results under build/prof_<tag> in the repository (build/ is not tracked)
 # For each scalar HashMode (hpc = the headline, regular):
-#  1. rocprofv3 --kernel-trace --stats of the bench command            -> gpurun_out/prof_<tag>/<mode>/stats
+#  1. rocprofv3 --kernel-trace --stats of the bench command            -> build/prof_<tag>/<mode>/stats
 #  2. separate PMC passes (FETCH_SIZE / WRITE_SIZE / SQ sets), kernel-trace only, as the pool requires -> .../pmc
 # and a traffic.json with the HBM bytes of ALL kernels of a step (FETCH_SIZE x2 on gfx950 per MI355X_MICROARCH.md, WRITE_SIZE exact).
+# Every GPU step has its own time limit, and the first one that fails (a fault, an abort, a limit) ends the script: nothing else starts on the GPU.
 tag=$1
-out=$GRAFT_REPO_ROOT/gpurun_out/prof_$tag
+root=$(cd "$(dirname "$0")/.." && pwd)
+out=$root/build/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for mode in hpc regular; do
   args="--mode $mode --contexts 1 --no-other-mode --no-cpu-baseline --no-end-to-end --verify-reads 0"
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$mode/stats -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 $args > $out/$mode.stats.log 2>&1 || echo "stats pass failed ($mode)"
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$mode/stats -- python3 $root/bench.py --steps 5 --warmup 2 $args > $out/$mode.stats.log 2>&1 || { echo "stats pass failed ($mode)"; exit 1; }
   i=0
   for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAVES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    timeout -k 10 400 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out/$mode/pmc/p$i -- python3 $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 $args > $out/$mode.pmc_p$i.log 2>&1 || echo "pmc pass $i failed ($mode)"
+    timeout -k 10 400 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out/$mode/pmc/p$i -- python3 $root/bench.py --steps 2 --warmup 1 $args > $out/$mode.pmc_p$i.log 2>&1 || { echo "pmc pass $i failed ($mode)"; exit 1; }
   done
 done
 # the headline configuration itself (two chained contexts): kernel stats + trace, so that chunks x kernel time <= ms_per_step can be checked for `value`
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/hpc2ctx/stats -- python3 $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --mode hpc --contexts 2 --no-other-mode --no-cpu-baseline --no-end-to-end --verify-reads 0 > $out/hpc2ctx.stats.log 2>&1 || echo "stats pass failed (two contexts)"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/hpc2ctx/stats -- python3 $root/bench.py --steps 6 --warmup 2 --mode hpc --contexts 2 --no-other-mode --no-cpu-baseline --no-end-to-end --verify-reads 0 > $out/hpc2ctx.stats.log 2>&1 || { echo "stats pass failed (two contexts)"; exit 1; }
 # the same two commands unprofiled, on this box: what the profiler itself costs
-python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --mode hpc --contexts 1 --no-other-mode --no-cpu-baseline --no-end-to-end --verify-reads 0 > $out/hpc.unprofiled.log 2>&1
-python3 $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --mode hpc --contexts 2 --no-other-mode --no-cpu-baseline --no-end-to-end --verify-reads 0 > $out/hpc2ctx.unprofiled.log 2>&1
+timeout -k 10 300 python3 $root/bench.py --steps 5 --warmup 2 --mode hpc --contexts 1 --no-other-mode --no-cpu-baseline --no-end-to-end --verify-reads 0 > $out/hpc.unprofiled.log 2>&1 || { echo "unprofiled run failed (one context)"; exit 1; }
+timeout -k 10 300 python3 $root/bench.py --steps 6 --warmup 2 --mode hpc --contexts 2 --no-other-mode --no-cpu-baseline --no-end-to-end --verify-reads 0 > $out/hpc2ctx.unprofiled.log 2>&1 || { echo "unprofiled run failed (two contexts)"; exit 1; }
 python3 - <<PY
 import csv, glob, json, collections, os
 out = "$out"
@@ -62,7 +64,7 @@ for mode in ("hpc", "regular"):
             sq[c] = sq.get(c, 0.0) + vals.get(c, 0.0) * calls_per_step
     open(out + "/%s_pmc_summary.txt" % mode, "w").write("\n".join(lines) + "\n")
     import sys
-    sys.path.insert(0, os.environ["GRAFT_REPO_ROOT"])
+    sys.path.insert(0, "$root")
     import bench  # kernel_source_id(): the state of the device sources these counters were collected on (bench.py refuses a stale file)
     res[mode] = {"mode": mode, "n_bases": 10000000000, "kernel_source_id": bench.kernel_source_id(), "hbm_bytes_per_step": int((2 * fetch + write) * 1024),
                  "fetch_size_kb_per_step": fetch, "write_size_kb_per_step": write, "kernels": per_kernel,
@@ -92,7 +94,7 @@ def trace_rows(d):
     for f in glob.glob(out + "/%s/stats/*/*kernel_trace.csv" % d):
         for r in csv.DictReader(open(f)):
             n = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void s2k::", "").replace("s2k::", "")
-            ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n))
+            ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n, r.get("Queue_Id", "?"), r.get("Stream_Id", "?")))
     return sorted(ev)
 def bench_line(log):
     try:
@@ -107,7 +109,7 @@ with open(out + "/timed_kernel_stats.txt", "w") as o:
         if bl:
             o.write("   bench line of the profiled run: ms_per_step %.3f (value %.1f), one_context %s\n" % (bl["ms_per_step"], bl["value"], bl.get("one_context")))
         by = collections.defaultdict(list)
-        for st, en, n in ev:
+        for st, en, n, _, _ in ev:
             if "tile_minimizer" in n or "desc_kminmer" in n or "desc_scan" in n or "read_table" in n or "finalize" in n:
                 by[n].append((st, en))
         for n in sorted(by):
@@ -128,11 +130,12 @@ with open(out + "/timed_kernel_stats.txt", "w") as o:
     mins = [e for e in ev if "tile_minimizer" in e[2]]
     if len(mins) >= 7:
         t0 = mins[-6][0]
-        o.write("== hpc2ctx: kernel timeline of the last two chained calls (us from the first minimizer kernel of the second-to-last call)\n")
-        for st, en, n in ev:
+        o.write("== hpc2ctx: kernel timeline of the last two chained calls (us from the first minimizer kernel of the second-to-last call; "
+                "q = hardware queue, s = HIP stream, as rocprofv3 reports them)\n")
+        for st, en, n, q, s in ev:
             if st >= t0 and ("tile_minimizer" in n or "desc_kminmer" in n or "finalize" in n or "read_table" in n):
                 tag = "MIN" if "tile_minimizer" in n else "KMM" if "desc_kminmer" in n else "FIN" if "finalize" in n else "RT "
-                o.write("   %s start %9.1f end %9.1f dur %8.1f\n" % (tag, (st - t0) / 1e3, (en - t0) / 1e3, (en - st) / 1e3))
+                o.write("   %s q%-2s s%-3s start %9.1f end %9.1f dur %8.1f\n" % (tag, q, s, (st - t0) / 1e3, (en - t0) / 1e3, (en - st) / 1e3))
     # profiler overhead: the unprofiled runs of the same commands (written by the shell below)
     for d in ("hpc", "hpc2ctx"):
         a, b = bench_line(out + "/%s.stats.log" % d), bench_line(out + "/%s.unprofiled.log" % d)
