@@ -37,6 +37,7 @@ extern "C" {
  * + s2k_trim, s2k_density_for_bound, S2K_FLAG_LEGACY_PATH; s2k_counts.path tells the descriptor path (0) from the legacy one (2).
  * (Round 4 only ADDED entry points -- the benchmark helpers s2k_synth_hifi_lengths / s2k_synth_hifi_device, and s2k_chain_after: no existing entry point or
  * struct changed, the version stays 2.)
+ * (s2k_count_device_ex and S2K_COUNT_SORTED were added later the same way: an added entry point, the version stays 2.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -211,6 +212,16 @@ s2k_status s2k_hpc_device_ex(s2k_ctx *ctx, const uint8_t *d_bases, const uint64_
  * unspecified order; *n_distinct is always set (S2K_ERR_CAPACITY when it exceeds capacity). */
 s2k_status s2k_count_device(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n, uint64_t *d_keys, uint32_t *d_counts,
                             uint64_t capacity, uint64_t *n_distinct);
+/* Counting with an abundance cutoff (what rust-mdbg keeps: the "solid" k-min-mers): the pairs (key, count) of every distinct value
+ * of d_hash[0..n) that occurs at least min_count times (min_count 0 and 1 both mean all).  With S2K_COUNT_SORTED the pairs come in
+ * ascending order of key (unsigned 64-bit) and the output is bit-identical from call to call; without it the order is unspecified.
+ * *n_distinct (distinct keys before the cutoff) and *n_kept (after it) are always set; S2K_ERR_CAPACITY when *n_kept > capacity and
+ * d_keys or d_counts is non-NULL (nothing is written then); both may be NULL (sizes only).  Every 64-bit value is a key, 0 and
+ * 2^64-1 included.  n >= 2^32 (counts are uint32_t) and unknown flag bits are refused (S2K_ERR_INVALID_ARG).  Runs on the context's
+ * stream, in the context's grow-only workspace (about 20 bytes per key); returns when the pairs are written. */
+#define S2K_COUNT_SORTED 1u /* pairs in ascending order of key (unsigned 64-bit) */
+s2k_status s2k_count_device_ex(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n, uint32_t min_count, uint32_t flags,
+                               uint64_t *d_keys, uint32_t *d_counts, uint64_t capacity, uint64_t *n_distinct, uint64_t *n_kept);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

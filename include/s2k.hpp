@@ -103,6 +103,19 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         }
         return extract(reinterpret_cast<const uint8_t *>(bases.data()), off.data(), reads.size(), l, k, density, mode, flags);
     }
+    // s2k_count_device_ex on device-resident hashes: the pairs of the keys that occur >= min_count times, in ascending key order when
+    // `sorted`; d_keys / d_counts may be nullptr (sizes only).  Throws Error(S2K_ERR_CAPACITY) when n_kept > capacity.
+    struct CountSizes {
+        uint64_t n_distinct, n_kept;
+    };
+    CountSizes count_device(const uint64_t *d_hash, uint64_t n, uint32_t min_count, bool sorted, uint64_t *d_keys = nullptr,
+                            uint32_t *d_counts = nullptr, uint64_t capacity = 0) {
+        CountSizes r{0, 0};
+        s2k_status st = s2k_count_device_ex(ctx_, d_hash, n, min_count, sorted ? S2K_COUNT_SORTED : 0u, d_keys, d_counts, capacity,
+                                            &r.n_distinct, &r.n_kept);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return r;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

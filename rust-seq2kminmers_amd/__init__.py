@@ -26,7 +26,7 @@ ABI_VERSION = 2  # include/s2k.h S2K_ABI_VERSION this mirror was written against
 ABI_SYMBOLS = [
     "s2k_trim", "s2k_density_for_bound", "s2k_abi_version", "s2k_device_count", "s2k_create", "s2k_destroy", "s2k_set_stream", "s2k_chain_after", "s2k_set_host_batch", "s2k_strerror",
     "s2k_last_error", "s2k_hash_bound", "s2k_extract", "s2k_result_free", "s2k_extract_device", "s2k_sync",
-    "s2k_hpc_device", "s2k_hpc_device_ex", "s2k_count_device", "s2k_partition_device", "s2k_synth_bases_device", "s2k_synth_hifi_lengths", "s2k_synth_hifi_device", "s2k_last_kernel_ms", "s2k_enable_timing", "s2k_timing_total", "s2k_fastx_open", "s2k_fastx_next", "s2k_fastx_close", "s2k_run_file", "s2k_fastx_parse_device",
+    "s2k_hpc_device", "s2k_hpc_device_ex", "s2k_count_device", "s2k_count_device_ex", "s2k_partition_device", "s2k_synth_bases_device", "s2k_synth_hifi_lengths", "s2k_synth_hifi_device", "s2k_last_kernel_ms", "s2k_enable_timing", "s2k_timing_total", "s2k_fastx_open", "s2k_fastx_next", "s2k_fastx_close", "s2k_run_file", "s2k_fastx_parse_device",
 ]
 
 
@@ -42,6 +42,7 @@ FLAG_FORCE_SERIAL = 2
 FLAG_LEGACY_PATH = 8  # round-2 records (16 B with the read index, per-read scans) instead of the descriptor path
 FLAG_NO_PACK2 = 4  # s2k_extract: bases as ASCII over PCIe instead of 2-bit packed + exception list
 HPC_RLE_ALPHABET = 1  # s2k_hpc_device_ex: the run rule of encode_rle (src/hpc.rs:14)
+COUNT_SORTED = 1  # s2k_count_device_ex: pairs in ascending order of key
 
 
 class S2kError(RuntimeError):
@@ -128,6 +129,8 @@ def load_library(path=None):
     L.s2k_hpc_device_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_count_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.s2k_count_device_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -333,6 +336,20 @@ class Engine:
         if st != 7 or capacity:
             self._check(st)
         return int(nd.value)
+
+    def count_device_ex(self, d_hash, n, min_count=1, sorted=True, d_keys=0, d_counts=0, capacity=0):
+        """(key, count) pairs of the distinct hashes of d_hash[0..n) that occur at least min_count times, in ascending key order
+        with sorted=True (s2k_count_device_ex); returns (n_distinct, n_kept).  Raises S2kError(7) when n_kept exceeds a non-zero
+        capacity (the exception's n_distinct / n_kept hold the sizes); no outputs asks for the sizes."""
+        nd, nk = C.c_uint64(0), C.c_uint64(0)
+        st = self.lib.s2k_count_device_ex(self.ctx, C.c_void_p(d_hash or 0), n, min_count, COUNT_SORTED if sorted else 0,
+                                          C.c_void_p(d_keys or 0), C.c_void_p(d_counts or 0), capacity, C.byref(nd), C.byref(nk))
+        try:
+            self._check(st)
+        except S2kError as e:
+            e.n_distinct, e.n_kept = int(nd.value), int(nk.value)  # set with status 7: the sizes that were needed
+            raise
+        return int(nd.value), int(nk.value)
 
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""

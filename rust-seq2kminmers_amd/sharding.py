@@ -46,7 +46,8 @@ def allreduce_counts(counts, dist=None, device=None):
 
 # ---- downstream k-min-mer counting across GPUs: the one place this path has a real exchange step ----
 class EngineCountOps:
-    """partition / count on the GPU through the C ABI (s2k_partition_device / s2k_count_device); tensors are torch CUDA tensors."""
+    """partition / count on the GPU through the C ABI (s2k_partition_device / s2k_count_device, and s2k_count_device_ex for an
+    abundance cutoff); tensors are torch CUDA tensors."""
 
     def __init__(self, eng, device):
         self.eng, self.device = eng, device
@@ -72,17 +73,37 @@ class EngineCountOps:
         nd = self.eng.count_device(keys.data_ptr() if n else 0, n, k.data_ptr(), c.data_ptr(), max(n, 1))
         return nd, k[:nd], c[:nd]
 
+    def count_ex(self, keys, min_count, want_pairs=False):
+        """-> (n_distinct, n_kept, keys, counts): the pairs of the keys that occur >= min_count times, ascending (s2k_count_device_ex)"""
+        import torch
 
-def count_kminmers(keys, ops, dist=None, collectives_on_device=True, want_pairs=False):
+        n = keys.numel()
+        torch.cuda.synchronize(self.device)
+        if not want_pairs:
+            nd, nk = self.eng.count_device_ex(keys.data_ptr() if n else 0, n, min_count)
+            return nd, nk, None, None
+        k = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        c = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        nd, nk = self.eng.count_device_ex(keys.data_ptr() if n else 0, n, min_count, True, k.data_ptr(), c.data_ptr(), max(n, 1))
+        return nd, nk, k[:nk], c[:nk]
+
+
+def count_kminmers(keys, ops, dist=None, collectives_on_device=True, want_pairs=False, min_count=1):
     """Distinct k-min-mer hashes and their multiplicities over ALL ranks.  `keys`: this rank's k-min-mer hashes (int64 view of
     the u64 values).  One rank: count locally.  Several: every rank splits its keys by hash prefix into world_size groups,
     one all-to-all (RCCL when the tensors live on the GPU) moves group p to rank p, which then owns every occurrence of its
     range of the hash space and counts it; the totals are summed with an all-reduce.
-    Returns dict(n_keys, n_distinct, n_distinct_local, keys, counts) -- keys/counts are this rank's range (want_pairs)."""
+    Returns dict(n_keys, n_distinct, n_distinct_local, keys, counts) -- keys/counts are this rank's range (want_pairs).
+    min_count > 1 keeps only the keys that occur at least min_count times over ALL ranks (ops.count_ex; keys/counts then ascend
+    by key, and the dict adds n_kept / n_kept_local).  Filtering after the exchange is exact: a rank owns every occurrence of
+    its range."""
     import torch
 
     world = dist.get_world_size() if (dist is not None and dist.is_initialized()) else 1
     if world == 1:
+        if min_count > 1:
+            nd, nk, k, c = ops.count_ex(keys, min_count, want_pairs)
+            return {"n_keys": int(keys.numel()), "n_distinct": nd, "n_distinct_local": nd, "n_kept": nk, "n_kept_local": nk, "keys": k, "counts": c}
         nd, k, c = ops.count(keys, want_pairs)
         return {"n_keys": int(keys.numel()), "n_distinct": nd, "n_distinct_local": nd, "keys": k, "counts": c}
     grouped, off = ops.partition(keys, world)
@@ -96,6 +117,12 @@ def count_kminmers(keys, ops, dist=None, collectives_on_device=True, want_pairs=
     got = torch.empty(int(recv.sum()), dtype=keys.dtype, device=cdev)
     dist.all_to_all_single(got, src, output_split_sizes=[int(x) for x in recv], input_split_sizes=[int(x) for x in send])
     got = got.to(keys.device)
+    if min_count > 1:
+        nd, nk, k, c = ops.count_ex(got, min_count, want_pairs)
+        t = torch.tensor([int(keys.numel()), nd, nk], dtype=torch.int64, device=cdev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return {"n_keys": int(t[0]), "n_distinct": int(t[1]), "n_distinct_local": nd, "n_kept": int(t[2]), "n_kept_local": nk, "keys": k,
+                "counts": c, "n_received": int(got.numel())}
     nd, k, c = ops.count(got, want_pairs)
     t = torch.tensor([int(keys.numel()), nd], dtype=torch.int64, device=cdev)
     dist.all_reduce(t, op=dist.ReduceOp.SUM)
