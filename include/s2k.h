@@ -38,6 +38,8 @@ extern "C" {
  * (Round 4 only ADDED entry points -- the benchmark helpers s2k_synth_hifi_lengths / s2k_synth_hifi_device, and s2k_chain_after: no existing entry point or
  * struct changed, the version stays 2.)
  * (s2k_count_device_ex and S2K_COUNT_SORTED were added later the same way: an added entry point, the version stays 2.)
+ * (s2k_count_merge_device, the opaque s2k_counter with s2k_counter_create / _destroy / _add / _finish, and s2k_run_file_count were
+ * added the same way: added entry points and one opaque type, the version stays 2.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -222,6 +224,33 @@ s2k_status s2k_count_device(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n, ui
 #define S2K_COUNT_SORTED 1u /* pairs in ascending order of key (unsigned 64-bit) */
 s2k_status s2k_count_device_ex(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n, uint32_t min_count, uint32_t flags,
                                uint64_t *d_keys, uint32_t *d_counts, uint64_t capacity, uint64_t *n_distinct, uint64_t *n_kept);
+/* Merge of two count tables: (a_keys, a_counts)[0..n_a) and (b_keys, b_counts)[0..n_b), each strictly ascending by key (unsigned
+ * 64-bit; every value is a key, 0 and 2^64-1 included), into the table of their union in ascending key order, a key present in both
+ * getting the sum of its counts, saturated at 2^32-1.  Pairs whose merged count is under min_count (0 and 1 both mean all) are
+ * dropped.  *n_distinct (union before the cutoff) and *n_kept are always set; outputs may both be NULL (sizes only);
+ * S2K_ERR_CAPACITY when *n_kept > capacity and an output is non-NULL (nothing written).  An input that is not strictly ascending
+ * -> S2K_ERR_INVALID_ARG, detected on the device, nothing written.  Outputs must not overlap the inputs (S2K_ERR_INVALID_ARG).
+ * With n_b == 0 the call is the cutoff filter of one table.  Runs on the context's stream; returns when the pairs are written. */
+s2k_status s2k_count_merge_device(s2k_ctx *ctx, const uint64_t *d_a_keys, const uint32_t *d_a_counts, uint64_t n_a,
+                                  const uint64_t *d_b_keys, const uint32_t *d_b_counts, uint64_t n_b, uint32_t min_count,
+                                  uint64_t *d_keys, uint32_t *d_counts, uint64_t capacity, uint64_t *n_distinct, uint64_t *n_kept);
+/* Accumulating k-min-mer count over many batches (and files): s2k_counter_add counts each batch of device-resident hashes as it
+ * arrives (s2k_count_device_ex, sorted) and keeps the per-batch tables as a stack of runs in which every run is less than half the
+ * size of the one below it (a new run is merged down while it is at least half the size of the run under it), so every key takes
+ * part in O(log(total / batch)) merges.  s2k_counter_finish merges the stack into one run, keeps it (add may go on; a second finish
+ * is one filter pass), and writes the pairs that occur at least min_count times in ascending key order.  Its output is
+ * bit-identical to s2k_count_device_ex(concatenation of everything added, min_count, S2K_COUNT_SORTED) except where counts saturate
+ * (2^32-1); sizes-only, capacity and refusal rules are those of s2k_count_device_ex.  d_hash of any length (split internally below
+ * 2^32 keys); it may be reused when add returns.  Device memory owned by the counter: about 12 B per key of each run in the stack
+ * (at most about twice the distinct keys), 12 B per key of the largest batch (scratch), and one merge target while a merge runs;
+ * the context's count workspace grows to that of the largest batch.  An add that fails leaves its batch out.  One thread at a time;
+ * destroy the counter before its context. */
+typedef struct s2k_counter s2k_counter; /* opaque */
+s2k_counter *s2k_counter_create(s2k_ctx *ctx, s2k_status *status);
+void s2k_counter_destroy(s2k_counter *c);
+s2k_status s2k_counter_add(s2k_counter *c, const uint64_t *d_hash, uint64_t n);
+s2k_status s2k_counter_finish(s2k_counter *c, uint32_t min_count, uint64_t *d_keys, uint32_t *d_counts, uint64_t capacity,
+                              uint64_t *n_distinct, uint64_t *n_kept);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */
@@ -279,6 +308,11 @@ s2k_status s2k_fastx_parse_device(s2k_ctx *ctx, const uint8_t *d_text, uint64_t 
  * (src/main.rs:65-76).  `seconds` receives the wall time of the whole call (file read included). */
 s2k_status s2k_run_file(s2k_ctx *ctx, const char *path, const s2k_params *params, uint64_t batch_bases,
                         s2k_counts *totals, double *seconds);
+/* s2k_run_file that also counts: the k-min-mer hashes of every batch are added to `counter` (s2k_counter_add) before the batch's
+ * buffers are reused; totals and seconds as s2k_run_file (seconds include the counting).  Call it on several files with one counter
+ * to count a multi-file dataset, then s2k_counter_finish.  The counter's context must be on ctx's device (S2K_ERR_INVALID_ARG). */
+s2k_status s2k_run_file_count(s2k_ctx *ctx, const char *path, const s2k_params *params, uint64_t batch_bases, s2k_counter *counter,
+                              s2k_counts *totals, double *seconds);
 
 #ifdef __cplusplus
 }

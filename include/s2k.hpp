@@ -116,10 +116,57 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return r;
     }
+    // s2k_count_merge_device: the union of two strictly ascending count tables, counts added (saturated), pairs under min_count
+    // dropped; d_keys / d_counts may be nullptr (sizes only).  Throws Error(S2K_ERR_CAPACITY) when n_kept > capacity.
+    CountSizes count_merge(const uint64_t *d_a_keys, const uint32_t *d_a_counts, uint64_t n_a, const uint64_t *d_b_keys,
+                           const uint32_t *d_b_counts, uint64_t n_b, uint32_t min_count, uint64_t *d_keys = nullptr,
+                           uint32_t *d_counts = nullptr, uint64_t capacity = 0) {
+        CountSizes r{0, 0};
+        s2k_status st = s2k_count_merge_device(ctx_, d_a_keys, d_a_counts, n_a, d_b_keys, d_b_counts, n_b, min_count, d_keys, d_counts,
+                                               capacity, &r.n_distinct, &r.n_kept);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return r;
+    }
+    // s2k_run_file_count: the file mode, each batch's k-min-mer hashes added to `counter` (a Counter of an engine on this device)
+    s2k_counts run_file_count(const char *path, const s2k_params &params, uint64_t batch_bases, s2k_counter *counter,
+                              double *seconds = nullptr) {
+        s2k_counts tot{};
+        s2k_status st = s2k_run_file_count(ctx_, path, &params, batch_bases, counter, &tot, seconds);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return tot;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:
     s2k_ctx *ctx_;
+};
+
+// Accumulating k-min-mer count (s2k_counter_*) over batches and files: add() device-resident hashes batch by batch, finish() the
+// solid pairs in ascending key order (d_keys / d_counts may be nullptr: sizes only).  Destroy it before its Engine.
+class Counter {
+  public:
+    explicit Counter(Engine &eng) : eng_(&eng) {
+        s2k_status st;
+        c_ = s2k_counter_create(eng.raw(), &st);
+        if (!c_) throw Error(st, std::string("s2k_counter_create: ") + s2k_strerror(st));
+    }
+    Counter(const Counter &) = delete;
+    Counter &operator=(const Counter &) = delete;
+    ~Counter() { s2k_counter_destroy(c_); }
+    void add(const uint64_t *d_hash, uint64_t n) { check(s2k_counter_add(c_, d_hash, n)); }
+    Engine::CountSizes finish(uint32_t min_count, uint64_t *d_keys = nullptr, uint32_t *d_counts = nullptr, uint64_t capacity = 0) {
+        Engine::CountSizes r{0, 0};
+        check(s2k_counter_finish(c_, min_count, d_keys, d_counts, capacity, &r.n_distinct, &r.n_kept));
+        return r;
+    }
+    s2k_counter *raw() { return c_; }
+
+  private:
+    void check(s2k_status st) {
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(eng_->raw()));
+    }
+    Engine *eng_;
+    s2k_counter *c_;
 };
 
 class KminmersIterator { // src/lib.rs:70-131: per-read facade

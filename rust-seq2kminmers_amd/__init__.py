@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "s2k_trim", "s2k_density_for_bound", "s2k_abi_version", "s2k_device_count", "s2k_create", "s2k_destroy", "s2k_set_stream", "s2k_chain_after", "s2k_set_host_batch", "s2k_strerror",
     "s2k_last_error", "s2k_hash_bound", "s2k_extract", "s2k_result_free", "s2k_extract_device", "s2k_sync",
     "s2k_hpc_device", "s2k_hpc_device_ex", "s2k_count_device", "s2k_count_device_ex", "s2k_partition_device", "s2k_synth_bases_device", "s2k_synth_hifi_lengths", "s2k_synth_hifi_device", "s2k_last_kernel_ms", "s2k_enable_timing", "s2k_timing_total", "s2k_fastx_open", "s2k_fastx_next", "s2k_fastx_close", "s2k_run_file", "s2k_fastx_parse_device",
+    "s2k_count_merge_device", "s2k_counter_create", "s2k_counter_destroy", "s2k_counter_add", "s2k_counter_finish", "s2k_run_file_count",
 ]
 
 
@@ -131,6 +132,15 @@ def load_library(path=None):
     L.s2k_count_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_count_device_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_count_merge_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_counter_create.restype = C.c_void_p
+    L.s2k_counter_create.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.s2k_counter_destroy.restype = None
+    L.s2k_counter_destroy.argtypes = [C.c_void_p]
+    L.s2k_counter_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.s2k_counter_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_run_file_count.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Params), C.c_uint64, C.c_void_p, C.POINTER(Counts), C.POINTER(C.c_double)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -351,9 +361,108 @@ class Engine:
             raise
         return int(nd.value), int(nk.value)
 
+    def count_merge_device(self, d_a_keys, d_a_counts, n_a, d_b_keys=0, d_b_counts=0, n_b=0, min_count=1, d_keys=0, d_counts=0, capacity=0):
+        """union of two count tables, each strictly ascending by key (s2k_count_merge_device): counts of a key in both added (saturated at
+        2^32-1), pairs under min_count dropped, ascending key order; n_b == 0 filters one table.  Returns (n_distinct, n_kept); raises
+        S2kError(7) with the sizes when n_kept exceeds a non-zero capacity, S2kError(1) for an input that is not strictly ascending."""
+        nd, nk = C.c_uint64(0), C.c_uint64(0)
+        st = self.lib.s2k_count_merge_device(self.ctx, C.c_void_p(d_a_keys or 0), C.c_void_p(d_a_counts or 0), n_a, C.c_void_p(d_b_keys or 0),
+                                             C.c_void_p(d_b_counts or 0), n_b, min_count, C.c_void_p(d_keys or 0), C.c_void_p(d_counts or 0),
+                                             capacity, C.byref(nd), C.byref(nk))
+        try:
+            self._check(st)
+        except S2kError as e:
+            e.n_distinct, e.n_kept = int(nd.value), int(nk.value)
+            raise
+        return int(nd.value), int(nk.value)
+
+    def run_file_count(self, path, l, k, density, mode=HashMode.Regular, min_count=2, batch_bases=256 << 20, counter=None, flags=0):
+        """run_file that also counts the k-min-mers (s2k_run_file_count): the totals dict of run_file plus `keys` / `counts` (torch int64 /
+        int32 tensors on the device holding the uint64 keys / uint32 counts, ascending by key) of the k-min-mers that occur at least
+        min_count times, `n_distinct` and `n_kept`.  With a KminmerCounter the file is added to it and the results cover everything it
+        holds (several files: one counter); without one, a counter lives for this call only."""
+        own = counter is None
+        ctr = KminmerCounter(self) if own else counter
+        try:
+            p = Params(int(l), int(k), float(density), int(mode), int(flags))
+            cnt, sec = Counts(), C.c_double(0)
+            self._check(self.lib.s2k_run_file_count(self.ctx, os.fsencode(path), C.byref(p), batch_bases, C.c_void_p(ctr.handle), C.byref(cnt),
+                                                    C.byref(sec)))
+            d = cnt.as_dict()
+            d["seconds"] = float(sec.value)
+            keys, counts = ctr.finish(min_count)
+            d.update(keys=keys, counts=counts, n_distinct=ctr.last_sizes[0], n_kept=ctr.last_sizes[1])
+            return d
+        finally:
+            if own:
+                ctr.close()
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
+
+
+class KminmerCounter:
+    """Accumulating k-min-mer count over batches and files (s2k_counter_*): add device-resident hashes batch by batch, finish(min_count)
+    -> the solid pairs in ascending key order, equal to Engine.count_device_ex over the concatenation of everything added.  The counter
+    keeps its runs in HBM (about 12 B per distinct key); close() it before its Engine."""
+
+    def __init__(self, engine):
+        self.engine = engine
+        self.lib = engine.lib
+        st = C.c_int(0)
+        self.handle = self.lib.s2k_counter_create(engine.ctx, C.byref(st))
+        if not self.handle:
+            raise S2kError(st.value, self.lib.s2k_strerror(st.value).decode())
+        self.last_sizes = (0, 0)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.s2k_counter_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, d_hash, n):
+        """hashes d_hash[0..n) (a device pointer; any n): counted now, the buffer may be reused on return"""
+        self.engine._check(self.lib.s2k_counter_add(self.handle, C.c_void_p(d_hash or 0), int(n)))
+
+    def add_tensor(self, t):
+        """a 1-D int64 / uint64 torch tensor on the engine's device (its bits are the uint64 hashes)"""
+        import torch
+
+        if t.dim() != 1 or t.element_size() != 8 or not t.is_cuda:
+            raise ValueError("add_tensor wants a 1-D 64-bit tensor on the GPU")
+        t = t.contiguous()
+        torch.cuda.synchronize(t.device)  # the library's stream does not follow torch's
+        self.add(t.data_ptr() if t.numel() else 0, t.numel())
+
+    def sizes(self, min_count=1):
+        """(n_distinct, n_kept) of everything added so far"""
+        nd, nk = C.c_uint64(0), C.c_uint64(0)
+        self.engine._check(self.lib.s2k_counter_finish(self.handle, int(min_count), None, None, 0, C.byref(nd), C.byref(nk)))
+        self.last_sizes = (int(nd.value), int(nk.value))
+        return self.last_sizes
+
+    def finish(self, min_count=1):
+        """-> (keys, counts): torch int64 / int32 tensors on the device with the uint64 keys / uint32 counts of the pairs that occur at least
+        min_count times, ascending by key.  add() may go on afterwards."""
+        import torch
+
+        nd, nk = self.sizes(min_count)
+        dev = torch.device("cuda", self.engine.device)
+        keys = torch.empty(max(nk, 1), dtype=torch.int64, device=dev)
+        counts = torch.empty(max(nk, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        if nk:
+            a, b = C.c_uint64(0), C.c_uint64(0)
+            self.engine._check(self.lib.s2k_counter_finish(self.handle, int(min_count), C.c_void_p(keys.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                           nk, C.byref(a), C.byref(b)))
+        return keys[:nk], counts[:nk]
 
 
 class FastxReader:

@@ -330,8 +330,12 @@ s2k_status s2k_fastx_parse_device(s2k_ctx *ctx, const uint8_t *d_text, uint64_t 
     return rc;
 }
 
-s2k_status s2k_run_file(s2k_ctx *ctx, const char *path, const s2k_params *params, uint64_t batch_bases,
-                        s2k_counts *totals, double *seconds) {
+} // extern "C"
+
+namespace {
+// s2k_run_file, and with a counter s2k_run_file_count: each batch's hashes are added to it in collect(), before its slot is reused
+s2k_status run_file_impl(s2k_ctx *ctx, const char *path, const s2k_params *params, uint64_t batch_bases, s2k_counter *counter,
+                         s2k_counts *totals, double *seconds) {
     if (!ctx || !params || !totals || !path) return S2K_ERR_INVALID_ARG;
     auto t_start = std::chrono::steady_clock::now();
     memset(totals, 0, sizeof *totals);
@@ -433,6 +437,8 @@ s2k_status s2k_run_file(s2k_ctx *ctx, const char *path, const s2k_params *params
         totals->xor_hash ^= c.xor_hash;
         totals->hash_bound = c.hash_bound;
         totals->path = c.path;
+        if (counter && c.n_kminmers) // the hashes sit behind the read table in the slot's output block (see launch)
+            return s2k_counter_add(counter, (const uint64_t *)((char *)d.out + (((d.nr + 1) * 8 + 255) & ~(size_t)255)), c.n_kminmers);
         return S2K_OK;
     };
 
@@ -532,6 +538,24 @@ s2k_status s2k_run_file(s2k_ctx *ctx, const char *path, const s2k_params *params
     close(fd);
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     return st;
+}
+} // namespace
+
+extern "C" {
+
+s2k_status s2k_run_file(s2k_ctx *ctx, const char *path, const s2k_params *params, uint64_t batch_bases,
+                        s2k_counts *totals, double *seconds) {
+    return run_file_impl(ctx, path, params, batch_bases, nullptr, totals, seconds);
+}
+
+s2k_status s2k_run_file_count(s2k_ctx *ctx, const char *path, const s2k_params *params, uint64_t batch_bases, s2k_counter *counter,
+                              s2k_counts *totals, double *seconds) {
+    if (!ctx || !counter) return S2K_ERR_INVALID_ARG;
+    if (s2k::ctx_device(s2k::counter_ctx(counter)) != s2k::ctx_device(ctx)) {
+        s2k::ctx_set_error(ctx, "the counter's context is on another device");
+        return S2K_ERR_INVALID_ARG;
+    }
+    return run_file_impl(ctx, path, params, batch_bases, counter, totals, seconds);
 }
 
 } // extern "C"

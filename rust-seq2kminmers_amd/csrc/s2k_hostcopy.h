@@ -96,3 +96,8 @@ void ctx_set_error(s2k_ctx *c, const char *what);
 // grow-only device buffer of the context for s2k_count_device / s2k_partition_device (nullptr: allocation failed)
 void *ctx_count_table(s2k_ctx *c, size_t bytes);
 } // namespace s2k
+
+struct s2k_counter;
+namespace s2k {
+s2k_ctx *counter_ctx(s2k_counter *c); // the context a counter was created on (s2k_count_merge.hip)
+} // namespace s2k

@@ -1,9 +1,10 @@
 // s2k_main -- command-line driver, the counterpart of the reference's src/main.rs:
 //   no arguments : demo on a test sequence (src/main.rs:13-48): HPC string, then the k-min-mers of the four
 //                  HashModes at l=28, k=5, d=0.1
-//   <fastx> [l k density mode batch_Mbp] : file mode (src/main.rs:51-83; defaults l=31 k=5 d=0.01 Regular like
+//   <fastx> [l k density mode batch_Mbp [min_count]] : file mode (src/main.rs:51-83; defaults l=31 k=5 d=0.01 Regular like
 //                  :53-60) -- streams the file through the GPU and prints the k-min-mer count and the wall time.
-//                  (The reference's second argument, the thread count, has no meaning here.)
+//                  (The reference's second argument, the thread count, has no meaning here.)  With min_count the k-min-mers are
+//                  also counted (s2k_run_file_count) and one more line gives the distinct and the solid (>= min_count) ones.
 #include "../../include/s2k.hpp"
 
 #include <cstdio>
@@ -39,7 +40,16 @@ int main(int argc, char **argv) {
                     p.density, mode_name(p.mode));
         s2k_counts tot;
         double sec = 0;
-        s2k_status st = s2k_run_file(eng.raw(), argv[1], &p, batch, &tot, &sec);
+        const bool count = argc > 7;
+        s2k::Engine::CountSizes solid{0, 0};
+        s2k_status st;
+        if (count) {
+            s2k::Counter counter(eng);
+            st = s2k_run_file_count(eng.raw(), argv[1], &p, batch, counter.raw(), &tot, &sec);
+            if (st == S2K_OK) solid = counter.finish((uint32_t)std::strtoul(argv[7], nullptr, 10));
+        } else {
+            st = s2k_run_file(eng.raw(), argv[1], &p, batch, &tot, &sec);
+        }
         if (st != S2K_OK) {
             std::fprintf(stderr, "error: %s (%s)\n", s2k_strerror(st), s2k_last_error(eng.raw()));
             return 1;
@@ -47,6 +57,7 @@ int main(int argc, char **argv) {
         std::printf("reads: %llu bases: %llu minimizers: %llu kminmers: %llu xor: %llu\n", (unsigned long long)tot.n_reads,
                     (unsigned long long)tot.n_bases, (unsigned long long)tot.n_minimizers, (unsigned long long)tot.n_kminmers,
                     (unsigned long long)tot.xor_hash);
+        if (count) std::printf("distinct: %llu solid: %llu\n", (unsigned long long)solid.n_distinct, (unsigned long long)solid.n_kept);
         std::printf("FASTA to kminmers in %.3fs.\n", sec);
     } catch (const s2k::Error &e) {
         std::fprintf(stderr, "s2k error %d: %s\n", (int)e.status, e.what());
