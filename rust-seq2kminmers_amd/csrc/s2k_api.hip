@@ -620,6 +620,8 @@ s2k_status enqueue(s2k_ctx *ctx) {
                 sem.tile_heads = tile_heads;
             }
         }
+        // Hpc and Regular run the kernel with their semantics compiled in; Simd and HpcSimd the one that reads them from sem
+        const uint32_t tile_mode = tile_mode_of(sem);
         if (use_desc) {
             Desc dz{};
             dz.agg = d_agg;
@@ -660,7 +662,7 @@ s2k_status enqueue(s2k_ctx *ctx) {
                 };
                 const uint64_t T0 = cut(ch), T1 = cut(ch + 1);
                 const bool last = ch + 1 == n_chunks;
-                S2K_TRY(launch_tile_minimizers(c.d_bases, c.d_read_off, n_reads, n_bases, T1, tile_read0, sem, rec,
+                S2K_TRY(launch_tile_minimizers(c.d_bases, c.d_read_off, n_reads, n_bases, T1, tile_read0, sem, tile_mode, rec,
                                                pool_cursor + (size_t)CURSOR_WORDS * ch, nullptr, nullptr, nullptr, ctx->d_counts, &dz, T0, sp),
                         "tiled minimizer kernel");
                 if (last) {
@@ -692,7 +694,7 @@ s2k_status enqueue(s2k_ctx *ctx) {
             return S2K_OK;
         }
         if (tm) S2K_TRY(hipEventRecord(ctx->ev[1], sp), "event");
-        S2K_TRY(launch_tile_minimizers(c.d_bases, c.d_read_off, n_reads, n_bases, n_tiles, tile_read0, sem, rec, pool_cursor,
+        S2K_TRY(launch_tile_minimizers(c.d_bases, c.d_read_off, n_reads, n_bases, n_tiles, tile_read0, sem, tile_mode, rec, pool_cursor,
                                        tile_rec_off, tile_cnt, mn_cnt, ctx->d_counts, nullptr, 0, sp),
                 "tiled minimizer kernel");
         s2k_status hs = hand_over();

@@ -72,6 +72,18 @@ struct Sem {
     uint32_t *tile_heads;
 };
 
+// Result semantics compiled into the tiled kernel (its MODE template parameter).  With a fixed mode, the fields of Sem its tile loop
+// branches on are constants and need neither a register nor a test per tile; TILE_MODE_RUNTIME reads them from Sem (Simd, HpcSimd
+// and any other combination).
+enum TileMode : uint32_t { TILE_MODE_RUNTIME = 0, TILE_MODE_REGULAR = 1, TILE_MODE_HPC = 2 };
+// the fixed mode sem is exactly, else TILE_MODE_RUNTIME (the launch picks the kernel by it; bound_le, l and k stay run-time values)
+__host__ __device__ inline uint32_t tile_mode_of(const Sem &s) {
+    if (s.enabled != 1 || s.simd_seeds || s.tail_quirk || s.read_runs || s.tile_heads) return TILE_MODE_RUNTIME;
+    if (!s.hpc && s.keep_last == 1 && s.end_kind == 0) return TILE_MODE_REGULAR; // src/lib.rs:215-230
+    if (s.hpc == 1 && s.keep_last == 0 && s.end_kind == 1) return TILE_MODE_HPC;  // src/nthash_hpc.rs:115-283
+    return TILE_MODE_RUNTIME;
+}
+
 struct Counts { // mirrored by s2k_counts (include/s2k.h)
     uint64_t n_reads, n_bases, n_minimizers, n_kminmers, xor_hash;
     uint32_t hash_bound, path;
@@ -284,8 +296,9 @@ hipError_t launch_finalize(Counts *counts, const uint64_t *xor_shards, const uin
 
 // desc != nullptr: descriptor path (8-byte records in rec.hash / rec.j, agg word + meta per tile; tile_rec_off / tile_cnt / mn_cnt unused).
 // The launch works on the tiles [tile_begin, n_tiles); pool_cursor must be zeroed (CURSOR_WORDS words) for every launch.
+// mode: tile_mode_of(sem), or TILE_MODE_RUNTIME (any other value than those two is refused).
 hipError_t launch_tile_minimizers(const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint64_t n_bases,
-                                  uint64_t n_tiles, const uint32_t *tile_read0, Sem sem, Records rec,
+                                  uint64_t n_tiles, const uint32_t *tile_read0, Sem sem, uint32_t mode, Records rec,
                                   uint64_t *pool_cursor, uint64_t *tile_rec_off, uint32_t *tile_cnt, uint32_t *mn_cnt,
                                   Counts *counts, const Desc *desc, uint64_t tile_begin, hipStream_t st);
 // descriptor path, for the tiles [tile_begin, tile_end): (G, p) of every tile from the tile words -- starting from state[tile_begin]

@@ -1367,6 +1367,8 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
     // in the listing, and the hit masks and kept hashes (19 registers) are dead once the hits are listed -- inside the loop
     // of the general case they stay live through the rounds for the next batch.
     auto batch = [&](uint32_t b0, auto single_c) {
+        // (the kernel's Records live in memory (TileCold): the record arrays' addresses are read here, once per batch, not in every round)
+        uint32_t *const rec_j = rec.j, *const rec_hash = rec.hash, *const rec_jend = rec.jend, *const rec_rid = rec.rid;
         constexpr bool SINGLE = decltype(single_c)::value;
         wave_sync();
         // Hpc tiles of at most 112 hash positions per lane (all but incompressible input) whose hits fit one batch: ONE LANE PER HIT (round 6).  The
@@ -1468,7 +1470,7 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
                     const uint32_t hvk = CAPP == 16 ? ((bit & 16) ? cap1 : cap0) : ((bit & 16) ? ((bit & 8) ? cap3 : cap2) : ((bit & 8) ? cap1 : cap0));
                     if (SINGLE || (k >= b0 && k < b0 + LISTCAP)) {
                         S.list[k - b0] = (uint16_t)((tql + 32 * d + bit) | (later ? 0x8000u : 0u));
-                        if (!later && !(sem.dbg_skip & 16)) rec.hash[base + k] = hvk;
+                        if (!later && !(sem.dbg_skip & 16)) rec_hash[base + k] = hvk;
                     }
                     k++;
                 }
@@ -1543,7 +1545,7 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
                     const uint32_t span = erel - prel;
                     if (span > (uint32_t)REC_SPAN_MAX) counts->need_legacy = 1; // (a homopolymer stretch of > 262 kbp inside one l-mer)
                     const uint32_t sp = span > (uint32_t)REC_SPAN_MAX ? (uint32_t)REC_SPAN_MAX : span;
-                    if (!(sem.dbg_skip & 16)) rec.j[base + b0 + kk] = prel | (sp << 14);
+                    if (!(sem.dbg_skip & 16)) rec_j[base + b0 + kk] = prel | (sp << 14);
                 }
             } else {
             const uint64_t p = t0 + prel, e1 = t0 + erel;
@@ -1566,9 +1568,9 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
                 }
                 const uint64_t slot = base + b0 + kk;
                 if (!(sem.dbg_skip & 16)) {
-                    rec.j[slot] = (uint32_t)(p - rstart);
-                    rec.jend[slot] = (uint32_t)(e1 - rstart);
-                    rec.rid[slot] = rid;
+                    rec_j[slot] = (uint32_t)(p - rstart);
+                    rec_jend[slot] = (uint32_t)(e1 - rstart);
+                    rec_rid[slot] = rid;
                 }
             }
             S2K_STAMP(10); // round: read lookup + stores
@@ -1606,14 +1608,57 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
 // read-table entries of the next tiles are fetched before they are needed, so no global-load latency sits on the critical
 // path except in the first iteration.
 // DESC: the descriptor path (8-byte records + one word and a segment list per tile, see dense_phase); else the legacy records.
-template <int L, bool HPC, bool DESC>
+// MODE (TileMode): the result semantics, compiled in (TILE_MODE_HPC / TILE_MODE_REGULAR) or read from sem (TILE_MODE_RUNTIME).
+// Outside S2K_DEBUG_KNOBS builds the ablation knob dbg_skip is a constant zero as well.
+template <int MODE>
+__device__ __forceinline__ Sem tile_sem(Sem s) {
+#ifndef S2K_DEBUG_KNOBS
+    s.dbg_skip = 0;
+#endif
+    if constexpr (MODE != TILE_MODE_RUNTIME) { // (the launch checked that sem is exactly this: tile_mode_of)
+        s.enabled = 1;
+        s.hpc = MODE == TILE_MODE_HPC;
+        s.simd_seeds = 0;
+        s.keep_last = MODE == TILE_MODE_HPC ? 0 : 1;
+        s.end_kind = MODE == TILE_MODE_HPC ? 1 : 0;
+        s.tail_quirk = 0;
+        s.read_runs = nullptr;
+        s.tile_heads = nullptr;
+    }
+    return s;
+}
+
+// The kernel's arguments that the tile loop needs only outside the hash loop: the pool and its overflow path, the per-tile and
+// per-read tables, the counters.  Held in SGPRs across the whole persistent loop they did not fit beside the loop's own scalars
+// (the Hpc kernel spilled 76 SGPRs to VGPR lanes: a v_writelane / v_readlane per spill and reload, and the hazard nops around
+// them).  They stay in the kernarg segment and are read with s_load where they are used (cold_args()).
+struct TileCold {
+    Records rec;
+    uint64_t *pool_cursor;
+    uint64_t *tile_rec_off; // (legacy path)
+    uint32_t *tile_cnt;     // (legacy path)
+    uint32_t *mn_cnt;       // (legacy path)
+    Counts *counts;
+    unsigned long long *d_agg; // (descriptor path)
+    TileMeta *d_meta;          // (descriptor path)
+    const uint32_t *tile_read0;
+    uint32_t K1; // (descriptor path) k - 1
+};
+typedef const __attribute__((address_space(4))) TileCold *cold_ptr_t;
+
+template <int L, bool HPC, bool DESC, int MODE>
 __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_minimizer_kernel(
-    const uint8_t *__restrict__ bases, const uint64_t *__restrict__ read_off, uint64_t n_reads, uint64_t n_bases,
-    uint64_t n_tiles, const uint32_t *__restrict__ tile_read0, Sem sem, Records rec, uint64_t *pool_cursor,
-    uint64_t *__restrict__ tile_rec_off, uint32_t *__restrict__ tile_cnt, uint32_t *mn_cnt, Counts *counts,
-    unsigned long long *__restrict__ d_agg, TileMeta *__restrict__ d_meta, uint32_t K1, uint64_t tile_begin) {
+    const TileCold cold, const uint8_t *__restrict__ bases, const uint64_t *__restrict__ read_off, uint64_t n_reads,
+    uint64_t n_bases, uint64_t n_tiles, Sem sem_arg, uint64_t tile_begin) {
     // (this launch works on the tiles [tile_begin, n_tiles): the descriptor path cuts a call into a few chunks of tiles so that
     // the k-min-mer kernel of one chunk runs, on a second stream, beside the minimizer kernel of the next)
+    const Sem sem = tile_sem<MODE>(sem_arg);
+    // The cold arguments, through a pointer into the kernarg segment that is made opaque again at the top of every tile: the
+    // compiler can neither hoist their loads out of the tile loop nor keep the values across it.  (cold is the first argument:
+    // offset 0 of the segment, tests/test_tile_sgpr_budget.py checks it in the code object's metadata.)
+    (void)cold;
+    cold_ptr_t cold_p = (cold_ptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+    auto cold_args = [&]() -> const TileCold & { return *(const TileCold *)cold_p; };
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     using WL = WaveLdsT<HPC>;
     uint2 *tab = reinterpret_cast<uint2 *>(smem);
@@ -1644,12 +1689,14 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
 #ifdef S2K_DEBUG_KNOBS
     const uint64_t dbg_mt0 = __builtin_amdgcn_s_memtime(), dbg_rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    WL &S = *reinterpret_cast<WL *>(smem + table_bytes<HPC>() + (size_t)w * sizeof(WL));
-    uint8_t *D = S.buf + HS_OFF;
+    // this wave's LDS block (S, and its tile buffer D) from an offset that is made opaque again at the top of every tile (as
+    // lane, bases and cold_p): addresses of S's fields are otherwise hoisted out of the tile loop and held, or spilled, across it
+    uint32_t wl_off = (uint32_t)(table_bytes<HPC>() + (size_t)w * sizeof(WL));
+    uint8_t *D = reinterpret_cast<WL *>(smem + wl_off)->buf + HS_OFF;
     const uint64_t n_waves = (uint64_t)gridDim.x * TW;
     uint64_t t = tile_begin + (uint64_t)blockIdx.x * TW + w;
     if (t >= n_tiles) return;
-    if (__builtin_amdgcn_readfirstlane((int)counts->bad_input)) return; // malformed read table (validate_read_off_kernel): touch nothing
+    if (__builtin_amdgcn_readfirstlane((int)cold_args().counts->bad_input)) return; // malformed read table (validate_read_off_kernel): touch nothing
     uint64_t stamp = __builtin_amdgcn_s_memtime();
 #ifdef S2K_PROFILE
     ph_ptr_t ph = reinterpret_cast<ph_ptr_t>((uint32_t)(table_bytes<HPC>() + TW * sizeof(WL) + (size_t)w * 128)); // (the dynamic region starts at LDS address 0)
@@ -1707,7 +1754,7 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
         bp = bri <= n_reads ? read_off[bri] : ~0ull; // entry n_reads is the end of the stream
         rs = read_off[rr0];
     };
-    uint32_t r0 = tile_read0[t], r1 = tile_read0[t + 1];
+    uint32_t r0 = cold_args().tile_read0[t], r1 = cold_args().tile_read0[t + 1];
     uint64_t bpos0, rs0;
     read_entries(r0, bpos0, rs0);
     if (is_full(t)) prevb = byte_before(t);
@@ -1731,15 +1778,15 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
     // only is still dealing when the others have run dry (TW = 16: 16 b + w mod 64 keeps w -- the last wave finished 2.7 ms
     // after the first).  The second term walks the wave index through the cursors' residues as the blocks go by.
     const uint32_t cur_g = (uint32_t)((blockIdx.x * TW + w + blockIdx.x / (TILE_CURSORS / 4)) % TILE_CURSORS);
-    unsigned int *const cursors = (unsigned int *)(pool_cursor + 16); // 32-bit draws (a 64-bit result's dead upper half would be
-                                                                       // reused early and pull a vmcnt(0) in front of the compaction); cursor g = word 32 g
+    auto cursors = [&]() { return (unsigned int *)(cold_args().pool_cursor + 16); }; // 32-bit draws (a 64-bit result's dead upper half would be
+                                                                                      // reused early and pull a vmcnt(0) in front of the compaction); cursor g = word 32 g
     // (A wave stays with its cursor: when that runs dry the wave is done.  Round 2 let it move on to another cursor that was not;
     // measured again in round 3 (same-call A/B, profiles/r03_ab_knobs.txt) that costs 1 % instead of gaining anything: the 64
     // cursors run dry within a tile time of each other, and the extra code sits in the tile loop.)
     uint32_t r0n = 0, r1n = 0;
     if (tn < n_tiles) {
-        r0n = tile_read0[tn];
-        r1n = tile_read0[tn + 1];
+        r0n = cold_args().tile_read0[tn];
+        r1n = cold_args().tile_read0[tn + 1];
     }
 
     // (the persistent kernel's waves at a raised issue priority over the k-min-mer kernel's beside them -- s_setprio 1 / 3 for the whole kernel -- changed nothing:
@@ -1747,7 +1794,7 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
     uint32_t prio_iter = 0;
     // HpcSimd look-back (lookback_heads): a wave that has waited in vain once does not wait again -- nor does any wave once the
     // call is known to be run again (need_runs; e.g. the minimizer kernel of a later chunk)
-    bool lb_dead = sem.tile_heads != nullptr && __builtin_amdgcn_readfirstlane((int)counts->need_runs) != 0;
+    bool lb_dead = sem.tile_heads != nullptr && __builtin_amdgcn_readfirstlane((int)cold_args().counts->need_runs) != 0;
     for (; t < n_tiles;) {
         // A dozen values derived from the lane index (64-bit zero-extensions, 16 x lane offsets, masks) are loop-invariant; LLVM
         // hoists them out of this loop and then holds -- or spills -- them across the hash loop, where the register pressure
@@ -1755,6 +1802,11 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
         // instructions each where they are used.
         lane = lane0;
         asm volatile("" : "+v"(lane));
+        asm volatile("" : "+s"(cold_p));
+        asm volatile("" : "+s"(bases));
+        asm volatile("" : "+s"(wl_off));
+        WL &S = *reinterpret_cast<WL *>(smem + wl_off);
+        D = S.buf + HS_OFF;
         if (sem.tile_heads) {
             // HpcSimd, look-back for run heads (lookback_heads): the SIMD's arbiter serves its oldest wave first, so the three waves of
             // a SIMD run at lastingly different speeds, and a tile whose predecessor sits on a slower wave waits for that wave's
@@ -1810,7 +1862,7 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
         const uint32_t cr0 = r0, cr1 = r1, cprev = prevb; // this tile's values (the registers get reused below)
         // ---- loads for the next tiles that land in registers: issued now, waited for right after the hash loop ----------
         uint32_t took = 0; // draw for the tile after tnn
-        if (lane == 0 && tnn < n_tiles) took = atomicAdd(&cursors[32 * cur_g], 1u);
+        if (lane == 0 && tnn < n_tiles) took = atomicAdd(&cursors()[32 * cur_g], 1u);
         // (raw loads at always-valid addresses: the selects that make the final values come after the wait -- a consumer in
         // here would pull a vmcnt(0) in front of the compaction)
         // The wave-uniform ones are VECTOR loads on purpose (index + an opaque zero in a VGPR): as scalar loads they count in
@@ -1826,8 +1878,8 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
             rs0n = read_off[(uint64_t)r0n + vzero];
             prevbn = (uint32_t)bases[tn * (uint64_t)TILE_BASES - 1 + vzero]; // tn > 0
             if (tnn < n_tiles) {
-                r0nn = tile_read0[tnn + vzero];
-                r1nn = tile_read0[tnn + 1 + vzero];
+                r0nn = cold_args().tile_read0[tnn + vzero];
+                r1nn = cold_args().tile_read0[tnn + 1 + vzero];
             }
         }
         if (lane == 0) S.buf[HS_OFF - 1] = 0;
@@ -1876,8 +1928,8 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
         auto issue_next = [&](uint32_t n_rec, uint64_t rec_base) {
             if constexpr (!DESC) {
                 if (lane == 0) { // before the DMA loads: only the rounds' stores may follow them
-                    tile_cnt[t] = n_rec;
-                    tile_rec_off[t] = rec_base;
+                    cold_args().tile_cnt[t] = n_rec;
+                    cold_args().tile_rec_off[t] = rec_base;
                 }
             }
             have_pre = false;
@@ -1958,7 +2010,8 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
 #ifndef EXP_NODENSE
             if (!(sem.dbg_skip & 2))
                 N = dense_phase<L, HPC, DESC>(issue_once, S, D, tab, read_off, n_reads, t, t0, tile_len, nh, halo_n, Tq, rcpTq, l, cr0, cr1,
-                                           bpos0, rs0, lane_d, rec, pool_cursor, mn_cnt, counts, base, sem, d_agg, d_meta, K1,
+                                           bpos0, rs0, lane_d, cold_args().rec, cold_args().pool_cursor, cold_args().mn_cnt,
+                                           cold_args().counts, base, sem, cold_args().d_agg, cold_args().d_meta, cold_args().K1,
                                            caps, raw, lb_early, lb_dead, ph, stamp);
 #endif
             S2K_STAMP(5); // rounds
@@ -1981,20 +2034,20 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
     }
 #ifdef S2K_PROFILE
     if ((sem.dbg_skip & 8) && lane == 0)
-        for (int i = 0; i < 16; i++) atomicAdd((unsigned long long *)&counts->dbg_cycles[blockIdx.x & 63][i], (unsigned long long)ph[i]);
+        for (int i = 0; i < 16; i++) atomicAdd((unsigned long long *)&cold_args().counts->dbg_cycles[blockIdx.x & 63][i], (unsigned long long)ph[i]);
 #endif
 #ifdef S2K_DEBUG_KNOBS // S2K_DEBUG_SKIP & 32: when did the first and the last wave run out of tiles (100 MHz clock)?
     if ((sem.dbg_skip & 32) && lane == 0) {
         const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-        atomicMax((unsigned long long *)&counts->dbg_cycles[0][0], now);
-        atomicMax((unsigned long long *)&counts->dbg_cycles[0][1], ~now);
+        atomicMax((unsigned long long *)&cold_args().counts->dbg_cycles[0][0], now);
+        atomicMax((unsigned long long *)&cold_args().counts->dbg_cycles[0][1], ~now);
         // shader clock under this kernel's load: s_memtime counts shader cycles, s_memrealtime the constant 100 MHz clock
-        atomicAdd((unsigned long long *)&counts->dbg_cycles[1][0], (unsigned long long)(__builtin_amdgcn_s_memtime() - dbg_mt0));
-        atomicAdd((unsigned long long *)&counts->dbg_cycles[1][1], (unsigned long long)(now - dbg_rt0));
+        atomicAdd((unsigned long long *)&cold_args().counts->dbg_cycles[1][0], (unsigned long long)(__builtin_amdgcn_s_memtime() - dbg_mt0));
+        atomicAdd((unsigned long long *)&cold_args().counts->dbg_cycles[1][1], (unsigned long long)(now - dbg_rt0));
         const uint32_t wid = blockIdx.x * TW + w;
         if (wid < 4096) {
-            counts->dbg_wave[wid][0] = now;
-            counts->dbg_wave[wid][1] = ((uint64_t)__builtin_amdgcn_s_getreg((20 | (0 << 6) | (31 << 11))) << 32) | (uint32_t)__builtin_amdgcn_s_getreg((4 | (0 << 6) | (31 << 11)));
+            cold_args().counts->dbg_wave[wid][0] = now;
+            cold_args().counts->dbg_wave[wid][1] = ((uint64_t)__builtin_amdgcn_s_getreg((20 | (0 << 6) | (31 << 11))) << 32) | (uint32_t)__builtin_amdgcn_s_getreg((4 | (0 << 6) | (31 << 11)));
         }
     }
 #endif
@@ -2169,11 +2222,11 @@ hipError_t launch_stream_l(hipStream_t st, const uint8_t *bases, const uint64_t 
 }
 #endif // S2K_STREAM_BUILD
 
-template <int L, bool HPC, bool DESC>
+template <int L, bool HPC, bool DESC, int MODE>
 hipError_t launch_tiles_lh(hipStream_t st, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint64_t n_bases,
                            uint64_t n_tiles, const uint32_t *tile_read0, Sem sem, Records rec, uint64_t *pool_cursor,
                            uint64_t *tile_rec_off, uint32_t *tile_cnt, uint32_t *mn_cnt, Counts *counts, const Desc *desc, uint64_t tile_begin) {
-    auto kern = tile_minimizer_kernel<L, HPC, DESC>;
+    auto kern = tile_minimizer_kernel<L, HPC, DESC, MODE>;
     constexpr int TW = tw<HPC>();
     const int lds = block_lds_bytes<HPC>();
     // per instantiation AND per device: function attributes and occupancy belong to the device the module is loaded on
@@ -2206,20 +2259,33 @@ hipError_t launch_tiles_lh(hipStream_t st, const uint8_t *bases, const uint64_t 
     uint64_t blocks = (n_tiles - tile_begin + TW - 1) / TW;
     const uint64_t resident = (uint64_t)n_cu * per_cu;
     if (blocks > resident) blocks = resident; // persistent: waves loop over the remaining tiles
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * TW), lds, st, bases, read_off, n_reads, n_bases, n_tiles,
-                       tile_read0, sem, rec, pool_cursor, tile_rec_off, tile_cnt, mn_cnt, counts, desc ? desc->agg : nullptr,
-                       desc ? desc->meta : nullptr, desc ? desc->k - 1u : 0u, tile_begin);
+    TileCold cold{};
+    cold.rec = rec;
+    cold.pool_cursor = pool_cursor;
+    cold.tile_rec_off = tile_rec_off;
+    cold.tile_cnt = tile_cnt;
+    cold.mn_cnt = mn_cnt;
+    cold.counts = counts;
+    cold.d_agg = desc ? desc->agg : nullptr;
+    cold.d_meta = desc ? desc->meta : nullptr;
+    cold.tile_read0 = tile_read0;
+    cold.K1 = desc ? desc->k - 1u : 0u;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * TW), lds, st, cold, bases, read_off, n_reads, n_bases, n_tiles, sem,
+                       tile_begin);
     return hipGetLastError();
 }
 
 template <int L>
 hipError_t launch_tiles_l(bool hpc, hipStream_t st, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads,
-                          uint64_t n_bases, uint64_t n_tiles, const uint32_t *tile_read0, Sem sem, Records rec,
+                          uint64_t n_bases, uint64_t n_tiles, const uint32_t *tile_read0, Sem sem, uint32_t mode, Records rec,
                           uint64_t *pool_cursor, uint64_t *tile_rec_off, uint32_t *tile_cnt, uint32_t *mn_cnt,
                           Counts *counts, const Desc *desc, uint64_t tile_begin) {
-#define S2K_GO(H, F)                                                                                                       \
-    launch_tiles_lh<L, H, F>(st, bases, read_off, n_reads, n_bases, n_tiles, tile_read0, sem, rec, pool_cursor, tile_rec_off, \
-                             tile_cnt, mn_cnt, counts, desc, tile_begin)
+    // (mode: TILE_MODE_RUNTIME, or the fixed mode of sem's family -- launch_tile_minimizers checked it)
+#define S2K_GO_M(H, F, M)                                                                                                    \
+    launch_tiles_lh<L, H, F, M>(st, bases, read_off, n_reads, n_bases, n_tiles, tile_read0, sem, rec, pool_cursor,         \
+                                tile_rec_off, tile_cnt, mn_cnt, counts, desc, tile_begin)
+#define S2K_GO(H, F) \
+    (mode != TILE_MODE_RUNTIME ? S2K_GO_M(H, F, H ? TILE_MODE_HPC : TILE_MODE_REGULAR) : S2K_GO_M(H, F, TILE_MODE_RUNTIME))
 #if S2K_STREAM_BUILD
     if constexpr (L > 0) {
         // Regular family, descriptor path: the tiles that lie wholly inside the stream (all but the last one or two) go to the kernel without a
@@ -2233,8 +2299,11 @@ hipError_t launch_tiles_l(bool hpc, hipStream_t st, const uint8_t *bases, const 
                 S2K_HIP_CHECK(launch_stream_l<L>(st, bases, read_off, n_reads, n_bases, hi, tile_read0, sem, rec, pool_cursor, counts, desc, tile_begin));
                 if (hi >= n_tiles) return hipSuccess;
                 const uint64_t tb = hi; // (the one or two tiles at the end of the stream: no draws from the cursors, which the launch above has used)
-                return launch_tiles_lh<L, false, true>(st, bases, read_off, n_reads, n_bases, n_tiles, tile_read0, sem, rec, pool_cursor, tile_rec_off, tile_cnt,
-                                                       mn_cnt, counts, desc, tb);
+                if (mode != TILE_MODE_RUNTIME)
+                    return launch_tiles_lh<L, false, true, TILE_MODE_REGULAR>(st, bases, read_off, n_reads, n_bases, n_tiles, tile_read0, sem, rec,
+                                                                              pool_cursor, tile_rec_off, tile_cnt, mn_cnt, counts, desc, tb);
+                return launch_tiles_lh<L, false, true, TILE_MODE_RUNTIME>(st, bases, read_off, n_reads, n_bases, n_tiles, tile_read0, sem, rec, pool_cursor,
+                                                                          tile_rec_off, tile_cnt, mn_cnt, counts, desc, tb);
             }
         }
     }
@@ -2242,6 +2311,7 @@ hipError_t launch_tiles_l(bool hpc, hipStream_t st, const uint8_t *bases, const 
     if (desc) return hpc ? S2K_GO(true, true) : S2K_GO(false, true);
     return hpc ? S2K_GO(true, false) : S2K_GO(false, false);
 #undef S2K_GO
+#undef S2K_GO_M
 }
 
 } // namespace

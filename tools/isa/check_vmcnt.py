@@ -17,6 +17,51 @@ import sys
 VMEM = re.compile(r"^\s*(global_|buffer_|flat_|scratch_)(store|load|atomic)")
 
 
+BLOCK = re.compile(r"^(\.LBB\d+_\d+:|; %bb\.\d+:)")
+
+
+def loop_lines(lines, a, b, mk):
+    """Lines of the loop whose body holds line mk, child loops included, from the compiler's own loop annotations (a block's label
+    carries "in Loop: Header=BBx_y", a loop header "This [Inner] Loop Header" and "Parent Loop BBx_y" for every loop around it):
+    the blocks of a rotated loop need not lie between its header and a backward branch.  None without annotations."""
+    blocks = []  # [name, first line, last line, annotation]
+    for i in range(a, b):
+        m = BLOCK.match(lines[i].strip())
+        if m:
+            if blocks:
+                blocks[-1][2] = i - 1
+            name = m.group(1)[2:-1] if m.group(1).startswith(".L") else None
+            note, j = lines[i], i + 1
+            while j < b and lines[j].strip().startswith(";") and not lines[j].strip().startswith(";;"):
+                note += lines[j]
+                j += 1
+            blocks.append([name, i, b - 1, note])
+    own = [blk for blk in blocks if blk[1] <= mk <= blk[2]]
+    if not own:
+        return None
+    name, _, _, note = own[0]
+    if "Loop Header" in note and name:
+        head = name
+    else:
+        m = re.search(r"Header=(BB\d+_\d+)", note)
+        if not m:
+            return None
+        head = m.group(1)
+    heads, grew = {head}, True
+    while grew:  # the headers of the loops nested in it
+        grew = False
+        for blk in blocks:
+            if blk[0] and blk[0] not in heads and "Loop Header" in blk[3] and any("Parent Loop %s " % h in blk[3] + " " for h in heads):
+                heads.add(blk[0])
+                grew = True
+    body = []
+    for n, lo, hi, note in blocks:
+        m = re.search(r"Header=(BB\d+_\d+)", note)
+        if n in heads or (m and m.group(1) in heads):
+            body += range(lo, hi + 1)
+    return body
+
+
 def check(path):
     """The round loop is found structurally: the innermost backward branch whose span contains the `round_begin many=0`
     marker (the compiler rotates the loop, so the markers are not in program order in the text)."""
@@ -69,13 +114,12 @@ def check(path):
         if not marks:
             errors.append("%s: round loop (many=0) not marked" % tag)
         for mk in marks:
-            spans = [(bl - labels[t], labels[t], bl) for bl, t in branches if t in labels and labels[t] <= mk <= bl]
-            if not spans:
+            body = loop_lines(lines, a, b, mk)
+            if body is None:
                 errors.append("%s: no loop around the round_begin marker" % tag)
                 continue
-            _, lo, hi = min(spans)  # innermost loop header around the marker ...
-            hi = max(bl for bl, t in branches if t in labels and labels[t] == lo)  # ... and its last back edge
-            ops = [lines[i].split()[0] for i in range(lo, hi + 1) if VMEM.match(lines[i])]
+            lo, hi = min(body), max(body)
+            ops = [lines[i].split()[0] for i in body if VMEM.match(lines[i])]
             stores = [o for o in ops if "store" in o or "atomic" in o]
             report.append("%s: round loop = lines %d..%d, %d vector-memory ops per round (%s), kernel counts %d" % (
                 tag, lo + 1, hi + 1, len(ops), " ".join(ops), need))
