@@ -182,7 +182,9 @@ s2k_status s2k_trim(s2k_ctx *ctx);
  * accepted: the stream is first copied to an aligned buffer (one device-to-device pass) and takes the same tiled
  * kernels.  Enqueued on the context's stream; if
  * `counts` is non-NULL the call waits for completion and fills it (and returns S2K_ERR_CAPACITY if
- * an output capacity was too small -- counts then hold the required sizes).  With counts == NULL the
+ * an output capacity was too small -- counts then hold the required sizes, xor_hash is still the XOR of ALL k-min-mers,
+ * km_off / mn_off are whole, the given arrays hold the first km_capacity / mn_capacity items, and nothing is written past
+ * them; the same on the descriptor, legacy and read-serial paths).  With counts == NULL the
  * call returns after enqueueing; s2k_sync() later waits and reports the same status/counts. */
 s2k_status s2k_extract_device(s2k_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_read_off,
                               uint64_t n_reads, uint64_t n_bases, const s2k_params *params,

@@ -34,6 +34,21 @@ def compare(eng, oracle, reads, l, k, d, mode, force_serial=False, expect_path=N
         # a caller that expects "tiled" accepts both, "fused" / "two-kernel" / "serial" (1) are exact
         ok = {0: (0, 2), "desc": (0,), "legacy": (2,), 1: (1,), 2: (2,)}[expect_path]
         assert c["path"] in ok, ("path", ctx, c["path"])
+    if minimizers:
+        # the same call without the triples takes the other family of k-min-mer kernels (desc_kminmer_kernel<KT, FULL = true, ...>: lane-serial
+        # windows for k in {5, 10}, staged stores when the kernel runs alone) -- the one production runs; checked against the same oracle run
+        km = eng.extract(bases, off, l, k, d, mode, want_minimizers=False, force_serial=force_serial)
+        ctx = ctx + ("no triples",)
+        assert km["n"] == ref["n"], ("n_kminmers", ctx, km["n"], ref["n"])
+        for f in FIELDS:
+            if not (km[f] == ref[f]).all():
+                bad = int(np.nonzero(km[f] != ref[f])[0][0])
+                raise AssertionError(("mismatch", f, ctx, bad, int(km[f][bad]), int(ref[f][bad])))
+        kc = km["counts"]
+        assert kc["n_kminmers"] == ref["n"] and kc["xor_hash"] == c["xor_hash"], ("counts", ctx, kc)
+        assert kc["n_reads"] == len(reads) and kc["n_bases"] == len(bases) and kc["hash_bound"] == c["hash_bound"], ("counts", ctx, kc)
+        if expect_path is not None:
+            assert kc["path"] in ok, ("path", ctx, kc["path"])
     return got
 
 

@@ -418,10 +418,12 @@ def test_device_api_capacity_and_async(eng, oracle):
     ref = oracle.batch(bases, off, 31, 10, 0.01, 0)
     nk = ref["n"]
 
+    guard = 9216  # elements behind the capacity, filled with a sentinel: more than one tile's windows, so that a wrong write stays inside them
+
     def mk(cap):
-        t = {"km_off": torch.zeros(len(reads) + 1, dtype=torch.int64, device=dev), "hash": torch.zeros(max(cap, 1), dtype=torch.int64, device=dev),
-             "start": torch.zeros(max(cap, 1), dtype=torch.int32, device=dev), "end": torch.zeros(max(cap, 1), dtype=torch.int32, device=dev),
-             "rev": torch.zeros(max(cap, 1), dtype=torch.uint8, device=dev)}
+        t = {"km_off": torch.zeros(len(reads) + 1, dtype=torch.int64, device=dev), "hash": torch.full((max(cap, 1) + guard,), -7, dtype=torch.int64, device=dev),
+             "start": torch.full((max(cap, 1) + guard,), -7, dtype=torch.int32, device=dev), "end": torch.full((max(cap, 1) + guard,), -7, dtype=torch.int32, device=dev),
+             "rev": torch.full((max(cap, 1) + guard,), 0xA5, dtype=torch.uint8, device=dev)}
         o = pkg.DeviceOut()
         o.km_capacity = cap
         o.km_off, o.hash, o.start, o.end, o.rev = (t[x].data_ptr() for x in ("km_off", "hash", "start", "end", "rev"))
@@ -434,14 +436,19 @@ def test_device_api_capacity_and_async(eng, oracle):
     assert e.value.status == 7  # S2K_ERR_CAPACITY
     # entries below the capacity are still correct, nothing was written past it
     assert (t["hash"].cpu().numpy().view(np.uint64)[: nk // 2] == ref["hash"][: nk // 2]).all()
+    for f in ("start", "end", "rev"):
+        assert (t[f][: nk // 2].cpu().numpy().view(ref[f].dtype) == ref[f][: nk // 2]).all(), f
+    for f, sentinel in (("hash", -7), ("start", -7), ("end", -7), ("rev", 0xA5)):
+        assert (t[f][nk // 2:] == sentinel).all().item(), ("written past the capacity", f)
     t, o = mk(nk)
     eng.extract_device(d_b.data_ptr(), d_o.data_ptr(), len(reads), len(bases), 31, 10, 0.01, 0, o, sync=False)
     c = eng.sync()
     assert c["n_kminmers"] == nk and c["path"] == 0
-    assert (t["hash"].cpu().numpy().view(np.uint64) == ref["hash"]).all()
+    assert (t["hash"][:nk].cpu().numpy().view(np.uint64) == ref["hash"]).all()
     assert (t["km_off"].cpu().numpy().view(np.uint64) == ref["km_off"]).all()
-    assert (t["start"].cpu().numpy().view(np.uint32) == ref["start"]).all()
-    assert (t["rev"].cpu().numpy() == ref["rev"]).all()
+    assert (t["start"][:nk].cpu().numpy().view(np.uint32) == ref["start"]).all()
+    assert (t["rev"][:nk].cpu().numpy() == ref["rev"]).all()
+    assert (t["hash"][nk:] == -7).all().item() and (t["rev"][nk:] == 0xA5).all().item()
     # misaligned base pointers stay on the tiled kernels (the library realigns the stream with one device copy), same answer
     for shift in (1, 7, 15):
         d_b2 = torch.zeros(len(bases) + 16, dtype=torch.uint8, device=dev)
