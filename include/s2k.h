@@ -40,6 +40,8 @@ extern "C" {
  * (s2k_count_device_ex and S2K_COUNT_SORTED were added later the same way: an added entry point, the version stays 2.)
  * (s2k_count_merge_device, the opaque s2k_counter with s2k_counter_create / _destroy / _add / _finish, and s2k_run_file_count were
  * added the same way: added entry points and one opaque type, the version stays 2.)
+ * (The opaque s2k_table with s2k_table_create / _destroy / _lookup / _filter and the struct s2k_solid_out were added the same way:
+ * added entry points, one opaque type and one new struct; no existing entry point or struct changed, the version stays 2.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -253,6 +255,41 @@ void s2k_counter_destroy(s2k_counter *c);
 s2k_status s2k_counter_add(s2k_counter *c, const uint64_t *d_hash, uint64_t n);
 s2k_status s2k_counter_finish(s2k_counter *c, uint32_t min_count, uint64_t *d_keys, uint32_t *d_counts, uint64_t capacity,
                               uint64_t *n_distinct, uint64_t *n_kept);
+/* Look-ups against a count table (rust-mdbg's second pass: each read's k-min-mers with their abundance, the solid ones kept).
+ * s2k_table_create indexes (d_keys, d_counts)[0..n), any table strictly ascending by key (unsigned 64-bit) -- what
+ * s2k_count_device_ex(S2K_COUNT_SORTED), s2k_count_merge_device and s2k_counter_finish write.  The table BORROWS the two arrays: they
+ * must stay valid and unchanged until s2k_table_destroy.  d_counts == NULL makes a membership table (every key present counts 1).
+ * n == 0 is allowed (every look-up gives 0); n >= 2^32 is refused (S2K_ERR_INVALID_ARG).  Every 64-bit value is a key, 0 and 2^64-1
+ * included.  A table that is not strictly ascending is detected on the device: NULL and S2K_ERR_INVALID_ARG.  Device memory owned
+ * by the table: a directory over the top B bits of the keys (4 B x (2^B + 1), B chosen for 4-7 keys per bucket, at most 26: at most
+ * about 1 B per key, 256 MiB).  Destroy a table before its context; one thread at a time per context, as for every call on it. */
+typedef struct s2k_table s2k_table; /* opaque: a read-only index over a count table */
+s2k_table *s2k_table_create(s2k_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_counts, uint64_t n, s2k_status *status);
+void s2k_table_destroy(s2k_table *t);
+/* d_out[i] = the count of d_query[i] in the table, 0 if absent, for i < n (any n, 0 included).  Runs on the context's stream;
+ * returns when d_out is written. */
+s2k_status s2k_table_lookup(s2k_table *t, const uint64_t *d_query, uint64_t n, uint32_t *d_out);
+/* Output of s2k_table_filter (device pointers; capacity in items).  Kept item i of read r (km_off[r] <= i < km_off[r+1]) is
+ * KminmerHash{ hash[i], start[i], end[i], offset[i], rev[i] } (src/kminmer.rs:128-135) with offset = its index in the read before
+ * filtering (so a consumer can tell which kept k-min-mers were adjacent) and count[i] = the table's count of hash[i]. */
+typedef struct s2k_solid_out {
+    uint64_t capacity;
+    uint64_t *km_off; /* n_reads + 1, required */
+    uint64_t *hash;   /* every item array may be NULL */
+    uint32_t *start;
+    uint32_t *end;
+    uint8_t *rev;
+    uint32_t *offset;
+    uint32_t *count;
+} s2k_solid_out;
+/* For every read of `in` (the s2k_device_out that s2k_extract_device filled for n_reads reads: km_off and hash required, km_off[0]
+ * == 0; start / end / rev optional), the k-min-mers whose count in the table is at least min_count (0 and 1 both mean "present"),
+ * in read order.  An output array whose input array is NULL must be NULL (S2K_ERR_INVALID_ARG).  *n_kept is always set and
+ * out->km_off always written; the item arrays are written only when *n_kept <= out->capacity, otherwise S2K_ERR_CAPACITY and
+ * nothing is written to them; all NULL asks for the sizes only.  Uses the context's grow-only count workspace (shared with
+ * s2k_count_device_ex): about 4.2 B per input item.  Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_table_filter(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t min_count, const s2k_solid_out *out,
+                            uint64_t *n_kept);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

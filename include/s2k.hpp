@@ -169,6 +169,35 @@ class Counter {
     s2k_counter *c_;
 };
 
+// Look-ups against a count table (s2k_table_*): the table borrows d_keys / d_counts (d_counts may be nullptr: membership), which must
+// stay valid and unchanged while it lives.  lookup() writes each query's count (0 if absent); filter() keeps each read's k-min-mers
+// whose count is at least min_count and returns how many were kept (throws on S2K_ERR_CAPACITY too).  Destroy it before its Engine.
+class Table {
+  public:
+    Table(Engine &eng, const uint64_t *d_keys, const uint32_t *d_counts, uint64_t n) : eng_(&eng) {
+        s2k_status st;
+        t_ = s2k_table_create(eng.raw(), d_keys, d_counts, n, &st);
+        if (!t_) throw Error(st, std::string("s2k_table_create: ") + s2k_strerror(st) + ": " + s2k_last_error(eng.raw()));
+    }
+    Table(const Table &) = delete;
+    Table &operator=(const Table &) = delete;
+    ~Table() { s2k_table_destroy(t_); }
+    void lookup(const uint64_t *d_query, uint64_t n, uint32_t *d_out) { check(s2k_table_lookup(t_, d_query, n, d_out)); }
+    uint64_t filter(uint64_t n_reads, const s2k_device_out &in, uint32_t min_count, const s2k_solid_out &out) {
+        uint64_t n_kept = 0;
+        check(s2k_table_filter(t_, n_reads, &in, min_count, &out, &n_kept));
+        return n_kept;
+    }
+    s2k_table *raw() { return t_; }
+
+  private:
+    void check(s2k_status st) {
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(eng_->raw()));
+    }
+    Engine *eng_;
+    s2k_table *t_;
+};
+
 class KminmersIterator { // src/lib.rs:70-131: per-read facade
   public:
     KminmersIterator(Engine &eng, std::string_view seq, size_t l, size_t k, double density, HashMode mode)

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "s2k_last_error", "s2k_hash_bound", "s2k_extract", "s2k_result_free", "s2k_extract_device", "s2k_sync",
     "s2k_hpc_device", "s2k_hpc_device_ex", "s2k_count_device", "s2k_count_device_ex", "s2k_partition_device", "s2k_synth_bases_device", "s2k_synth_hifi_lengths", "s2k_synth_hifi_device", "s2k_last_kernel_ms", "s2k_enable_timing", "s2k_timing_total", "s2k_fastx_open", "s2k_fastx_next", "s2k_fastx_close", "s2k_run_file", "s2k_fastx_parse_device",
     "s2k_count_merge_device", "s2k_counter_create", "s2k_counter_destroy", "s2k_counter_add", "s2k_counter_finish", "s2k_run_file_count",
+    "s2k_table_create", "s2k_table_destroy", "s2k_table_lookup", "s2k_table_filter",
 ]
 
 
@@ -77,6 +78,11 @@ class DeviceOut(C.Structure):
     _fields_ = [("km_capacity", C.c_uint64), ("km_off", C.c_void_p), ("hash", C.c_void_p), ("start", C.c_void_p),
                 ("end", C.c_void_p), ("rev", C.c_void_p), ("mn_capacity", C.c_uint64), ("mn_off", C.c_void_p),
                 ("mn_j", C.c_void_p), ("mn_jend", C.c_void_p), ("mn_hash", C.c_void_p)]
+
+
+class SolidOut(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("km_off", C.c_void_p), ("hash", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p),
+                ("rev", C.c_void_p), ("offset", C.c_void_p), ("count", C.c_void_p)]
 
 
 _lib = None
@@ -141,6 +147,12 @@ def load_library(path=None):
     L.s2k_counter_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.s2k_counter_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.s2k_run_file_count.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Params), C.c_uint64, C.c_void_p, C.POINTER(Counts), C.POINTER(C.c_double)]
+    L.s2k_table_create.restype = C.c_void_p
+    L.s2k_table_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int)]
+    L.s2k_table_destroy.restype = None
+    L.s2k_table_destroy.argtypes = [C.c_void_p]
+    L.s2k_table_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.s2k_table_filter.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.POINTER(SolidOut), C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -463,6 +475,83 @@ class KminmerCounter:
             self.engine._check(self.lib.s2k_counter_finish(self.handle, int(min_count), C.c_void_p(keys.data_ptr()), C.c_void_p(counts.data_ptr()),
                                                            nk, C.byref(a), C.byref(b)))
         return keys[:nk], counts[:nk]
+
+
+class CountTable:
+    """Look-ups against a count table (s2k_table_*): keys (1-D 64-bit tensor on the engine's device, strictly ascending as uint64) and
+    counts (32-bit tensor of the same length, or None for a membership table), as KminmerCounter.finish or Engine.count_device_ex write
+    them.  The table borrows both tensors (it keeps references to them); they must not change until close().  close() it before its
+    Engine."""
+
+    def __init__(self, engine, keys, counts=None):
+        import torch
+
+        for t, size in ((keys, 8), (counts, 4)):
+            if t is not None and (t.dim() != 1 or t.element_size() != size or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("CountTable wants contiguous 1-D GPU tensors: keys of 64-bit, counts of 32-bit elements")
+        if counts is not None and counts.numel() != keys.numel():
+            raise ValueError("keys and counts differ in length")
+        self.engine = engine
+        self.lib = engine.lib
+        self.keys, self.counts, self.n = keys, counts, keys.numel()
+        torch.cuda.synchronize(keys.device)  # the library's stream does not follow torch's
+        st = C.c_int(0)
+        self.handle = self.lib.s2k_table_create(engine.ctx, C.c_void_p(keys.data_ptr() if self.n else 0),
+                                                C.c_void_p(counts.data_ptr() if counts is not None and self.n else 0), self.n, C.byref(st))
+        if not self.handle:
+            raise S2kError(st.value, self.lib.s2k_strerror(st.value).decode() + " -- " + self.lib.s2k_last_error(engine.ctx).decode())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.s2k_table_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def lookup(self, query):
+        """-> int32 tensor (the uint32 counts' bits) of the count of every element of `query` (1-D 64-bit GPU tensor), 0 if absent"""
+        import torch
+
+        if query.dim() != 1 or query.element_size() != 8 or not query.is_cuda:
+            raise ValueError("lookup wants a 1-D 64-bit tensor on the GPU")
+        query = query.contiguous()
+        out = torch.empty(max(query.numel(), 1), dtype=torch.int32, device=query.device)
+        torch.cuda.synchronize(query.device)
+        self.engine._check(self.lib.s2k_table_lookup(self.handle, C.c_void_p(query.data_ptr()), query.numel(), C.c_void_p(out.data_ptr())))
+        return out[:query.numel()]
+
+    def filter(self, out_tensors, n_reads, min_count=2):
+        """Each read's k-min-mers whose count is at least min_count, in read order (s2k_table_filter).  out_tensors: the GPU tensors
+        extract_device wrote (dict with km_off and hash; start / end / rev optional).  -> dict of GPU tensors km_off (n_reads + 1),
+        hash, offset (index in the read before filtering), count, and start / end / rev where given; 'n' = kept items."""
+        import torch
+
+        dev = out_tensors["km_off"].device
+        n_items = int(out_tensors["km_off"][n_reads].item()) if n_reads else 0
+        cap = max(n_items, 1)
+        res = {"km_off": torch.empty(n_reads + 1, dtype=torch.int64, device=dev), "hash": torch.empty(cap, dtype=torch.int64, device=dev),
+               "offset": torch.empty(cap, dtype=torch.int32, device=dev), "count": torch.empty(cap, dtype=torch.int32, device=dev)}
+        i, o = DeviceOut(), SolidOut()
+        i.km_capacity = n_items
+        i.km_off, i.hash = out_tensors["km_off"].data_ptr(), out_tensors["hash"].data_ptr()
+        for f, dt in (("start", torch.int32), ("end", torch.int32), ("rev", torch.uint8)):
+            if out_tensors.get(f) is not None:
+                res[f] = torch.empty(cap, dtype=dt, device=dev)
+                setattr(i, f, out_tensors[f].data_ptr())
+        o.capacity = cap
+        for f, t in res.items():
+            setattr(o, f, t.data_ptr())
+        nk = C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self.engine._check(self.lib.s2k_table_filter(self.handle, n_reads, C.byref(i), int(min_count), C.byref(o), C.byref(nk)))
+        n = int(nk.value)
+        out = {f: (t if f == "km_off" else t[:n]) for f, t in res.items()}
+        out["n"] = n
+        return out
 
 
 class FastxReader:

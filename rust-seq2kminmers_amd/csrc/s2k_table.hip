@@ -1,0 +1,468 @@
+// s2k_table.hip -- look-ups against a count table that is strictly ascending by key (what s2k_count_device_ex(S2K_COUNT_SORTED),
+// s2k_count_merge_device and s2k_counter_finish produce), and the per-read filter that keeps each read's solid k-min-mers
+// (include/s2k.h: s2k_table_*).
+//
+// Index (once per table, table_index_kernel): one coalesced pass over the keys.  Each key is compared with the one before it (one
+// flag word records a failure), and dir[p] = the first key index whose top B bits are at least p, for p = 0 .. 2^B (2^B + 1 u32
+// entries; dir[2^B] = n).  Lane i writes the entries (prefix(key[i-1]), prefix(key[i])]; the last lane also the tail up to 2^B.
+// B is chosen from n for 4-7 keys per bucket on average (TB_KEYS_PER_BUCKET, measured); buckets are not uniform and nothing depends
+// on their size: a bucket that holds the whole table is searched the same way, only slower.
+//
+// Look-up (lookup_many): every lane takes TB_Q queries and issues all 2 x TB_Q directory loads before the first use; then the
+// TB_Q binary searches over [dir[p], dir[p+1]) run interleaved, one key load per search per step (unconditional, at a clamped
+// index, so the compiler keeps them in flight together); the count is loaded on a hit only.  No atomics.
+//
+// Filter, a stable stream compaction over the k-min-mer items, tiles of TB_TILE items (lane tid holds items r * 256 + tid):
+//  1. filter_count_kernel: the look-up fused in; per item its count (4 B of workspace, so the write pass does not look up again),
+//     per 64 items a kept mask (one wave's ballot) and the kept items before that word inside the tile; per tile the kept total.
+//  2. launch_scan_u32 over the tile totals: each tile's first output slot.
+//  3. filter_offsets_kernel: out->km_off[r] = kept items before input index km_off[r] (tile start + word prefix + mask popcount).
+//  4. filter_write_kernel (only when item outputs are wanted and fit): each kept item goes to LDS at its tile-relative slot, one
+//     output array at a time, and leaves the workgroup as one contiguous, coalesced run.  offset = item index - its read's first
+//     item, the read found by a binary search of km_off narrowed to the reads that overlap the tile.
+#include <algorithm>
+#include <cstdlib>
+#include <new>
+
+#include "../../include/s2k.h"
+#include "s2k_dev.h"
+#include "s2k_hostcopy.h"
+
+namespace s2k {
+namespace {
+
+constexpr int TB_THREADS = 256;
+constexpr int TB_Q = 8;                             // queries (items) per lane
+constexpr uint32_t TB_TILE = TB_THREADS * TB_Q;    // 2 048 items per workgroup of the filter
+constexpr int TB_WORDS = TB_TILE / 64;              // kept-mask words per tile
+constexpr uint64_t TB_KEYS_PER_BUCKET = 4;          // B = floor(log2(n / 4)): 4-7 keys per bucket on average
+constexpr uint32_t TB_MAX_BITS = 26;
+
+struct TableView {
+    const uint64_t *keys;
+    const uint32_t *counts; // NULL: membership table (count 1)
+    const uint32_t *dir;    // 2^bits + 1 entries
+    uint32_t n;
+    uint32_t shift;         // 64 - bits
+};
+
+// c[r] = count of q[r] in the table (0 if absent)
+__device__ inline void lookup_many(const TableView &tv, const uint64_t (&q)[TB_Q], uint32_t (&c)[TB_Q]) {
+    if (tv.n == 0) {
+#pragma unroll
+        for (int r = 0; r < TB_Q; r++) c[r] = 0;
+        return;
+    }
+    uint32_t lo[TB_Q], hi[TB_Q], pos[TB_Q];
+    bool hit[TB_Q];
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) { // every directory load in flight before the first use
+        const uint64_t p = q[r] >> tv.shift;
+        lo[r] = tv.dir[p];
+        hi[r] = tv.dir[p + 1];
+    }
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) {
+        hit[r] = false;
+        pos[r] = 0;
+    }
+    for (;;) { // TB_Q searches side by side; a finished one reloads its last key (a cache hit) instead of branching around the load
+        uint64_t kv[TB_Q];
+        uint32_t mid[TB_Q];
+#pragma unroll
+        for (int r = 0; r < TB_Q; r++) {
+            mid[r] = (lo[r] + hi[r]) >> 1;
+            kv[r] = tv.keys[std::min<uint32_t>(mid[r], tv.n - 1)];
+        }
+        bool more = false;
+#pragma unroll
+        for (int r = 0; r < TB_Q; r++) {
+            if (lo[r] < hi[r]) {
+                if (kv[r] < q[r]) lo[r] = mid[r] + 1;
+                else if (kv[r] > q[r]) hi[r] = mid[r];
+                else { // keys are strictly ascending: the one match
+                    hit[r] = true;
+                    pos[r] = mid[r];
+                    lo[r] = hi[r];
+                }
+                more |= lo[r] < hi[r];
+            }
+        }
+        if (!more) break;
+    }
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) c[r] = hit[r] ? (tv.counts ? tv.counts[pos[r]] : 1u) : 0u;
+}
+
+__global__ __launch_bounds__(256) void table_index_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint32_t shift, uint32_t bits,
+                                                          uint32_t *__restrict__ dir, uint32_t *__restrict__ bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t k = keys[i], p = k >> shift;
+    uint64_t from = 0;
+    if (i > 0) {
+        const uint64_t prev = keys[i - 1];
+        if (!(prev < k)) {
+            atomicOr(bad, 1u);
+            return;
+        }
+        from = (prev >> shift) + 1;
+    }
+    for (uint64_t x = from; x <= p; x++) dir[x] = (uint32_t)i;
+    if (i + 1 == n)
+        for (uint64_t x = p + 1; x <= (1ull << bits); x++) dir[x] = n;
+}
+
+__global__ __launch_bounds__(TB_THREADS) void table_lookup_kernel(TableView tv, const uint64_t *__restrict__ query, uint64_t n,
+                                                                  uint32_t *__restrict__ out) {
+    const uint64_t base = (uint64_t)blockIdx.x * TB_TILE + threadIdx.x;
+    uint64_t q[TB_Q];
+    uint32_t c[TB_Q];
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) q[r] = query[std::min<uint64_t>(base + (uint64_t)r * TB_THREADS, n - 1)];
+    lookup_many(tv, q, c);
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++)
+        if (base + (uint64_t)r * TB_THREADS < n) out[base + (uint64_t)r * TB_THREADS] = c[r];
+}
+
+struct FilterWs {
+    uint32_t *cnt;       // per item: its count
+    uint64_t *wmask;     // per 64 items: kept mask
+    uint32_t *wpre;      // per 64 items: kept items before the word inside its tile
+    uint32_t *tile_kept; // per tile
+    uint64_t *tile_off;  // n_tiles + 1
+};
+
+__global__ __launch_bounds__(TB_THREADS) void filter_count_kernel(TableView tv, const uint64_t *__restrict__ hash, uint64_t n_items, uint32_t minc,
+                                                                  FilterWs ws) {
+    __shared__ uint32_t wc[TB_WORDS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
+    uint64_t q[TB_Q];
+    uint32_t c[TB_Q];
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) q[r] = hash[std::min<uint64_t>(t0 + (uint64_t)r * TB_THREADS + tid, n_items - 1)];
+    lookup_many(tv, q, c);
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) {
+        const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
+        const bool valid = j < n_items;
+        if (valid) ws.cnt[j] = c[r];
+        const uint64_t m = __ballot(valid && c[r] >= minc);
+        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64; // first item of this wave's word
+        if (lane == 0) {
+            wc[r * 4 + wv] = (uint32_t)__popcll(m);
+            if (w0 < n_items) ws.wmask[w0 >> 6] = m;
+        }
+    }
+    __syncthreads();
+    if (tid < TB_WORDS) { // word k of the tile = items t0 + 64k ..: r = k / 4, wave k % 4
+        uint32_t pre = 0;
+        for (int x = 0; x < tid; x++) pre += wc[x];
+        const uint64_t w0 = t0 + (uint64_t)tid * 64;
+        if (w0 < n_items) ws.wpre[w0 >> 6] = pre;
+        if (tid == TB_WORDS - 1) ws.tile_kept[blockIdx.x] = pre + wc[tid];
+    }
+}
+
+// kept items before input index j (j <= n_items)
+__device__ inline uint64_t kept_before(const FilterWs &ws, uint64_t n_items, uint64_t n_tiles, uint64_t j) {
+    if (j >= n_items) return ws.tile_off[n_tiles];
+    const uint64_t w = j >> 6;
+    const uint64_t below = (j & 63) ? ws.wmask[w] & ((1ull << (j & 63)) - 1ull) : 0ull;
+    return ws.tile_off[j / TB_TILE] + ws.wpre[w] + (uint64_t)__popcll(below);
+}
+
+__global__ __launch_bounds__(256) void filter_offsets_kernel(const uint64_t *__restrict__ km_off, uint64_t n_reads, uint64_t n_items, uint64_t n_tiles,
+                                                             FilterWs ws, uint64_t *__restrict__ o_km_off) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n_reads) return;
+    o_km_off[r] = kept_before(ws, n_items, n_tiles, km_off[r]);
+}
+
+// the last read r in [lo, hi] with km_off[r] <= j (km_off[lo] <= j holds)
+__device__ inline uint64_t read_of(const uint64_t *__restrict__ km_off, uint64_t lo, uint64_t hi, uint64_t j) {
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (km_off[mid] <= j) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+struct FilterIo {
+    const uint64_t *km_off;
+    uint64_t n_reads;
+    const uint64_t *hash;
+    const uint32_t *start, *end;
+    const uint8_t *rev;
+    uint64_t *o_hash;
+    uint32_t *o_start, *o_end, *o_offset, *o_count;
+    uint8_t *o_rev;
+    uint64_t capacity;
+};
+
+__global__ __launch_bounds__(TB_THREADS) void filter_write_kernel(FilterIo io, uint64_t n_items, uint32_t minc, FilterWs ws) {
+    __shared__ uint64_t s64[TB_TILE];
+    __shared__ uint64_t sread[2];
+    uint32_t *s32 = (uint32_t *)s64;
+    uint8_t *s8 = (uint8_t *)s64;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE, t1 = std::min<uint64_t>(t0 + TB_TILE, n_items);
+    const uint64_t base = ws.tile_off[blockIdx.x], tot = ws.tile_off[blockIdx.x + 1] - base;
+    if (tot == 0) return;
+    if (tid < 2 && io.o_offset) // the reads that hold the tile's first and last item
+        sread[tid] = read_of(io.km_off, 0, io.n_reads - 1, tid == 0 ? t0 : t1 - 1);
+    uint32_t slot[TB_Q], cnt[TB_Q];
+    uint32_t keep = 0;
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) {
+        const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
+        cnt[r] = ws.cnt[std::min<uint64_t>(j, n_items - 1)];
+        const bool kept = j < n_items && cnt[r] >= minc;
+        const uint64_t m = __ballot(kept);
+        const uint64_t w = (t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64) >> 6;
+        slot[r] = (kept ? ws.wpre[w] : 0u) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        keep |= kept ? 1u << r : 0u;
+    }
+    __syncthreads();
+    const uint64_t rlo = io.o_offset ? sread[0] : 0, rhi = io.o_offset ? sread[1] : 0;
+#define TB_STAGE(ARR, VAL)                                                                  \
+    do {                                                                                    \
+        _Pragma("unroll") for (int r = 0; r < TB_Q; r++) if (keep & (1u << r)) {            \
+            const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;                         \
+            (void)j;                                                                        \
+            ARR[slot[r]] = (VAL);                                                           \
+        }                                                                                   \
+        __syncthreads();                                                                    \
+    } while (0)
+#define TB_LEAVE(OUT, ARR)                                                                  \
+    do {                                                                                    \
+        for (uint32_t i = tid; i < tot; i += TB_THREADS) {                                  \
+            if (base + i >= io.capacity) break; /* the host checked n_kept <= capacity */   \
+            OUT[base + i] = ARR[i];                                                         \
+        }                                                                                   \
+        __syncthreads();                                                                    \
+    } while (0)
+    if (io.o_hash) {
+        TB_STAGE(s64, io.hash[j]);
+        TB_LEAVE(io.o_hash, s64);
+    }
+    if (io.o_start) {
+        TB_STAGE(s32, io.start[j]);
+        TB_LEAVE(io.o_start, s32);
+    }
+    if (io.o_end) {
+        TB_STAGE(s32, io.end[j]);
+        TB_LEAVE(io.o_end, s32);
+    }
+    if (io.o_rev) {
+        TB_STAGE(s8, io.rev[j]);
+        TB_LEAVE(io.o_rev, s8);
+    }
+    if (io.o_count) {
+        TB_STAGE(s32, cnt[r]);
+        TB_LEAVE(io.o_count, s32);
+    }
+    if (io.o_offset) {
+        TB_STAGE(s32, (uint32_t)(j - io.km_off[read_of(io.km_off, rlo, rhi, j)]));
+        TB_LEAVE(io.o_offset, s32);
+    }
+#undef TB_STAGE
+#undef TB_LEAVE
+}
+
+size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+uint32_t table_bits(uint64_t n) {
+    uint32_t b = 1;
+    while (b < TB_MAX_BITS && (n >> (b + 1)) >= TB_KEYS_PER_BUCKET) b++; // largest b with n / 2^b >= 4
+#ifdef S2K_DEBUG_KNOBS // `make KNOBS=1` only: S2K_DEBUG_TABLE_BITS fixes B (tools/table_rate.py --bits-sweep)
+    if (const char *e = std::getenv("S2K_DEBUG_TABLE_BITS")) {
+        const long v = std::strtol(e, nullptr, 10);
+        if (v >= 1 && v <= (long)TB_MAX_BITS) b = (uint32_t)v;
+    }
+#endif
+    return b;
+}
+
+} // namespace
+} // namespace s2k
+
+using namespace s2k;
+
+struct s2k_table {
+    s2k_ctx *ctx;
+    const uint64_t *keys;
+    const uint32_t *counts;
+    uint64_t n;
+    uint32_t bits;
+    uint32_t *dir; // 2^bits + 1 entries, then the validation flag
+    TableView view() const { return TableView{keys, counts, dir, (uint32_t)n, 64u - bits}; }
+};
+
+extern "C" {
+
+s2k_table *s2k_table_create(s2k_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_counts, uint64_t n, s2k_status *status) {
+    auto fail = [&](s2k_status s) -> s2k_table * {
+        if (status) *status = s;
+        return nullptr;
+    };
+    if (!ctx || (n && !d_keys)) return fail(S2K_ERR_INVALID_ARG);
+    if (n >= (1ull << 32)) {
+        ctx_set_error(ctx, "s2k_table_create: 2^32 keys or more");
+        return fail(S2K_ERR_INVALID_ARG);
+    }
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return fail(S2K_ERR_DEVICE);
+    s2k_table *t = new (std::nothrow) s2k_table;
+    if (!t) return fail(S2K_ERR_NOMEM);
+    t->ctx = ctx;
+    t->keys = d_keys;
+    t->counts = d_counts;
+    t->n = n;
+    t->bits = table_bits(n);
+    const size_t dir_n = (1ull << t->bits) + 1;
+    if (hipMalloc((void **)&t->dir, (dir_n + 1) * 4) != hipSuccess) {
+        delete t;
+        ctx_set_error(ctx, "s2k_table_create: directory allocation");
+        return fail(S2K_ERR_NOMEM);
+    }
+    uint32_t *bad = t->dir + dir_n;
+    hipStream_t st = ctx_stream(ctx);
+    hipError_t e = hipMemsetAsync(t->dir, 0, (dir_n + 1) * 4, st); // n == 0: every bucket empty
+    if (e == hipSuccess && n) {
+        hipLaunchKernelGGL(table_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_keys, (uint32_t)n, 64u - t->bits, t->bits,
+                           t->dir, bad);
+        e = hipGetLastError();
+    }
+    uint32_t hbad = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = ctx_sync(ctx);
+    s2k_status s = S2K_OK;
+    if (e != hipSuccess) {
+        ctx_set_error(ctx, "s2k_table_create: HIP error");
+        s = S2K_ERR_DEVICE;
+    } else if (hbad) {
+        ctx_set_error(ctx, "s2k_table_create: the keys are not strictly ascending");
+        s = S2K_ERR_INVALID_ARG;
+    }
+    if (s != S2K_OK) {
+        (void)hipFree(t->dir);
+        delete t;
+        return fail(s);
+    }
+    if (status) *status = S2K_OK;
+    return t;
+}
+
+void s2k_table_destroy(s2k_table *t) {
+    if (!t) return;
+    (void)hipSetDevice(ctx_device(t->ctx));
+    (void)hipFree(t->dir);
+    delete t;
+}
+
+s2k_status s2k_table_lookup(s2k_table *t, const uint64_t *d_query, uint64_t n, uint32_t *d_out) {
+    if (!t || (n && (!d_query || !d_out))) return S2K_ERR_INVALID_ARG;
+    if (n == 0) return S2K_OK;
+    s2k_ctx *ctx = t->ctx;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
+    hipStream_t st = ctx_stream(ctx);
+    const uint64_t nb = (n + TB_TILE - 1) / TB_TILE;
+    if (nb >= (1ull << 32)) {
+        ctx_set_error(ctx, "s2k_table_lookup: too many queries for one call");
+        return S2K_ERR_INVALID_ARG;
+    }
+    hipLaunchKernelGGL(table_lookup_kernel, dim3((unsigned)nb), dim3(TB_THREADS), 0, st, t->view(), d_query, n, d_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = ctx_sync(ctx);
+    if (e != hipSuccess) {
+        ctx_set_error(ctx, "s2k_table_lookup: HIP error");
+        return S2K_ERR_DEVICE;
+    }
+    return S2K_OK;
+}
+
+s2k_status s2k_table_filter(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t min_count, const s2k_solid_out *out,
+                            uint64_t *n_kept) {
+    if (n_kept) *n_kept = 0;
+    if (!t || !in || !out || !n_kept || !in->km_off || !in->hash || !out->km_off || (out->start && !in->start) || (out->end && !in->end) ||
+        (out->rev && !in->rev))
+        return S2K_ERR_INVALID_ARG;
+    s2k_ctx *ctx = t->ctx;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
+    hipStream_t st = ctx_stream(ctx);
+    uint64_t ends[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(&ends[0], in->km_off, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&ends[1], in->km_off + n_reads, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = ctx_sync(ctx);
+    if (e != hipSuccess) {
+        ctx_set_error(ctx, "s2k_table_filter: HIP error");
+        return S2K_ERR_DEVICE;
+    }
+    if (ends[0] != 0 || ends[1] < ends[0]) {
+        ctx_set_error(ctx, "s2k_table_filter: in->km_off must start at 0 and end at or after its start");
+        return S2K_ERR_INVALID_ARG;
+    }
+    const uint64_t n_items = ends[1];
+    if (n_items == 0) { // no items: every read is empty
+        e = hipMemsetAsync(out->km_off, 0, (n_reads + 1) * 8, st);
+        if (e == hipSuccess) e = ctx_sync(ctx);
+        if (e != hipSuccess) {
+            ctx_set_error(ctx, "s2k_table_filter: HIP error");
+            return S2K_ERR_DEVICE;
+        }
+        return S2K_OK;
+    }
+    const uint64_t nt = (n_items + TB_TILE - 1) / TB_TILE, nw = (n_items + 63) / 64;
+    if (nt >= (1ull << 32) || n_reads + 1 >= (1ull << 40)) {
+        ctx_set_error(ctx, "s2k_table_filter: too many items for one call");
+        return S2K_ERR_INVALID_ARG;
+    }
+    size_t off = 0;
+    const size_t oC = off; off += al(n_items * 4);
+    const size_t oM = off; off += al(nw * 8);
+    const size_t oP = off; off += al(nw * 4);
+    const size_t oK = off; off += al(nt * 4);
+    const size_t oO = off; off += al((nt + 1) * 8);
+    const size_t oT = off; off += al(scan_tmp_bytes(nt));
+    char *w = (char *)ctx_count_table(ctx, off);
+    if (!w) {
+        ctx_set_error(ctx, "s2k_table_filter: workspace allocation");
+        return S2K_ERR_NOMEM;
+    }
+    FilterWs ws{(uint32_t *)(w + oC), (uint64_t *)(w + oM), (uint32_t *)(w + oP), (uint32_t *)(w + oK), (uint64_t *)(w + oO)};
+    const uint32_t minc = min_count ? min_count : 1u;
+    hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, t->view(), in->hash, n_items, minc, ws);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = launch_scan_u32(ws.tile_kept, nt, ws.tile_off, (uint64_t *)(w + oT), 0, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(filter_offsets_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, st, in->km_off, n_reads, n_items, nt, ws,
+                           out->km_off);
+        e = hipGetLastError();
+    }
+    uint64_t kept = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&kept, ws.tile_off + nt, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = ctx_sync(ctx);
+    if (e != hipSuccess) {
+        ctx_set_error(ctx, "s2k_table_filter: HIP error");
+        return S2K_ERR_DEVICE;
+    }
+    *n_kept = kept;
+    const bool want = out->hash || out->start || out->end || out->rev || out->offset || out->count;
+    if (!want || kept == 0) return S2K_OK;
+    if (kept > out->capacity) return S2K_ERR_CAPACITY;
+    FilterIo io{in->km_off, n_reads, in->hash, in->start, in->end, in->rev, out->hash, out->start, out->end, out->offset, out->count, out->rev,
+                out->capacity};
+    hipLaunchKernelGGL(filter_write_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, io, n_items, minc, ws);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = ctx_sync(ctx);
+    if (e != hipSuccess) {
+        ctx_set_error(ctx, "s2k_table_filter: HIP error");
+        return S2K_ERR_DEVICE;
+    }
+    return S2K_OK;
+}
+
+} // extern "C"
