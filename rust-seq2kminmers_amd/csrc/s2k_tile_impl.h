@@ -645,43 +645,38 @@ __device__ __forceinline__ uint32_t hpc_compact(uint8_t *D, WL &S, const uint8_t
         fmk[0] = r01.x; fmk[1] = r01.y; fmk[2] = r23.x; fmk[3] = r23.y;
         fmk[4] = S.row[lane][4];
     }
-    uint32_t prevw;
-    if (lane == 0) {
-        if (forced0) fmk[0] |= 1u; // the tile starts a read
-        prevw = prev_byte0 << 24;
-    } else {
-        prevw = (uint32_t)D[lane_off - 1] << 24;
-    }
+    if (lane == 0 && forced0) fmk[0] |= 1u; // the tile starts a read
+    // the byte before the lane's chunk at the top of prevw: the lane before's last dword (DPP wave_shr:1), the byte before the tile in lane 0
+    const uint32_t prevw = (uint32_t)__builtin_amdgcn_update_dpp((int)(prev_byte0 << 24), (int)c[35], 0x138, 0xf, 0xf, false);
     const uint32_t last_raw = bcast(c[35] >> 24, 63); // last raw byte of a full tile
     // the 128 staged look-ahead bytes serve the first round of the run-head search after the tile; read them
     // before the buffer is compacted in place (lanes 0..31, 4 bytes each)
     const uint32_t la_a = D[TILE_BASES + lane], la_b = D[TILE_BASES + 64 + lane]; // (one byte per lane and round)
     const int vb = (int)tile_len - (int)lane_off;      // valid bytes in this lane's chunk (may be <=0 or >=144)
     const bool partial = tile_len < (uint32_t)TILE_BASES;
-    // 3. pass 1: SWAR "differs from its predecessor" per byte -> four flags per dword -> natural-order masks
-    uint32_t pair7 = 0;
+    // 3. pass 1: "differs from its predecessor" per byte -> four flags per dword -> natural-order masks.  Four vector instructions per dword:
+    //    the predecessor bytes (v_alignbyte_b32), x = cur ^ prv ^ 0x0C0C0C0C (one v_bitop3_b32), and x as the selector of a v_perm_b32 whose
+    //    two sources are all ones -- a selector byte gives 0x00 for 12 and 0xFF for every other value, so 0xFF per byte that differs (the
+    //    SWAR "(((x & 0x7F7F7F7F) + 0x7F7F7F7F) | x) & 0x80808080" was three instructions and the xor a fourth); then one dot product.
+    uint32_t pr[4];
 #pragma unroll
     for (int d = 0; d < 36; d++) {
         const uint32_t cur = c[d];
         const uint32_t prv = __builtin_amdgcn_alignbyte(cur, d == 0 ? prevw : c[d - 1], 3); // predecessor of every byte
-        const uint32_t x = cur ^ prv;
-        const uint32_t y = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; // 0x80 per byte that differs
-        // the four flags as a nibble: one dot product with the weights 1, 2, 4, 8 (x 128: the flags sit at bit 7); the odd dword of a
-        // pair ADDS its nibble above the even one's (weights x 16 and the accumulator operand), so that two dwords cost one shift-or
-        if ((d & 1) == 0) {
-            pair7 = __builtin_amdgcn_udot4(y, 0x08040201u, 0u, false);
-        } else {
-            pair7 = __builtin_amdgcn_udot4(y, 0x80402010u, pair7, false);
-            const int sh = 8 * ((d & 7) >> 1) - 7; // (constants once the loop is unrolled)
-            // (v_lshl_or_b32: the opaque copy keeps the compiler from re-associating the ors into a tree of separate shifts and ors.
-            // The instruction itself must stay the compiler's: on gfx950 a VALU instruction may read a v_dot4 result only three wait
-            // states after it, which the hazard recognizer cannot arrange for an instruction hidden in inline asm -- measured: wrong flags)
-            if (sh >= 0) {
-                fmk[d >> 3] = (pair7 << (sh >= 0 ? sh : 0)) | fmk[d >> 3];
-                asm("" : "+v"(fmk[d >> 3]));
-            }
-            else fmk[d >> 3] |= pair7 >> 7;
-        }
+        uint32_t x; // (asm: left to itself the compiler splits the three-input xor in two)
+        asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(x) : "v"(cur), "v"(prv), "v"(0x0C0C0C0Cu));
+        const uint32_t y = __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, x); // 0xFF per byte that differs, else 0
+        // the eight flags of a pair of dwords as 255 (flags + 1): dot products with the weights 1, 2, 4, 8 (even dword, accumulator 255)
+        // and 16, 32, 64, 128 (odd dword, accumulating); 255 (P + 1) = 256 P + (255 - P) for P <= 255, so bits 8..15 are the flags P
+        const int j = (d & 7) >> 1; // pair within the mask word
+        if ((d & 1) == 0) pr[j] = __builtin_amdgcn_udot4(y, 0x08040201u, 255u, false);
+        else pr[j] = __builtin_amdgcn_udot4(y, 0x80402010u, pr[j], false);
+        // a word's pairs go in with two v_perm_b32 (byte 1 of each) and an OR -- the compiler's instructions: on gfx950 a VALU
+        // instruction may read a v_dot4 result only three wait states after it, which the hazard recognizer cannot arrange for an
+        // instruction hidden in inline asm (measured: wrong flags)
+        if (d == 35) fmk[4] |= __builtin_amdgcn_perm(pr[1], pr[0], 0x0C0C0501u);
+        else if ((d & 7) == 7)
+            fmk[d >> 3] |= __builtin_amdgcn_perm(pr[1], pr[0], 0x0C0C0501u) | __builtin_amdgcn_perm(pr[3], pr[2], 0x05010C0Cu);
     }
     if (partial) { // only the stream's last tile: bytes past the end are no run heads
 #pragma unroll
@@ -717,7 +712,7 @@ __device__ __forceinline__ uint32_t hpc_compact(uint8_t *D, WL &S, const uint8_t
     // 4. pass 2 (round 5): eight raw bytes (two dwords) per step.  Their flag BYTE indexes sel8 -- whose entry, the positions of the byte's set bits in
     //    order with 0x0C behind them, is at the same time the pair of v_perm_b32 selectors that packs the run heads of the eight bytes to the low end of
     //    a 64-bit value.  Shifted to the lane's fill level that value spans up to three dwords of the (zeroed) buffer, all at ALIGNED addresses:
-    //    18 steps of 14 vector + 3 LDS instructions per lane instead of 144 byte stores whose data-dependent slots collided in the banks (a byte
+    //    18 steps of 14 vector + 3 LDS instructions per lane (10 + 3 in dense tiles since, see below) instead of 144 byte stores whose data-dependent slots collided in the banks (a byte
     //    store cost 5.5 units of a plain vector instruction's 1.0 where it ran, 3.1 without the conflicts: profiles/r05_instruction_costs.txt; one
     //    dword per step through a 16-entry table, this round's first version: 22 + 4 per eight bytes, profiles/r05_ab_pass2_pairs.txt).  The dwords two
     //    lanes share (a lane's run heads begin and end at any byte) are merged in one of two ways:
@@ -743,6 +738,38 @@ __device__ __forceinline__ uint32_t hpc_compact(uint8_t *D, WL &S, const uint8_t
             uint32_t fm[5] = {fmk_[0], fmk_[1], fmk_[2], fmk_[3], fmk_[4]};
 #pragma unroll
             for (int g = 0; g < 5; g++) asm volatile("" : "+v"(fm[g]));
+            if constexpr (!SPARSE) {
+                // DENSE, byte-addressed: qa = LDS address of the last slot filled so far (slot -1 of the lane's range at first; D - 1 for lane 0, in
+                // the scratch bytes in front of the tile).  The window of a step spans the dwords at qa & ~3 and the two after it, the first run head at
+                // byte (qa + 1) & 3 of the first: each is one v_alignbyte_b32 by 3 - (qa & 3) = ~qa (the instruction reads 2 bits of it) -- 0 when
+                // qa ends a dword, which moves the heads to the second dword.  The third dword is non-zero only if the step ends in it, and then it is
+                // the next step's first: carried, and OR-ed in there.  10 vector instructions per step (the 64-bit window shifted by 8 (base & 3),
+                // with the fill level and the address updated apart: 14).
+                uint32_t qa = (uint32_t)(uintptr_t)(lds_u8 *)D + base - 1u, carry = 0;
+#pragma unroll
+                for (int q0 = 0; q0 < 18; q0 += 9) {
+                    unsigned long long e[9];
+                    uint32_t ix[9];
+#pragma unroll
+                    for (int qq = 0; qq < 9; qq++) {
+                        ix[qq] = byte_x8_sel(fm[(q0 + qq) >> 2], (q0 + qq) & 3); // 8 x the flag byte of raw bytes 8 q .. 8 q + 7 (one SDWA instruction)
+                        e[qq] = *reinterpret_cast<lds_cu64>((uint32_t)SEL8_OFF + ix[qq]);
+                    }
+#pragma unroll
+                    for (int qq = 0; qq < 9; qq++) {
+                        const int q = q0 + qq;
+                        const uint32_t plo = __builtin_amdgcn_perm(c[2 * q + 1], c[2 * q], (uint32_t)e[qq]);         // run heads 1-4 of the eight bytes
+                        const uint32_t phi = __builtin_amdgcn_perm(c[2 * q + 1], c[2 * q], (uint32_t)(e[qq] >> 32)); // ... 5-8 (selector 0x0C: a zero byte)
+                        const uint32_t sh = ~qa, waddr = qa & ~3u;
+                        const uint32_t w0 = __builtin_amdgcn_alignbyte(plo, 0u, sh) | carry, w1 = __builtin_amdgcn_alignbyte(phi, plo, sh);
+                        carry = __builtin_amdgcn_alignbyte(0u, phi, sh);
+                        asm volatile("ds_or_b32 %0, %1\n\tds_or_b32 %0, %2 offset:4" ::"v"(waddr), "v"(w0), "v"(w1) : "memory");
+                        qa += (uint32_t)__popc(ix[qq]);
+                    }
+                }
+                asm volatile("ds_or_b32 %0, %1" ::"v"(qa & ~3u), "v"(carry) : "memory");
+                return;
+            }
             uint32_t waddr = (uint32_t)(uintptr_t)(lds_u8 *)D + (base & ~3u); // aligned LDS address of the dword being filled
             uint32_t fill8 = 8u * (base & 3u), lo = 0;                        // bits of it that lie before this lane's next run head; this lane's share of them
             // (sparse tiles: a dump slot of two dwords, so that "offset:4" works on it as on the buffer; lanes i and i + 32 share one -- nobody reads it)
@@ -767,14 +794,9 @@ __device__ __forceinline__ uint32_t hpc_compact(uint8_t *D, WL &S, const uint8_t
                     const uint32_t w0 = lo | (uint32_t)win, w1 = (uint32_t)(win >> 32);
                     const uint32_t w2 = (phi >> 8) >> (24u - fill8);           // bits 64 .. of the window: phi >> (32 - fill8), and 0 for fill8 = 0
                     const uint32_t nb = fill8 + 8u * (uint32_t)__popc(ix[qq]); // <= 88
-                    if constexpr (!SPARSE) {
-                        asm volatile("ds_or_b32 %0, %1\n\tds_or_b32 %0, %2 offset:4" ::"v"(waddr), "v"(w0), "v"(w1) : "memory");
-                        lo = w2; // (the first two dwords are in place; only what lies beyond them is carried)
-                    } else {
-                        const uint32_t a0 = nb >= 32u ? waddr : dump, a1 = nb >= 64u ? waddr : dump;
-                        asm volatile("ds_write_b32 %0, %2\n\tds_write_b32 %1, %3 offset:4" ::"v"(a0), "v"(a1), "v"(w0), "v"(w1) : "memory");
-                        lo = nb >= 64u ? w2 : (nb >= 32u ? w1 : w0);
-                    }
+                    const uint32_t a0 = nb >= 32u ? waddr : dump, a1 = nb >= 64u ? waddr : dump;
+                    asm volatile("ds_write_b32 %0, %2\n\tds_write_b32 %1, %3 offset:4" ::"v"(a0), "v"(a1), "v"(w0), "v"(w1) : "memory");
+                    lo = nb >= 64u ? w2 : (nb >= 32u ? w1 : w0);
                     waddr += (nb >> 3) & 0xCu; // 4 x (dwords completed: 0, 1 or 2)
                     fill8 = nb & 24u;
                 }
