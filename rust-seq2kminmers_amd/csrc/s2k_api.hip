@@ -1529,6 +1529,7 @@ s2k_status s2k_hpc_device_ex(s2k_ctx *ctx, const uint8_t *d_bases, const uint64_
             if (n_runs) *n_runs = total1;
             return total1 > capacity && (d_hpc || d_pos) ? S2K_ERR_CAPACITY : S2K_OK;
         }
+        if (ctx->trace) fprintf(stderr, "[s2k] re-run: a single-pass hpc look-back gave up -> two-pass hpc\n");
     }
     if (seg_path) {
         S2K_TRY(launch_read_run_counts(d_bases, d_read_off, n_reads, n_bases, blk_cnt, blk_off, blk_tmp, cnt, read_c0, ctx->stream, rle),
