@@ -42,6 +42,7 @@ extern "C" {
  * added the same way: added entry points and one opaque type, the version stays 2.)
  * (The opaque s2k_table with s2k_table_create / _destroy / _lookup / _filter and the struct s2k_solid_out were added the same way:
  * added entry points, one opaque type and one new struct; no existing entry point or struct changed, the version stays 2.)
+ * (s2k_table_edges and s2k_graph_adjacency were added the same way: added entry points, the version stays 2.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -290,6 +291,29 @@ typedef struct s2k_solid_out {
  * s2k_count_device_ex): about 4.2 B per input item.  Runs on the context's stream; returns when the outputs are written. */
 s2k_status s2k_table_filter(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t min_count, const s2k_solid_out *out,
                             uint64_t *n_kept);
+/* The edges of the minimizer-space de Bruijn graph (rust-mdbg's graph) that the reads of `in` traverse (km_off, hash and rev required,
+ * km_off[0] == 0).  Node i is key i of the table (ids are stable while the table lives); the oriented node u = 2 * i + o.  Item j of
+ * a read is the oriented node 2 * index(hash[j]) + rev[j]; items j and j + 1 form an adjacency when they belong to the same read and
+ * both hashes are in the table with a count of at least min_count (0 and 1 both mean "present"): a non-solid item between two solid
+ * ones breaks the chain.  An adjacency gives the edge e = (u, v), key(e) = u << 32 | v, and its twin (v ^ 1, u ^ 1), the same
+ * adjacency read on the other strand; it emits key(e) and then key(twin(e)) unless twin(e) == e (a hairpin, v == u ^ 1: one key).
+ * A loop u -> u has a distinct twin.  Keys come in item order, bit-identical from call to call.  Counting them
+ * (s2k_count_device_ex, an s2k_counter over batches) gives the edge multiplicities, count(e) == count(twin(e)).  *n_edges is always
+ * set; the keys are written only when *n_edges <= capacity, otherwise S2K_ERR_CAPACITY and nothing is written; d_edge_keys NULL asks
+ * for the size only.  A table of 2^31 keys or more is refused (S2K_ERR_INVALID_ARG: oriented ids are 32-bit).  Uses the context's
+ * grow-only count workspace (shared with s2k_count_device_ex): about 4.2 B per input item.  Runs on the context's stream; returns
+ * when the keys are written. */
+s2k_status s2k_table_edges(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t min_count, uint64_t *d_edge_keys,
+                           uint64_t capacity, uint64_t *n_edges);
+/* The adjacency (CSR) of a graph over the 2 * n_nodes oriented nodes from its edge keys d_edge_keys[0..n_edges), strictly ascending
+ * (unsigned 64-bit, what s2k_count_device_ex(S2K_COUNT_SORTED) and s2k_counter_finish write) with both node ids u = key >> 32 and
+ * v = key & 0xFFFFFFFF below 2 * n_nodes.  d_row_off[u] (2 * n_nodes + 1 entries) = the first edge index whose source is >= u, so
+ * row_off[2 * n_nodes] == n_edges and the out-edges of u are [row_off[u], row_off[u + 1]); d_dst[i] = the low 32 bits of key i (may
+ * be NULL).  An input that breaks the rules is detected on the device: S2K_ERR_INVALID_ARG and nothing written.  Symmetry (every
+ * edge's twin present) is not checked.  n_nodes >= 2^31 is refused (S2K_ERR_INVALID_ARG).  Runs on the context's stream; returns when
+ * the arrays are written. */
+s2k_status s2k_graph_adjacency(s2k_ctx *ctx, const uint64_t *d_edge_keys, uint64_t n_edges, uint64_t n_nodes, uint64_t *d_row_off,
+                               uint32_t *d_dst);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

@@ -135,6 +135,12 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return tot;
     }
+    // s2k_graph_adjacency: the CSR over 2 * n_nodes oriented nodes from strictly ascending edge keys (u << 32 | v); d_row_off holds
+    // 2 * n_nodes + 1 entries, d_dst (may be nullptr) n_edges.  Throws Error(S2K_ERR_INVALID_ARG) for keys that break the rules.
+    void graph_adjacency(const uint64_t *d_edge_keys, uint64_t n_edges, uint64_t n_nodes, uint64_t *d_row_off, uint32_t *d_dst = nullptr) {
+        s2k_status st = s2k_graph_adjacency(ctx_, d_edge_keys, n_edges, n_nodes, d_row_off, d_dst);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:
@@ -171,7 +177,9 @@ class Counter {
 
 // Look-ups against a count table (s2k_table_*): the table borrows d_keys / d_counts (d_counts may be nullptr: membership), which must
 // stay valid and unchanged while it lives.  lookup() writes each query's count (0 if absent); filter() keeps each read's k-min-mers
-// whose count is at least min_count and returns how many were kept (throws on S2K_ERR_CAPACITY too).  Destroy it before its Engine.
+// whose count is at least min_count and returns how many were kept (throws on S2K_ERR_CAPACITY too); edges() writes the graph edge
+// keys of the reads (s2k_table_edges; d_edge_keys nullptr: size only) and returns how many there are (throws on S2K_ERR_CAPACITY too).
+// Destroy it before its Engine.
 class Table {
   public:
     Table(Engine &eng, const uint64_t *d_keys, const uint32_t *d_counts, uint64_t n) : eng_(&eng) {
@@ -187,6 +195,11 @@ class Table {
         uint64_t n_kept = 0;
         check(s2k_table_filter(t_, n_reads, &in, min_count, &out, &n_kept));
         return n_kept;
+    }
+    uint64_t edges(uint64_t n_reads, const s2k_device_out &in, uint32_t min_count, uint64_t *d_edge_keys = nullptr, uint64_t capacity = 0) {
+        uint64_t n_edges = 0;
+        check(s2k_table_edges(t_, n_reads, &in, min_count, d_edge_keys, capacity, &n_edges));
+        return n_edges;
     }
     s2k_table *raw() { return t_; }
 

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "s2k_last_error", "s2k_hash_bound", "s2k_extract", "s2k_result_free", "s2k_extract_device", "s2k_sync",
     "s2k_hpc_device", "s2k_hpc_device_ex", "s2k_count_device", "s2k_count_device_ex", "s2k_partition_device", "s2k_synth_bases_device", "s2k_synth_hifi_lengths", "s2k_synth_hifi_device", "s2k_last_kernel_ms", "s2k_enable_timing", "s2k_timing_total", "s2k_fastx_open", "s2k_fastx_next", "s2k_fastx_close", "s2k_run_file", "s2k_fastx_parse_device",
     "s2k_count_merge_device", "s2k_counter_create", "s2k_counter_destroy", "s2k_counter_add", "s2k_counter_finish", "s2k_run_file_count",
-    "s2k_table_create", "s2k_table_destroy", "s2k_table_lookup", "s2k_table_filter",
+    "s2k_table_create", "s2k_table_destroy", "s2k_table_lookup", "s2k_table_filter", "s2k_table_edges", "s2k_graph_adjacency",
 ]
 
 
@@ -153,6 +153,8 @@ def load_library(path=None):
     L.s2k_table_destroy.argtypes = [C.c_void_p]
     L.s2k_table_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.s2k_table_filter.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.POINTER(SolidOut), C.POINTER(C.c_uint64)]
+    L.s2k_table_edges.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.s2k_graph_adjacency.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -409,6 +411,23 @@ class Engine:
             if own:
                 ctr.close()
 
+    def graph_adjacency(self, edge_keys, n_nodes):
+        """The CSR of a graph over 2 * n_nodes oriented nodes (s2k_graph_adjacency) from its edge keys (1-D 64-bit GPU tensor, strictly
+        ascending as uint64, both node ids below 2 * n_nodes; S2kError(1) otherwise) -> (row_off, dst): int64 tensor of 2 * n_nodes + 1
+        row offsets and int32 tensor of the destination of every edge, on the device."""
+        import torch
+
+        if edge_keys.dim() != 1 or edge_keys.element_size() != 8 or not edge_keys.is_cuda:
+            raise ValueError("graph_adjacency wants a 1-D 64-bit tensor on the GPU")
+        edge_keys = edge_keys.contiguous()
+        n, dev = edge_keys.numel(), edge_keys.device
+        row_off = torch.empty(2 * int(n_nodes) + 1, dtype=torch.int64, device=dev)
+        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_graph_adjacency(self.ctx, C.c_void_p(edge_keys.data_ptr() if n else 0), n, int(n_nodes),
+                                                 C.c_void_p(row_off.data_ptr()), C.c_void_p(dst.data_ptr())))
+        return row_off, dst[:n]
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -552,6 +571,95 @@ class CountTable:
         out = {f: (t if f == "km_off" else t[:n]) for f, t in res.items()}
         out["n"] = n
         return out
+
+    def edges(self, out_tensors, n_reads, min_count=2):
+        """The graph edges that the reads traverse (s2k_table_edges): out_tensors = the GPU tensors extract_device wrote (dict with
+        km_off, hash and rev).  Node i is key i of this table, oriented node 2 * i + rev.  -> int64 tensor of the edge keys
+        (u << 32 | v as uint64 bits) in emission order: each adjacency of two solid consecutive items of a read, then its twin
+        ((v ^ 1) << 32 | u ^ 1) unless it is its own."""
+        import torch
+
+        dev = out_tensors["km_off"].device
+        n_items = int(out_tensors["km_off"][n_reads].item()) if n_reads else 0
+        cap = 2 * n_items  # at most two keys per item
+        keys = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        i = DeviceOut()
+        i.km_capacity = n_items
+        i.km_off, i.hash, i.rev = (out_tensors[f].data_ptr() for f in ("km_off", "hash", "rev"))
+        ne = C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self.engine._check(self.lib.s2k_table_edges(self.handle, n_reads, C.byref(i), int(min_count), C.c_void_p(keys.data_ptr()), cap,
+                                                    C.byref(ne)))
+        return keys[:int(ne.value)]
+
+
+class KminmerGraph:
+    """The minimizer-space de Bruijn graph of a read set, built on the device in two passes over its extraction outputs (dicts of the
+    GPU tensors extract_device wrote: km_off, hash, rev; n_reads = len(km_off) - 1): pass 1 counts the k-min-mers (KminmerCounter) and
+    keeps those seen at least min_count times as the nodes; pass 2 emits every batch's edges (CountTable.edges) into a second counter,
+    keeps the edges seen at least min_edge_count times and builds their adjacency (Engine.graph_adjacency).  Node i is k-min-mer
+    keys[i] (count counts[i]); oriented node u = 2 * i + o; edge i goes from u = edge_keys[i] >> 32 (as uint64) to v = dst[i] and was
+    seen edge_counts[i] times; the out-edges of u are row_off[u] .. row_off[u + 1].  Every edge's twin (v ^ 1, u ^ 1) is present with
+    the same count."""
+
+    def __init__(self, keys, counts, edge_keys, edge_counts, row_off, dst):
+        self.keys, self.counts, self.edge_keys, self.edge_counts, self.row_off, self.dst = keys, counts, edge_keys, edge_counts, row_off, dst
+
+    @property
+    def n_nodes(self):
+        return self.keys.numel()
+
+    @property
+    def n_edges(self):
+        return self.edge_keys.numel()
+
+    @classmethod
+    def build(cls, engine, outs, min_count=2, min_edge_count=1):
+        nodes = KminmerCounter(engine)
+        try:
+            for o in outs:
+                n = int(o["km_off"][-1].item())
+                nodes.add_tensor(o["hash"][:n])
+            keys, counts = nodes.finish(min_count)
+        finally:
+            nodes.close()
+        table = CountTable(engine, keys, counts)
+        edges = KminmerCounter(engine)
+        try:
+            for o in outs:
+                edges.add_tensor(table.edges(o, o["km_off"].numel() - 1, min_count))
+            edge_keys, edge_counts = edges.finish(min_edge_count)
+        finally:
+            edges.close()
+            table.close()
+        row_off, dst = engine.graph_adjacency(edge_keys, keys.numel())
+        return cls(keys, counts, edge_keys, edge_counts, row_off, dst)
+
+    def write_gfa(self, path):
+        """GFA 1: an S line per node (name = node index, sequence *, KC:i: its count, kh:Z: its hash in 16 hex digits) and an L line per
+        twin pair, written once, for the edge whose key is not above its twin's (orientation 0 -> +, 1 -> -, overlap *, RC:i: its
+        count)."""
+        keys = self.keys.cpu().numpy().view(np.uint64)
+        counts = self.counts.cpu().numpy().view(np.uint32)
+        ek = self.edge_keys.cpu().numpy().view(np.uint64)
+        ec = self.edge_counts.cpu().numpy().view(np.uint32)
+        write_gfa(path, keys, counts, ek, ec)
+
+
+def write_gfa(path, keys, counts, edge_keys, edge_counts):
+    """KminmerGraph.write_gfa on host arrays: node keys / counts (uint64 / uint32) and edge keys / counts (uint64 / uint32)."""
+    keys, counts = np.asarray(keys, dtype=np.uint64), np.asarray(counts, dtype=np.uint32)
+    ek, ec = np.asarray(edge_keys, dtype=np.uint64), np.asarray(edge_counts, dtype=np.uint32)
+    u, v = ek >> np.uint64(32), ek & np.uint64(0xFFFFFFFF)
+    twin = ((v ^ np.uint64(1)) << np.uint64(32)) | (u ^ np.uint64(1))
+    sel = ek <= twin
+    sign = np.array(["+", "-"])
+    with open(path, "w") as f:
+        f.write("H\tVN:Z:1.0\n")
+        f.writelines("S\t%d\t*\tKC:i:%d\tkh:Z:%016x\n" % (i, c, h) for i, (h, c) in enumerate(zip(keys.tolist(), counts.tolist())))
+        su, sv = u[sel], v[sel]
+        f.writelines("L\t%d\t%s\t%d\t%s\t*\tRC:i:%d\n" % (a >> 1, sign[a & 1], b >> 1, sign[b & 1], c)
+                     for a, b, c in zip(su.tolist(), sv.tolist(), ec[sel].tolist()))
 
 
 class FastxReader:

@@ -20,6 +20,14 @@
 //  4. filter_write_kernel (only when item outputs are wanted and fit): each kept item goes to LDS at its tile-relative slot, one
 //     output array at a time, and leaves the workgroup as one contiguous, coalesced run.  offset = item index - its read's first
 //     item, the read found by a binary search of km_off narrowed to the reads that overlap the tile.
+//
+// Edges (s2k_table_edges), the same compaction with 0, 1 or 2 keys per item:
+//  1. edges_count_kernel: the look-up fused in, returning each item's rank too; per item its oriented node (4 B of workspace), per
+//     64 items the mask of items that start an adjacency and the keys before that word inside the tile; per tile the key total.  The
+//     next tile's first item (the halo) is looked up once more by lane 0; read starts come from km_off, as in the filter.
+//  2. launch_scan_u32 over the tile totals.
+//  3. edges_write_kernel (only when keys are wanted and fit): each adjacency's key and its twin's to LDS at tile-relative slots; the
+//     tile's keys leave as one contiguous run.
 #include <algorithm>
 #include <cstdlib>
 #include <new>
@@ -46,11 +54,16 @@ struct TableView {
     uint32_t shift;         // 64 - bits
 };
 
-// c[r] = count of q[r] in the table (0 if absent)
-__device__ inline void lookup_many(const TableView &tv, const uint64_t (&q)[TB_Q], uint32_t (&c)[TB_Q]) {
+// c[r] = count of q[r] in the table (0 if absent); with POS also rank[r] = its index in the table (0 if absent).  The look-up and
+// the filter use POS = false, the instantiation that compiles to the code they had before the ranks existed.
+template <bool POS>
+__device__ inline void lookup_many(const TableView &tv, const uint64_t (&q)[TB_Q], uint32_t (&c)[TB_Q], uint32_t *rank) {
     if (tv.n == 0) {
 #pragma unroll
-        for (int r = 0; r < TB_Q; r++) c[r] = 0;
+        for (int r = 0; r < TB_Q; r++) {
+            c[r] = 0;
+            if (POS) rank[r] = 0;
+        }
         return;
     }
     uint32_t lo[TB_Q], hi[TB_Q], pos[TB_Q];
@@ -92,6 +105,29 @@ __device__ inline void lookup_many(const TableView &tv, const uint64_t (&q)[TB_Q
     }
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) c[r] = hit[r] ? (tv.counts ? tv.counts[pos[r]] : 1u) : 0u;
+    if (POS) {
+#pragma unroll
+        for (int r = 0; r < TB_Q; r++) rank[r] = pos[r];
+    }
+}
+
+// one query (the edge kernel's halo item): *c its count, *pos its index (both 0 if absent)
+__device__ inline void lookup_one(const TableView &tv, uint64_t q, uint32_t *c, uint32_t *pos) {
+    *c = *pos = 0;
+    if (tv.n == 0) return;
+    const uint64_t p = q >> tv.shift;
+    uint32_t lo = tv.dir[p], hi = tv.dir[p + 1];
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const uint64_t k = tv.keys[mid];
+        if (k < q) lo = mid + 1;
+        else if (k > q) hi = mid;
+        else {
+            *c = tv.counts ? tv.counts[mid] : 1u;
+            *pos = mid;
+            return;
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void table_index_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint32_t shift, uint32_t bits,
@@ -120,7 +156,7 @@ __global__ __launch_bounds__(TB_THREADS) void table_lookup_kernel(TableView tv, 
     uint32_t c[TB_Q];
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) q[r] = query[std::min<uint64_t>(base + (uint64_t)r * TB_THREADS, n - 1)];
-    lookup_many(tv, q, c);
+    lookup_many<false>(tv, q, c, nullptr);
 #pragma unroll
     for (int r = 0; r < TB_Q; r++)
         if (base + (uint64_t)r * TB_THREADS < n) out[base + (uint64_t)r * TB_THREADS] = c[r];
@@ -143,7 +179,7 @@ __global__ __launch_bounds__(TB_THREADS) void filter_count_kernel(TableView tv, 
     uint32_t c[TB_Q];
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) q[r] = hash[std::min<uint64_t>(t0 + (uint64_t)r * TB_THREADS + tid, n_items - 1)];
-    lookup_many(tv, q, c);
+    lookup_many<false>(tv, q, c, nullptr);
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) {
         const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
@@ -271,6 +307,131 @@ __global__ __launch_bounds__(TB_THREADS) void filter_write_kernel(FilterIo io, u
     }
 #undef TB_STAGE
 #undef TB_LEAVE
+}
+
+// ---- graph edges (s2k_table_edges): the same compaction, 0, 1 or 2 keys per item ----------------------------------
+constexpr uint32_t TB_NONE = 0xFFFFFFFFu; // an item that is not solid (oriented ids stay below 2^32 - 2: the table has < 2^31 keys)
+
+struct EdgeWs {
+    uint32_t *node;      // per item: its oriented node 2 * rank + rev, TB_NONE when it is not solid
+    uint64_t *wadj;      // per 64 items: the items j for which (j, j + 1) is an adjacency
+    uint32_t *wpre;      // per 64 items: keys emitted before the word inside its tile
+    uint32_t *tile_keys; // per tile
+    uint64_t *tile_off;  // n_tiles + 1
+};
+
+// the first r in [0, n_reads] with km_off[r] > x (n_reads + 1 if there is none)
+__device__ inline uint64_t reads_upto(const uint64_t *__restrict__ km_off, uint64_t n_reads, uint64_t x) {
+    uint64_t lo = 0, hi = n_reads + 1;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (km_off[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Items j and j + 1 form an adjacency when both are solid and j + 1 starts no read.  The tile's items and one halo item (the next
+// tile's first, looked up by lane 0) go to LDS as oriented nodes; the read starts inside (t0, t0 + TB_TILE] are marked from the reads
+// that a binary search of km_off finds there (an empty read marks the same item as the read after it).
+__global__ __launch_bounds__(TB_THREADS) void edges_count_kernel(TableView tv, const uint64_t *__restrict__ km_off, uint64_t n_reads,
+                                                                 const uint64_t *__restrict__ hash, const uint8_t *__restrict__ rev,
+                                                                 uint64_t n_items, uint32_t minc, EdgeWs ws) {
+    __shared__ uint32_t snode[TB_TILE + 1];
+    __shared__ uint8_t sstart[TB_TILE + 1]; // sstart[x]: item t0 + x starts a read
+    __shared__ uint32_t wc[TB_WORDS];
+    __shared__ uint64_t sreads[2];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
+    uint64_t q[TB_Q];
+    uint32_t c[TB_Q], pos[TB_Q];
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) q[r] = hash[std::min<uint64_t>(t0 + (uint64_t)r * TB_THREADS + tid, n_items - 1)];
+    if (tid < 2) sreads[tid] = reads_upto(km_off, n_reads, t0 + (tid ? TB_TILE : 0));
+    lookup_many<true>(tv, q, c, pos);
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) {
+        const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
+        uint32_t u = TB_NONE;
+        if (j < n_items) {
+            if (c[r] >= minc) u = 2u * pos[r] + rev[j];
+            ws.node[j] = u;
+        }
+        snode[r * TB_THREADS + tid] = u;
+        sstart[r * TB_THREADS + tid] = 0;
+    }
+    if (tid == 0) {
+        const uint64_t j = t0 + TB_TILE;
+        uint32_t u = TB_NONE;
+        if (j < n_items) {
+            uint32_t hc, hp;
+            lookup_one(tv, hash[j], &hc, &hp);
+            if (hc >= minc) u = 2u * hp + rev[j];
+        }
+        snode[TB_TILE] = u;
+        sstart[TB_TILE] = 0;
+    }
+    __syncthreads();
+    for (uint64_t r = sreads[0] + tid; r < sreads[1]; r += TB_THREADS) {
+        const uint64_t x = km_off[r] - t0; // in [1, TB_TILE] for a non-decreasing km_off; a table that is not one writes no LDS outside
+        if (x <= TB_TILE) sstart[x] = 1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) {
+        const int x = r * TB_THREADS + tid;
+        const uint64_t j = t0 + x;
+        const uint32_t u = snode[x], v = snode[x + 1];
+        const bool adj = j + 1 < n_items && !sstart[x + 1] && u != TB_NONE && v != TB_NONE;
+        const uint64_t m1 = __ballot(adj), m2 = __ballot(adj && v != (u ^ 1u)); // a hairpin (v == u ^ 1) is its own twin: one key
+        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
+        if (lane == 0) {
+            wc[r * 4 + wv] = (uint32_t)(__popcll(m1) + __popcll(m2));
+            if (w0 < n_items) ws.wadj[w0 >> 6] = m1;
+        }
+    }
+    __syncthreads();
+    if (tid < TB_WORDS) {
+        uint32_t pre = 0;
+        for (int x = 0; x < tid; x++) pre += wc[x];
+        const uint64_t w0 = t0 + (uint64_t)tid * 64;
+        if (w0 < n_items) ws.wpre[w0 >> 6] = pre;
+        if (tid == TB_WORDS - 1) ws.tile_keys[blockIdx.x] = pre + wc[tid];
+    }
+}
+
+// each adjacency's key (u << 32 | v), then its twin's ((v ^ 1) << 32 | u ^ 1) unless it is its own, staged in LDS at tile-relative
+// slots; the tile's keys leave as one contiguous run
+__global__ __launch_bounds__(TB_THREADS) void edges_write_kernel(uint64_t n_items, EdgeWs ws, uint64_t *__restrict__ out, uint64_t capacity) {
+    __shared__ uint64_t skey[2 * TB_TILE];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
+    const uint64_t base = ws.tile_off[blockIdx.x], tot = ws.tile_off[blockIdx.x + 1] - base;
+    if (tot == 0) return;
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) {
+        const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
+        const uint64_t w = (t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64) >> 6;
+        const bool adj = j < n_items && ((ws.wadj[w] >> lane) & 1ull); // j + 1 < n_items whenever the bit is set
+        uint32_t u = 0, v = 0;
+        if (adj) {
+            u = ws.node[j];
+            v = ws.node[j + 1];
+        }
+        const bool two = adj && v != (u ^ 1u);
+        const uint64_t below = (1ull << lane) - 1ull;
+        const uint64_t m1 = __ballot(adj), m2 = __ballot(two);
+        if (adj) {
+            const uint32_t slot = ws.wpre[w] + (uint32_t)(__popcll(m1 & below) + __popcll(m2 & below));
+            skey[slot] = ((uint64_t)u << 32) | v;
+            if (two) skey[slot + 1] = ((uint64_t)(v ^ 1u) << 32) | (u ^ 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < tot; i += TB_THREADS) {
+        if (base + i >= capacity) break; // the host checked n_edges <= capacity
+        out[base + i] = skey[i];
+    }
 }
 
 size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -460,6 +621,74 @@ s2k_status s2k_table_filter(s2k_table *t, uint64_t n_reads, const s2k_device_out
     if (e == hipSuccess) e = ctx_sync(ctx);
     if (e != hipSuccess) {
         ctx_set_error(ctx, "s2k_table_filter: HIP error");
+        return S2K_ERR_DEVICE;
+    }
+    return S2K_OK;
+}
+
+s2k_status s2k_table_edges(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t min_count, uint64_t *d_edge_keys,
+                           uint64_t capacity, uint64_t *n_edges) {
+    if (n_edges) *n_edges = 0;
+    if (!t || !in || !n_edges || !in->km_off || !in->hash || !in->rev) return S2K_ERR_INVALID_ARG;
+    s2k_ctx *ctx = t->ctx;
+    if (t->n >= (1ull << 31)) {
+        ctx_set_error(ctx, "s2k_table_edges: 2^31 keys or more (oriented node ids are 32-bit)");
+        return S2K_ERR_INVALID_ARG;
+    }
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
+    hipStream_t st = ctx_stream(ctx);
+    uint64_t ends[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(&ends[0], in->km_off, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&ends[1], in->km_off + n_reads, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = ctx_sync(ctx);
+    if (e != hipSuccess) {
+        ctx_set_error(ctx, "s2k_table_edges: HIP error");
+        return S2K_ERR_DEVICE;
+    }
+    if (ends[0] != 0 || ends[1] < ends[0]) {
+        ctx_set_error(ctx, "s2k_table_edges: in->km_off must start at 0 and end at or after its start");
+        return S2K_ERR_INVALID_ARG;
+    }
+    const uint64_t n_items = ends[1];
+    if (n_items == 0) return S2K_OK;
+    const uint64_t nt = (n_items + TB_TILE - 1) / TB_TILE, nw = (n_items + 63) / 64;
+    if (nt >= (1ull << 32)) {
+        ctx_set_error(ctx, "s2k_table_edges: too many items for one call");
+        return S2K_ERR_INVALID_ARG;
+    }
+    size_t off = 0;
+    const size_t oN = off; off += al(n_items * 4);
+    const size_t oA = off; off += al(nw * 8);
+    const size_t oP = off; off += al(nw * 4);
+    const size_t oK = off; off += al(nt * 4);
+    const size_t oO = off; off += al((nt + 1) * 8);
+    const size_t oT = off; off += al(scan_tmp_bytes(nt));
+    char *w = (char *)ctx_count_table(ctx, off);
+    if (!w) {
+        ctx_set_error(ctx, "s2k_table_edges: workspace allocation");
+        return S2K_ERR_NOMEM;
+    }
+    EdgeWs ws{(uint32_t *)(w + oN), (uint64_t *)(w + oA), (uint32_t *)(w + oP), (uint32_t *)(w + oK), (uint64_t *)(w + oO)};
+    const uint32_t minc = min_count ? min_count : 1u;
+    hipLaunchKernelGGL(edges_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, t->view(), in->km_off, n_reads, in->hash, in->rev,
+                       n_items, minc, ws);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = launch_scan_u32(ws.tile_keys, nt, ws.tile_off, (uint64_t *)(w + oT), 0, st);
+    uint64_t total = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, ws.tile_off + nt, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = ctx_sync(ctx);
+    if (e != hipSuccess) {
+        ctx_set_error(ctx, "s2k_table_edges: HIP error");
+        return S2K_ERR_DEVICE;
+    }
+    *n_edges = total;
+    if (!d_edge_keys || total == 0) return S2K_OK;
+    if (total > capacity) return S2K_ERR_CAPACITY;
+    hipLaunchKernelGGL(edges_write_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, n_items, ws, d_edge_keys, capacity);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = ctx_sync(ctx);
+    if (e != hipSuccess) {
+        ctx_set_error(ctx, "s2k_table_edges: HIP error");
         return S2K_ERR_DEVICE;
     }
     return S2K_OK;
