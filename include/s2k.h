@@ -43,6 +43,8 @@ extern "C" {
  * (The opaque s2k_table with s2k_table_create / _destroy / _lookup / _filter and the struct s2k_solid_out were added the same way:
  * added entry points, one opaque type and one new struct; no existing entry point or struct changed, the version stays 2.)
  * (s2k_table_edges and s2k_graph_adjacency were added the same way: added entry points, the version stays 2.)
+ * (s2k_graph_unitigs, s2k_graph_unitig_edges, s2k_graph_unitigs_last_steps and the struct s2k_unitig_out were added the same way:
+ * added entry points and one new struct, the version stays 2.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -314,6 +316,53 @@ s2k_status s2k_table_edges(s2k_table *t, uint64_t n_reads, const s2k_device_out 
  * the arrays are written. */
 s2k_status s2k_graph_adjacency(s2k_ctx *ctx, const uint64_t *d_edge_keys, uint64_t n_edges, uint64_t n_nodes, uint64_t *d_row_off,
                                uint32_t *d_dst);
+/* ---- unitigs: the non-branching paths of the graph compacted ----------------------------------------------
+ * Input of both calls: the CSR that s2k_graph_adjacency writes, d_row_off (2 * n_nodes + 1) and d_dst (n_edges; may be NULL when
+ * n_edges == 0).  Oriented node u = 2 i + o, twin(u) = u ^ 1, twin of the edge (u, v) = (v ^ 1, u ^ 1), out(u) = row_off[u + 1] -
+ * row_off[u].
+ * Accepted input: row_off[0] == 0, non-decreasing, row_off[2 n_nodes] == n_edges; every row strictly ascending with ids below
+ * 2 n_nodes; and twin-symmetric: for every edge (u, v) the row of v ^ 1 holds u ^ 1 (so in-degree(v) == out(v ^ 1) and no reverse
+ * graph is needed).  All of it is checked on the device before anything is written: a violation is S2K_ERR_INVALID_ARG.
+ * n_nodes >= 2^31 is refused.
+ * Link: next(u) = v iff out(u) == 1, v is that destination, out(v ^ 1) == 1, v != u (a loop) and v != u ^ 1 (a hairpin).  The rule
+ * is its own twin (next(u) = v <=> next(v ^ 1) = u ^ 1) and next is injective, so the oriented nodes fall into disjoint chains and
+ * cycles, each with a distinct twin that visits the twins in reverse order; none holds both u and u ^ 1.
+ * Unitig: one per twin pair of chains / cycles; every node belongs to exactly one, in one orientation.  Of a chain with head h and
+ * tail t the kept strand is the one with h < (t ^ 1) (a node without links: 2 i).  Of a cycle the kept strand is the one that holds
+ * the smallest oriented id of the two, and it starts there; circular[t] = 1.  Unitigs are numbered by ascending first member of the
+ * kept strand, so the outputs are a function of the input alone, bit-identical from call to call.  Oriented unitig U = 2 t + s: s = 0
+ * the kept strand, s = 1 its twin (members reversed, each ^ 1). */
+typedef struct s2k_unitig_out { /* all device pointers; any may be NULL */
+    uint64_t capacity;          /* unitigs that uni_off / circular can hold (uni_off has capacity + 1 entries) */
+    uint64_t *uni_off;          /* members of unitig t: [uni_off[t], uni_off[t + 1]); uni_off[n_unitigs] == n_nodes */
+    uint32_t *members;          /* n_nodes oriented node ids: the kept strands, in path order */
+    uint32_t *node_unitig;      /* n_nodes: the unitig of node i ... */
+    uint32_t *node_pos;         /* ... and its position on the kept strand */
+    uint8_t *circular;          /* per unitig */
+} s2k_unitig_out;
+/* *n_unitigs and *n_links (oriented nodes with a next: a link and its twin both count) are always set; the arrays are written only
+ * when *n_unitigs <= out->capacity, otherwise S2K_ERR_CAPACITY and nothing is written; out == NULL or all arrays NULL asks for the
+ * sizes only.  n_nodes == 0 and n_edges == 0 are valid (n isolated nodes are n unitigs of length 1).  A row of high degree is slow
+ * (one lane walks it), never wrong.  Uses the context's grow-only count workspace (shared with s2k_count_device_ex): 60 B per node.
+ * Runs on the context's stream; returns when the arrays are written. */
+s2k_status s2k_graph_unitigs(s2k_ctx *ctx, const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_nodes,
+                             const s2k_unitig_out *out, uint64_t *n_unitigs, uint64_t *n_links);
+/* The graph between the oriented unitigs: every edge (u, v) of the CSR that is not a link leaves the last member of an oriented
+ * unitig U and enters the first member of an oriented unitig V, and gives the key U << 32 | V (a loop on a unitig of length 1 gives
+ * U -> U, a hairpin U -> U ^ 1; the closing link of a cycle is a link and gives none), so *n_out == n_edges - n_links.  Keys are
+ * written strictly ascending -- s2k_graph_adjacency(d_keys, *n_out, n_unitigs) accepts them as they are, and its result is again
+ * twin-symmetric -- and d_src_edge[j] (may be NULL) = the index of the CSR edge key j came from.  d_uni_off, d_members,
+ * d_node_unitig and d_node_pos are what s2k_graph_unitigs wrote for the same CSR; neither they nor the CSR are validated again.
+ * *n_out is always set; the arrays are written only when *n_out <= capacity, otherwise S2K_ERR_CAPACITY and nothing is written;
+ * d_keys NULL asks for the size only.  Workspace: 12 B per oriented unitig. */
+s2k_status s2k_graph_unitig_edges(s2k_ctx *ctx, const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_nodes,
+                                  const uint64_t *d_uni_off, const uint32_t *d_members, const uint32_t *d_node_unitig,
+                                  const uint32_t *d_node_pos, uint64_t n_unitigs, uint64_t *d_keys, uint64_t *d_src_edge,
+                                  uint64_t capacity, uint64_t *n_out);
+/* Measurement helper (tools/unitig_rate.py): host-clock ms of the steps of the last s2k_graph_unitigs call of this process, each
+ * of which ends in a host wait -- ms[0] check, ms[1] links + list ranking, ms[2] numbering, ms[3] lengths + scatter -- and the number
+ * of jump rounds it ran (ranking, and for cycles the minimum rounds and the second ranking).  Not for concurrent callers. */
+void s2k_graph_unitigs_last_steps(double *ms, uint32_t *rounds);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

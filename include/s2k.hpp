@@ -141,6 +141,29 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         s2k_status st = s2k_graph_adjacency(ctx_, d_edge_keys, n_edges, n_nodes, d_row_off, d_dst);
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
     }
+    // s2k_graph_unitigs: the non-branching paths of a twin-symmetric CSR compacted; out (may be nullptr: sizes only) names the device
+    // arrays to fill.  Returns the number of unitigs, *n_links (may be nullptr) the number of oriented nodes with a next.  Throws
+    // Error(S2K_ERR_INVALID_ARG) for a CSR that breaks the rules or lacks a twin, Error(S2K_ERR_CAPACITY) when out->capacity is short.
+    uint64_t graph_unitigs(const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_nodes, const s2k_unitig_out *out,
+                           uint64_t *n_links = nullptr) {
+        uint64_t n_unitigs = 0, links = 0;
+        s2k_status st = s2k_graph_unitigs(ctx_, d_row_off, d_dst, n_edges, n_nodes, out, &n_unitigs, &links);
+        if (n_links) *n_links = links;
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_unitigs;
+    }
+    // s2k_graph_unitig_edges: the keys U << 32 | V between the oriented unitigs, strictly ascending, and (d_src_edge, may be nullptr)
+    // the CSR edge each came from; the unitig arrays are those graph_unitigs wrote for the same CSR.  Returns the number of keys
+    // (d_keys nullptr: the size only).
+    uint64_t graph_unitig_edges(const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_nodes, const uint64_t *d_uni_off,
+                                const uint32_t *d_members, const uint32_t *d_node_unitig, const uint32_t *d_node_pos, uint64_t n_unitigs,
+                                uint64_t *d_keys, uint64_t *d_src_edge, uint64_t capacity) {
+        uint64_t n_out = 0;
+        s2k_status st = s2k_graph_unitig_edges(ctx_, d_row_off, d_dst, n_edges, n_nodes, d_uni_off, d_members, d_node_unitig, d_node_pos, n_unitigs,
+                                               d_keys, d_src_edge, capacity, &n_out);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_out;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "s2k_hpc_device", "s2k_hpc_device_ex", "s2k_count_device", "s2k_count_device_ex", "s2k_partition_device", "s2k_synth_bases_device", "s2k_synth_hifi_lengths", "s2k_synth_hifi_device", "s2k_last_kernel_ms", "s2k_enable_timing", "s2k_timing_total", "s2k_fastx_open", "s2k_fastx_next", "s2k_fastx_close", "s2k_run_file", "s2k_fastx_parse_device",
     "s2k_count_merge_device", "s2k_counter_create", "s2k_counter_destroy", "s2k_counter_add", "s2k_counter_finish", "s2k_run_file_count",
     "s2k_table_create", "s2k_table_destroy", "s2k_table_lookup", "s2k_table_filter", "s2k_table_edges", "s2k_graph_adjacency",
+    "s2k_graph_unitigs", "s2k_graph_unitig_edges", "s2k_graph_unitigs_last_steps",
 ]
 
 
@@ -83,6 +84,11 @@ class DeviceOut(C.Structure):
 class SolidOut(C.Structure):
     _fields_ = [("capacity", C.c_uint64), ("km_off", C.c_void_p), ("hash", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p),
                 ("rev", C.c_void_p), ("offset", C.c_void_p), ("count", C.c_void_p)]
+
+
+class UnitigOut(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("uni_off", C.c_void_p), ("members", C.c_void_p), ("node_unitig", C.c_void_p),
+                ("node_pos", C.c_void_p), ("circular", C.c_void_p)]
 
 
 _lib = None
@@ -155,6 +161,12 @@ def load_library(path=None):
     L.s2k_table_filter.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.POINTER(SolidOut), C.POINTER(C.c_uint64)]
     L.s2k_table_edges.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_graph_adjacency.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.s2k_graph_unitigs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(UnitigOut), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64)]
+    L.s2k_graph_unitig_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.s2k_graph_unitigs_last_steps.restype = None
+    L.s2k_graph_unitigs_last_steps.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -428,6 +440,49 @@ class Engine:
                                                  C.c_void_p(row_off.data_ptr()), C.c_void_p(dst.data_ptr())))
         return row_off, dst[:n]
 
+    def graph_unitigs(self, row_off, dst, n_nodes):
+        """The unitigs of a twin-symmetric graph (s2k_graph_unitigs) from its CSR as graph_adjacency returns it (S2kError(1) when the
+        CSR breaks a rule or an edge's twin is missing) -> dict of GPU tensors uni_off (int64, n_unitigs + 1), members (int32, n_nodes
+        oriented ids: the kept strands in path order), node_unitig / node_pos (int32, n_nodes), circular (uint8, n_unitigs), and the ints
+        n_unitigs, n_links."""
+        import torch
+
+        if row_off.numel() != 2 * int(n_nodes) + 1 or row_off.element_size() != 8 or dst.element_size() != 4 or not row_off.is_cuda:
+            raise ValueError("graph_unitigs wants the row_off (2 * n_nodes + 1, 64-bit) and dst (32-bit) of graph_adjacency on the GPU")
+        row_off, dst = row_off.contiguous(), dst.contiguous()
+        n, ne, dev = int(n_nodes), dst.numel(), row_off.device
+        res = {"uni_off": torch.empty(n + 1, dtype=torch.int64, device=dev), "members": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+               "node_unitig": torch.empty(max(n, 1), dtype=torch.int32, device=dev), "node_pos": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+               "circular": torch.empty(max(n, 1), dtype=torch.uint8, device=dev)}
+        o = UnitigOut()
+        o.capacity = n  # at most one unitig per node
+        for f, t in res.items():
+            setattr(o, f, t.data_ptr())
+        nu, nl = C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_graph_unitigs(self.ctx, C.c_void_p(row_off.data_ptr()), C.c_void_p(dst.data_ptr() if ne else 0), ne, n,
+                                               C.byref(o), C.byref(nu), C.byref(nl)))
+        t = int(nu.value)
+        return {"uni_off": res["uni_off"][:t + 1], "members": res["members"][:n], "node_unitig": res["node_unitig"][:n],
+                "node_pos": res["node_pos"][:n], "circular": res["circular"][:t], "n_unitigs": t, "n_links": int(nl.value)}
+
+    def graph_unitig_edges(self, row_off, dst, n_nodes, unitigs):
+        """The edges between the oriented unitigs (s2k_graph_unitig_edges): `unitigs` is what graph_unitigs returned for the same CSR
+        -> (keys, src_edge): int64 tensors, keys U << 32 | V strictly ascending (as uint64) and the index of the CSR edge each came from."""
+        import torch
+
+        row_off, dst = row_off.contiguous(), dst.contiguous()
+        ne, dev = dst.numel(), row_off.device
+        cap = ne - unitigs["n_links"]
+        keys = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        src = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        no = C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_graph_unitig_edges(self.ctx, C.c_void_p(row_off.data_ptr()), C.c_void_p(dst.data_ptr() if ne else 0), ne, int(n_nodes),
+                                                    *(C.c_void_p(unitigs[f].data_ptr()) for f in ("uni_off", "members", "node_unitig", "node_pos")),
+                                                    unitigs["n_unitigs"], C.c_void_p(keys.data_ptr()), C.c_void_p(src.data_ptr()), cap, C.byref(no)))
+        return keys[:int(no.value)], src[:int(no.value)]
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -644,6 +699,66 @@ class KminmerGraph:
         ek = self.edge_keys.cpu().numpy().view(np.uint64)
         ec = self.edge_counts.cpu().numpy().view(np.uint32)
         write_gfa(path, keys, counts, ek, ec)
+
+    def unitigs(self, engine):
+        """Compacts the non-branching paths on the device (Engine.graph_unitigs, Engine.graph_unitig_edges) -> UnitigGraph"""
+        import torch
+
+        n = self.n_nodes
+        u = engine.graph_unitigs(self.row_off, self.dst, n)
+        t = u["n_unitigs"]
+        csum = torch.zeros(n + 1, dtype=torch.int64, device=self.row_off.device)
+        if n:  # per unitig the sum of its nodes' counts, in member order
+            csum[1:] = torch.cumsum((self.counts[(u["members"] >> 1).long()].long() & 0xFFFFFFFF), 0)
+        counts = csum[u["uni_off"][1:]] - csum[u["uni_off"][:-1]]
+        ek, src = engine.graph_unitig_edges(self.row_off, self.dst, n, u)
+        ec = self.edge_counts[src] if ek.numel() else self.edge_counts[:0]
+        row_off, dst = engine.graph_adjacency(ek, t)
+        return UnitigGraph(u["uni_off"], u["members"], u["node_unitig"], u["node_pos"], u["circular"], counts, ek, ec, row_off, dst, u["n_links"])
+
+
+class UnitigGraph:
+    """The compacted graph (KminmerGraph.unitigs; include/s2k.h: s2k_graph_unitigs): unitig t holds the oriented nodes
+    members[uni_off[t] : uni_off[t + 1]] (its kept strand, in path order), counts[t] = the sum of its nodes' counts, circular[t] tells a
+    cycle; node i lies in unitig node_unitig[i] at position node_pos[i].  Oriented unitig U = 2 t + s (s = 1: the twin strand); edge j
+    goes from edge_keys[j] >> 32 to dst[j] and was seen edge_counts[j] times; row_off / dst are the CSR over the oriented unitigs."""
+
+    def __init__(self, uni_off, members, node_unitig, node_pos, circular, counts, edge_keys, edge_counts, row_off, dst, n_links=0):
+        self.uni_off, self.members, self.node_unitig, self.node_pos, self.circular, self.counts = uni_off, members, node_unitig, node_pos, circular, counts
+        self.edge_keys, self.edge_counts, self.row_off, self.dst, self.n_links = edge_keys, edge_counts, row_off, dst, n_links
+
+    @property
+    def n_unitigs(self):
+        return self.circular.numel()
+
+    @property
+    def n_edges(self):
+        return self.edge_keys.numel()
+
+    def write_gfa(self, path, members=False):
+        """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
+        members=True an nd:Z: tag that lists node index and orientation in path order) and an L line per twin pair of edges, by the rule
+        of KminmerGraph.write_gfa (RC:i: the edge count)."""
+        write_unitig_gfa(path, self.uni_off.cpu().numpy().view(np.uint64), self.members.cpu().numpy().view(np.uint32), self.counts.cpu().numpy(),
+                         self.edge_keys.cpu().numpy().view(np.uint64), self.edge_counts.cpu().numpy().view(np.uint32), members=members)
+
+
+def write_unitig_gfa(path, uni_off, members_arr, counts, edge_keys, edge_counts, members=False):
+    """UnitigGraph.write_gfa on host arrays"""
+    uo, mem = np.asarray(uni_off, dtype=np.uint64).tolist(), np.asarray(members_arr, dtype=np.uint32).tolist()
+    ek, ec = np.asarray(edge_keys, dtype=np.uint64), np.asarray(edge_counts, dtype=np.uint32)
+    u, v = ek >> np.uint64(32), ek & np.uint64(0xFFFFFFFF)
+    twin = ((v ^ np.uint64(1)) << np.uint64(32)) | (u ^ np.uint64(1))
+    sel = ek <= twin
+    sign = "+-"
+    with open(path, "w") as f:
+        f.write("H\tVN:Z:1.0\n")
+        for t, c in enumerate(np.asarray(counts).tolist()):
+            a, b = uo[t], uo[t + 1]
+            nd = "\tnd:Z:" + ",".join("%d%s" % (x >> 1, sign[x & 1]) for x in mem[a:b]) if members else ""
+            f.write("S\t%d\t*\tLN:i:%d\tKC:i:%d%s\n" % (t, b - a, c, nd))
+        f.writelines("L\t%d\t%s\t%d\t%s\t*\tRC:i:%d\n" % (a >> 1, sign[a & 1], b >> 1, sign[b & 1], c)
+                     for a, b, c in zip(u[sel].tolist(), v[sel].tolist(), ec[sel].tolist()))
 
 
 def write_gfa(path, keys, counts, edge_keys, edge_counts):
