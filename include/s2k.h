@@ -45,6 +45,7 @@ extern "C" {
  * (s2k_table_edges and s2k_graph_adjacency were added the same way: added entry points, the version stays 2.)
  * (s2k_graph_unitigs, s2k_graph_unitig_edges, s2k_graph_unitigs_last_steps and the struct s2k_unitig_out were added the same way:
  * added entry points and one new struct, the version stays 2.)
+ * (s2k_table_representatives, s2k_table_node_sequences, s2k_unitig_sequences and the struct s2k_node_seqs were added the same way.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -363,6 +364,66 @@ s2k_status s2k_graph_unitig_edges(s2k_ctx *ctx, const uint64_t *d_row_off, const
  * of which ends in a host wait -- ms[0] check, ms[1] links + list ranking, ms[2] numbering, ms[3] lengths + scatter -- and the number
  * of jump rounds it ran (ranking, and for cycles the minimum rounds and the second ranking).  Not for concurrent callers. */
 void s2k_graph_unitigs_last_steps(double *ms, uint32_t *rounds);
+/* ---- base-space sequences of the nodes and unitigs -----------------------------------------------------------
+ * What rust-mdbg keeps per solid k-min-mer: the bases of one occurrence and two shifts; a unitig's sequence is each member's first
+ * `shift` bases, then the whole last member.  Inputs per batch: what s2k_extract_device wrote WITH S2K_FLAG_WANT_MINIMIZERS (km_off,
+ * hash, rev, mn_off, mn_j, mn_jend), the batch's d_bases / d_read_off, the order k, and the table whose keys are the nodes.
+ * Item j of read r is made of the read's minimizers j .. j + k - 1, the triples mn_off[r] + j .. mn_off[r] + j + k - 1: a read with
+ * n > 0 items has exactly n + k - 1 triples (src/lib.rs:231-258).
+ * Ordinal of item x of a batch: ordinal_base + x, ordinal_base = the items of all earlier batches (the global item order).
+ * Representative of node i: the occurrence (an item whose hash is key i, whatever its count) with the smallest ordinal.
+ * Node record, all from the representative (r, j): B = the read's bytes mn_j[j] ..= mn_jend[j + k - 1] as they are in d_bases
+ * (original space also in the Hpc modes), seq_len = |B|, rev = the item's rev, shift_fwd = mn_j[j + 1] - mn_j[j], shift_rev =
+ * mn_jend[j + k - 1] - mn_jend[j + k - 2].
+ * Oriented node u = 2 i + o: seq(u) = B and shift(u) = shift_fwd when o == rev, otherwise seq(u) = revcomp(B) and shift(u) =
+ * shift_rev; revcomp reverses and maps ACGTacgt -> TGCAtgca, every other byte stays what it is.  shift(u) <= seq_len always.
+ * Sequence of unitig t with kept-strand members m_0 .. m_(n-1): seq(m_0)[:shift(m_0)] + .. + seq(m_(n-2))[:shift(m_(n-2))] +
+ * seq(m_(n-1)); the last member of a circular unitig too gives only its first shift bytes.  The twin strand is the reverse
+ * complement by definition and is not stored.  Overlap of an edge that leaves the oriented node u (or the oriented unitig whose last
+ * member, in its orientation, is u): seq_len(u) - shift(u), "<n>M" in GFA.
+ * With reads that hold sequencing errors the occurrences of a node differ, so a stitched sequence is one consistent choice (the
+ * earliest occurrence of every node), not a consensus -- as in rust-mdbg.  The same holds, also for error-free reads, where two
+ * different k-min-mers share a 64-bit hash: they are one node, which takes the bytes of whichever occurs first.  Everything here is a
+ * function of the input alone (its order included): bit-identical from call to call.
+ *
+ * s2k_table_representatives: d_rep[i] = min(d_rep[i], ordinal_base + x) over the items x of the batch whose hash is key i.  d_rep
+ * (one uint64_t per key) is the caller's: filled with 0xFF bytes before the first batch, carried from batch to batch.  km_off and
+ * hash of `in` required, km_off[0] == 0. */
+s2k_status s2k_table_representatives(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint64_t ordinal_base, uint64_t *d_rep);
+typedef struct s2k_node_seqs { /* device pointers; the five record arrays hold one entry per key of the table */
+    uint64_t *seq_off;         /* where B starts in pool */
+    uint32_t *seq_len;         /* 0: no record (the caller zero-initialises seq_len; a key whose d_rep is still all ones keeps 0) */
+    uint32_t *shift_fwd;
+    uint32_t *shift_rev;
+    uint8_t *rev;
+    uint8_t *pool;
+    uint64_t pool_capacity;    /* bytes */
+} s2k_node_seqs;
+/* For every item of the batch that IS its node's representative (d_rep[node] == ordinal_base + x, d_rep complete: every batch has
+ * been through s2k_table_representatives) the node's record is written and B copied to pool + pool_used + (the summed lengths of the
+ * representatives before it in this batch, in item order): after the last batch the pool is ordered by representative ordinal.
+ * *n_bytes = the bytes this batch adds, always set; the caller adds it to pool_used for the next batch.  Every key that occurs in
+ * some batch has a record then.  nodes == NULL or nodes->pool == NULL asks for *n_bytes only; otherwise all five record arrays are
+ * required, and pool_used + *n_bytes > pool_capacity is S2K_ERR_CAPACITY with nothing written.  Checked on the device before
+ * anything is written, S2K_ERR_INVALID_ARG otherwise: km_off[0] == mn_off[0] == 0, neither decreases, in->mn_capacity covers
+ * mn_off[n_reads], every read with n > 0 items has n + k - 1 triples (it catches a wrong k, or the triples of another call), every
+ * position a representative uses lies inside its read and in order.  k < 2 is refused (no second minimizer), as are missing
+ * km_off / hash / rev / mn_off / mn_j / mn_jend.  d_read_off is trusted to be the table s2k_extract_device validated.  Uses the
+ * context's grow-only count workspace: 16 B per item.  Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_table_node_sequences(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t k, const uint8_t *d_bases,
+                                    const uint64_t *d_read_off, uint64_t ordinal_base, const uint64_t *d_rep, const s2k_node_seqs *nodes,
+                                    uint64_t pool_used, uint64_t *n_bytes);
+/* The stitch: d_out[d_out_off[t] .. d_out_off[t + 1]) = the sequence of unitig t, for the unitigs (d_uni_off, d_members, d_circular,
+ * n_unitigs) that s2k_graph_unitigs wrote over n_nodes nodes, whose records are `nodes` (pool_capacity bounds every read of the
+ * pool).  d_overlap (may be NULL; 2 * n_unitigs entries) = the overlap that leaves each oriented unitig.  *n_bases is always set;
+ * d_out_off (n_unitigs + 1 entries, may be NULL) and d_overlap are written whenever the call succeeds; d_out == NULL asks for them
+ * and the size only; *n_bases > capacity with d_out given is S2K_ERR_CAPACITY and nothing at all is written.  d_out must be 16-byte
+ * aligned (stores are 16 bytes wide).  Checked on the device before anything is written (S2K_ERR_INVALID_ARG): uni_off starts at 0,
+ * ends at n_nodes, every unitig holds a member; every member names a node below n_nodes whose record has rev <= 1, both shifts <=
+ * seq_len and its bytes inside the pool.  A node without a record (seq_len 0) contributes nothing.  Workspace: 12 B per member. */
+s2k_status s2k_unitig_sequences(s2k_ctx *ctx, const uint64_t *d_uni_off, const uint32_t *d_members, const uint8_t *d_circular,
+                                uint64_t n_unitigs, uint64_t n_nodes, const s2k_node_seqs *nodes, uint64_t *d_out_off, uint8_t *d_out,
+                                uint32_t *d_overlap, uint64_t capacity, uint64_t *n_bases);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

@@ -164,6 +164,18 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return n_out;
     }
+    // s2k_unitig_sequences: the unitigs' base-space sequences stitched from the node records (s2k_node_seqs, filled by
+    // Table::node_sequences); d_out_off (n_unitigs + 1), d_out (16-byte aligned) and d_overlap (2 * n_unitigs) may each be nullptr.
+    // Returns the number of bases (throws on S2K_ERR_CAPACITY too: nothing is written then).
+    uint64_t unitig_sequences(const uint64_t *d_uni_off, const uint32_t *d_members, const uint8_t *d_circular, uint64_t n_unitigs, uint64_t n_nodes,
+                              const s2k_node_seqs &nodes, uint64_t *d_out_off, uint8_t *d_out = nullptr, uint64_t capacity = 0,
+                              uint32_t *d_overlap = nullptr) {
+        uint64_t n_bases = 0;
+        s2k_status st = s2k_unitig_sequences(ctx_, d_uni_off, d_members, d_circular, n_unitigs, n_nodes, &nodes, d_out_off, d_out, d_overlap, capacity,
+                                             &n_bases);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_bases;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:
@@ -223,6 +235,20 @@ class Table {
         uint64_t n_edges = 0;
         check(s2k_table_edges(t_, n_reads, &in, min_count, d_edge_keys, capacity, &n_edges));
         return n_edges;
+    }
+    // s2k_table_representatives: d_rep[i] = min(d_rep[i], ordinal_base + x) over the batch's items x whose hash is key i (d_rep: one
+    // uint64_t per key, 0xFF bytes before the first batch)
+    void representatives(uint64_t n_reads, const s2k_device_out &in, uint64_t ordinal_base, uint64_t *d_rep) {
+        check(s2k_table_representatives(t_, n_reads, &in, ordinal_base, d_rep));
+    }
+    // s2k_table_node_sequences: the records and bytes of the nodes whose representative lies in this batch (`in` written with
+    // S2K_FLAG_WANT_MINIMIZERS); nodes nullptr: the size only.  Returns the bytes the batch adds to the pool (throws on
+    // S2K_ERR_CAPACITY too).
+    uint64_t node_sequences(uint64_t n_reads, const s2k_device_out &in, uint32_t k, const uint8_t *d_bases, const uint64_t *d_read_off,
+                            uint64_t ordinal_base, const uint64_t *d_rep, const s2k_node_seqs *nodes = nullptr, uint64_t pool_used = 0) {
+        uint64_t n_bytes = 0;
+        check(s2k_table_node_sequences(t_, n_reads, &in, k, d_bases, d_read_off, ordinal_base, d_rep, nodes, pool_used, &n_bytes));
+        return n_bytes;
     }
     s2k_table *raw() { return t_; }
 

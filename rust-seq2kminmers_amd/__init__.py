@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "s2k_count_merge_device", "s2k_counter_create", "s2k_counter_destroy", "s2k_counter_add", "s2k_counter_finish", "s2k_run_file_count",
     "s2k_table_create", "s2k_table_destroy", "s2k_table_lookup", "s2k_table_filter", "s2k_table_edges", "s2k_graph_adjacency",
     "s2k_graph_unitigs", "s2k_graph_unitig_edges", "s2k_graph_unitigs_last_steps",
+    "s2k_table_representatives", "s2k_table_node_sequences", "s2k_unitig_sequences",
 ]
 
 
@@ -89,6 +90,11 @@ class SolidOut(C.Structure):
 class UnitigOut(C.Structure):
     _fields_ = [("capacity", C.c_uint64), ("uni_off", C.c_void_p), ("members", C.c_void_p), ("node_unitig", C.c_void_p),
                 ("node_pos", C.c_void_p), ("circular", C.c_void_p)]
+
+
+class NodeSeqs(C.Structure):
+    _fields_ = [("seq_off", C.c_void_p), ("seq_len", C.c_void_p), ("shift_fwd", C.c_void_p), ("shift_rev", C.c_void_p), ("rev", C.c_void_p),
+                ("pool", C.c_void_p), ("pool_capacity", C.c_uint64)]
 
 
 _lib = None
@@ -167,6 +173,11 @@ def load_library(path=None):
                                          C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_graph_unitigs_last_steps.restype = None
     L.s2k_graph_unitigs_last_steps.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.s2k_table_representatives.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint64, C.c_void_p]
+    L.s2k_table_node_sequences.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                           C.POINTER(NodeSeqs), C.c_uint64, C.POINTER(C.c_uint64)]
+    L.s2k_unitig_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(NodeSeqs), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -483,6 +494,28 @@ class Engine:
                                                     unitigs["n_unitigs"], C.c_void_p(keys.data_ptr()), C.c_void_p(src.data_ptr()), cap, C.byref(no)))
         return keys[:int(no.value)], src[:int(no.value)]
 
+    def unitig_sequences(self, uni_off, members, circular, n_nodes, node_seqs):
+        """The unitigs' base-space sequences (s2k_unitig_sequences) from the arrays graph_unitigs returned and a NodeSequences ->
+        (out_off, out, overlap): int64 tensor of n_unitigs + 1 offsets, uint8 tensor of the bases (unitig t is out[out_off[t] :
+        out_off[t + 1]]), int32 tensor of the overlap that leaves each oriented unitig 2 t + s."""
+        import torch
+
+        uni_off, members, circular = uni_off.contiguous(), members.contiguous(), circular.contiguous()
+        t, n, dev = circular.numel(), int(n_nodes), uni_off.device
+        out_off = torch.zeros(t + 1, dtype=torch.int64, device=dev)
+        overlap = torch.zeros(max(2 * t, 1), dtype=torch.int32, device=dev)
+        ns, nb = node_seqs.struct(), C.c_uint64(0)
+        args = (self.ctx, C.c_void_p(uni_off.data_ptr()), C.c_void_p(members.data_ptr() if n else 0), C.c_void_p(circular.data_ptr() if t else 0), t, n,
+                C.byref(ns), C.c_void_p(out_off.data_ptr()))
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_unitig_sequences(*args, None, C.c_void_p(overlap.data_ptr()), 0, C.byref(nb)))
+        total = int(nb.value)
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        if total:
+            torch.cuda.synchronize(dev)
+            self._check(self.lib.s2k_unitig_sequences(*args, C.c_void_p(out.data_ptr()), C.c_void_p(overlap.data_ptr()), total, C.byref(nb)))
+        return out_off, out[:total], overlap[:2 * t]
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -648,6 +681,105 @@ class CountTable:
         return keys[:int(ne.value)]
 
 
+def _seq_in(o, n_reads):
+    """the DeviceOut of one batch's extraction outputs for the sequence calls (km_off, hash, rev; mn_off, mn_j, mn_jend when present)"""
+    i = DeviceOut()
+    i.km_capacity = int(o["km_off"][n_reads].item()) if n_reads else 0
+    i.km_off, i.hash = o["km_off"].data_ptr(), o["hash"].data_ptr()
+    if o.get("rev") is not None:
+        i.rev = o["rev"].data_ptr()
+    if o.get("mn_off") is not None:
+        i.mn_capacity = int(o["mn_off"][n_reads].item()) if n_reads else 0
+        i.mn_off, i.mn_j, i.mn_jend = (o[f].data_ptr() for f in ("mn_off", "mn_j", "mn_jend"))
+    return i
+
+
+class NodeSequences:
+    """Base-space records of a graph's nodes (include/s2k.h: s2k_table_representatives, s2k_table_node_sequences):
+    per node i the bytes pool[seq_off[i] : seq_off[i] + seq_len[i]] of its representative (the occurrence with the smallest global
+    item ordinal), its rev, and the two shifts; rep[i] = that ordinal.  All GPU tensors (int64 / int32 / uint8 holding the unsigned
+    values)."""
+
+    FIELDS = ("seq_off", "seq_len", "shift_fwd", "shift_rev", "rev")
+
+    def __init__(self, rep, seq_off, seq_len, shift_fwd, shift_rev, rev, pool, n_bytes, k):
+        self.rep, self.seq_off, self.seq_len, self.shift_fwd, self.shift_rev, self.rev = rep, seq_off, seq_len, shift_fwd, shift_rev, rev
+        self.pool, self.n_bytes, self.k = pool, n_bytes, k
+
+    def struct(self, pool_capacity=None):
+        ns = NodeSeqs()
+        for f in self.FIELDS + ("pool",):
+            setattr(ns, f, getattr(self, f).data_ptr())
+        ns.pool_capacity = self.n_bytes if pool_capacity is None else pool_capacity
+        return ns
+
+    def host(self):
+        """-> dict of numpy arrays: seq_off uint64, seq_len / shift_fwd / shift_rev uint32, rev uint8, pool uint8, rep uint64"""
+        d = {"seq_off": self.seq_off.cpu().numpy().view(np.uint64), "rev": self.rev.cpu().numpy(), "pool": self.pool[:self.n_bytes].cpu().numpy(),
+             "rep": self.rep.cpu().numpy().view(np.uint64)}
+        for f in ("seq_len", "shift_fwd", "shift_rev"):
+            d[f] = getattr(self, f).cpu().numpy().view(np.uint32)
+        return d
+
+    @classmethod
+    def build(cls, engine, table_or_graph, outs, k=None):
+        """outs: per batch the GPU tensors extract_device wrote with FLAG_WANT_MINIMIZERS (km_off, hash, rev, mn_off, mn_j, mn_jend) plus
+        the batch's `bases` and `read_off`, in the order the graph was built from; table_or_graph: the CountTable of the nodes, or a
+        KminmerGraph (a table over its keys lives for this call).  k (the k-min-mer order) is taken from the first read with items
+        when not given; the device checks it against every read.  Three rounds over the batches: representatives, sizes, records."""
+        import torch
+
+        own = isinstance(table_or_graph, KminmerGraph)
+        table = CountTable(engine, table_or_graph.keys, table_or_graph.counts) if own else table_or_graph
+        try:
+            dev = torch.device("cuda", engine.device)
+            n_keys = table.n
+            ins, bases = [], []
+            for o in outs:
+                nr = o["km_off"].numel() - 1
+                if o.get("mn_off") is None or o.get("bases") is None or o.get("read_off") is None:
+                    raise ValueError("NodeSequences.build wants mn_off, mn_j, mn_jend, bases and read_off beside km_off, hash and rev")
+                i = _seq_in(o, nr)
+                if k is None and i.km_capacity:
+                    n_it, n_tr = (o["km_off"][1:] - o["km_off"][:-1]), (o["mn_off"][1:] - o["mn_off"][:-1])
+                    r = int(torch.nonzero(n_it)[0, 0])
+                    k = int(n_tr[r]) - int(n_it[r]) + 1
+                ins.append((i, nr))
+                bases.append((o["bases"], o["read_off"]))
+            k = 2 if k is None else int(k)
+            rep = torch.full((max(n_keys, 1),), -1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize(dev)
+            base = 0
+            for i, nr in ins:
+                engine._check(engine.lib.s2k_table_representatives(table.handle, nr, C.byref(i), base, C.c_void_p(rep.data_ptr())))
+                base += i.km_capacity
+
+            def round_(ns):
+                base, used = 0, 0
+                for (i, nr), (b, ro) in zip(ins, bases):
+                    nb = C.c_uint64(0)
+                    engine._check(engine.lib.s2k_table_node_sequences(table.handle, nr, C.byref(i), k, C.c_void_p(b.data_ptr() if b.numel() else 0),
+                                                                      C.c_void_p(ro.data_ptr()), base, C.c_void_p(rep.data_ptr()),
+                                                                      C.byref(ns) if ns is not None else None, used, C.byref(nb)))
+                    base += i.km_capacity
+                    used += int(nb.value)
+                return used
+
+            total = round_(None)
+            m = max(n_keys, 1)
+            res = cls(rep[:n_keys], torch.zeros(m, dtype=torch.int64, device=dev), torch.zeros(m, dtype=torch.int32, device=dev),
+                      torch.zeros(m, dtype=torch.int32, device=dev), torch.zeros(m, dtype=torch.int32, device=dev),
+                      torch.zeros(m, dtype=torch.uint8, device=dev), torch.empty(max(total, 1), dtype=torch.uint8, device=dev), total, k)
+            torch.cuda.synchronize(dev)
+            round_(res.struct())
+            for f in cls.FIELDS:
+                setattr(res, f, getattr(res, f)[:n_keys])
+            return res
+        finally:
+            if own:
+                table.close()
+
+
 class KminmerGraph:
     """The minimizer-space de Bruijn graph of a read set, built on the device in two passes over its extraction outputs (dicts of the
     GPU tensors extract_device wrote: km_off, hash, rev; n_reads = len(km_off) - 1): pass 1 counts the k-min-mers (KminmerCounter) and
@@ -690,15 +822,16 @@ class KminmerGraph:
         row_off, dst = engine.graph_adjacency(edge_keys, keys.numel())
         return cls(keys, counts, edge_keys, edge_counts, row_off, dst)
 
-    def write_gfa(self, path):
+    def write_gfa(self, path, sequences=None):
         """GFA 1: an S line per node (name = node index, sequence *, KC:i: its count, kh:Z: its hash in 16 hex digits) and an L line per
         twin pair, written once, for the edge whose key is not above its twin's (orientation 0 -> +, 1 -> -, overlap *, RC:i: its
-        count)."""
+        count).  With sequences (a NodeSequences of this graph) the S line carries the bases of the node's orientation 0 and LN:i:
+        their number, and the L line the overlap seq_len(u) - shift(u) as <n>M."""
         keys = self.keys.cpu().numpy().view(np.uint64)
         counts = self.counts.cpu().numpy().view(np.uint32)
         ek = self.edge_keys.cpu().numpy().view(np.uint64)
         ec = self.edge_counts.cpu().numpy().view(np.uint32)
-        write_gfa(path, keys, counts, ek, ec)
+        write_gfa(path, keys, counts, ek, ec, sequences=None if sequences is None else sequences.host())
 
     def unitigs(self, engine):
         """Compacts the non-branching paths on the device (Engine.graph_unitigs, Engine.graph_unitig_edges) -> UnitigGraph"""
@@ -714,7 +847,9 @@ class KminmerGraph:
         ek, src = engine.graph_unitig_edges(self.row_off, self.dst, n, u)
         ec = self.edge_counts[src] if ek.numel() else self.edge_counts[:0]
         row_off, dst = engine.graph_adjacency(ek, t)
-        return UnitigGraph(u["uni_off"], u["members"], u["node_unitig"], u["node_pos"], u["circular"], counts, ek, ec, row_off, dst, u["n_links"])
+        ug = UnitigGraph(u["uni_off"], u["members"], u["node_unitig"], u["node_pos"], u["circular"], counts, ek, ec, row_off, dst, u["n_links"])
+        ug.n_nodes = n
+        return ug
 
 
 class UnitigGraph:
@@ -735,34 +870,75 @@ class UnitigGraph:
     def n_edges(self):
         return self.edge_keys.numel()
 
-    def write_gfa(self, path, members=False):
+    def sequences(self, engine, node_seqs):
+        """The unitigs' base-space sequences stitched on the device (Engine.unitig_sequences) from a NodeSequences of the graph this one
+        was compacted from -> (out_off, out): unitig t is out[out_off[t] : out_off[t + 1]] (its kept strand).  The overlap that leaves
+        every oriented unitig is kept in self.overlap for write_gfa."""
+        n = getattr(self, "n_nodes", self.members.numel())
+        out_off, out, self.overlap = engine.unitig_sequences(self.uni_off, self.members, self.circular, n, node_seqs)
+        return out_off, out
+
+    def write_gfa(self, path, members=False, sequences=None):
         """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
         members=True an nd:Z: tag that lists node index and orientation in path order) and an L line per twin pair of edges, by the rule
-        of KminmerGraph.write_gfa (RC:i: the edge count)."""
+        of KminmerGraph.write_gfa (RC:i: the edge count).  With sequences (the pair self.sequences returned) the S line carries the
+        bases, LN:i: their number and nm:i: the number of members, and the L line the overlap as <n>M."""
+        seq = None
+        if sequences is not None:
+            if getattr(self, "overlap", None) is None:
+                raise ValueError("write_gfa(sequences=...) wants the pair that self.sequences(engine, node_seqs) returned")
+            seq = (sequences[0].cpu().numpy().view(np.uint64), sequences[1].cpu().numpy(), self.overlap.cpu().numpy().view(np.uint32))
         write_unitig_gfa(path, self.uni_off.cpu().numpy().view(np.uint64), self.members.cpu().numpy().view(np.uint32), self.counts.cpu().numpy(),
-                         self.edge_keys.cpu().numpy().view(np.uint64), self.edge_counts.cpu().numpy().view(np.uint32), members=members)
+                         self.edge_keys.cpu().numpy().view(np.uint64), self.edge_counts.cpu().numpy().view(np.uint32), members=members, sequences=seq)
 
 
-def write_unitig_gfa(path, uni_off, members_arr, counts, edge_keys, edge_counts, members=False):
-    """UnitigGraph.write_gfa on host arrays"""
+_REVCOMP = np.arange(256, dtype=np.uint8)
+_REVCOMP[list(b"ACGTacgt")] = list(b"TGCAtgca")
+
+
+def revcomp(seq):
+    """reversed, ACGTacgt -> TGCAtgca, every other byte as it is (the revcomp of include/s2k.h) -> bytes"""
+    return _REVCOMP[_as_u8(seq)][::-1].tobytes()
+
+
+def write_fasta(path, out_off, out):
+    """One record per unitig: >index, then its bases on one line (out_off / out: what UnitigGraph.sequences returned, tensors or host
+    arrays)"""
+    off = np.asarray(out_off.cpu() if hasattr(out_off, "cpu") else out_off).astype(np.int64).tolist()
+    text = np.asarray(out.cpu() if hasattr(out, "cpu") else out, dtype=np.uint8).tobytes()
+    with open(path, "wb") as f:
+        for t in range(len(off) - 1):
+            f.write(b">%d\n%s\n" % (t, text[off[t]:off[t + 1]]))
+
+
+def write_unitig_gfa(path, uni_off, members_arr, counts, edge_keys, edge_counts, members=False, sequences=None):
+    """UnitigGraph.write_gfa on host arrays; sequences = (out_off, out, overlap): the offsets and bases of the unitigs and the overlap
+    that leaves each oriented unitig"""
     uo, mem = np.asarray(uni_off, dtype=np.uint64).tolist(), np.asarray(members_arr, dtype=np.uint32).tolist()
     ek, ec = np.asarray(edge_keys, dtype=np.uint64), np.asarray(edge_counts, dtype=np.uint32)
     u, v = ek >> np.uint64(32), ek & np.uint64(0xFFFFFFFF)
     twin = ((v ^ np.uint64(1)) << np.uint64(32)) | (u ^ np.uint64(1))
     sel = ek <= twin
     sign = "+-"
+    if sequences is not None:
+        so, text = np.asarray(sequences[0]).astype(np.int64).tolist(), np.asarray(sequences[1], dtype=np.uint8).tobytes()
+        ov = np.asarray(sequences[2]).astype(np.int64).tolist()
     with open(path, "w") as f:
         f.write("H\tVN:Z:1.0\n")
         for t, c in enumerate(np.asarray(counts).tolist()):
             a, b = uo[t], uo[t + 1]
             nd = "\tnd:Z:" + ",".join("%d%s" % (x >> 1, sign[x & 1]) for x in mem[a:b]) if members else ""
-            f.write("S\t%d\t*\tLN:i:%d\tKC:i:%d%s\n" % (t, b - a, c, nd))
-        f.writelines("L\t%d\t%s\t%d\t%s\t*\tRC:i:%d\n" % (a >> 1, sign[a & 1], b >> 1, sign[b & 1], c)
+            if sequences is None:
+                f.write("S\t%d\t*\tLN:i:%d\tKC:i:%d%s\n" % (t, b - a, c, nd))
+            else:
+                f.write("S\t%d\t%s\tLN:i:%d\tnm:i:%d\tKC:i:%d%s\n" % (t, text[so[t]:so[t + 1]].decode("latin-1"), so[t + 1] - so[t], b - a, c, nd))
+        f.writelines("L\t%d\t%s\t%d\t%s\t%s\tRC:i:%d\n" % (a >> 1, sign[a & 1], b >> 1, sign[b & 1], "*" if sequences is None else "%dM" % ov[a], c)
                      for a, b, c in zip(u[sel].tolist(), v[sel].tolist(), ec[sel].tolist()))
 
 
-def write_gfa(path, keys, counts, edge_keys, edge_counts):
-    """KminmerGraph.write_gfa on host arrays: node keys / counts (uint64 / uint32) and edge keys / counts (uint64 / uint32)."""
+def write_gfa(path, keys, counts, edge_keys, edge_counts, sequences=None):
+    """KminmerGraph.write_gfa on host arrays: node keys / counts (uint64 / uint32) and edge keys / counts (uint64 / uint32); sequences =
+    the dict NodeSequences.host() returns (seq_off, seq_len, shift_fwd, shift_rev, rev, pool)."""
     keys, counts = np.asarray(keys, dtype=np.uint64), np.asarray(counts, dtype=np.uint32)
     ek, ec = np.asarray(edge_keys, dtype=np.uint64), np.asarray(edge_counts, dtype=np.uint32)
     u, v = ek >> np.uint64(32), ek & np.uint64(0xFFFFFFFF)
@@ -771,9 +947,20 @@ def write_gfa(path, keys, counts, edge_keys, edge_counts):
     sign = np.array(["+", "-"])
     with open(path, "w") as f:
         f.write("H\tVN:Z:1.0\n")
-        f.writelines("S\t%d\t*\tKC:i:%d\tkh:Z:%016x\n" % (i, c, h) for i, (h, c) in enumerate(zip(keys.tolist(), counts.tolist())))
         su, sv = u[sel], v[sel]
-        f.writelines("L\t%d\t%s\t%d\t%s\t*\tRC:i:%d\n" % (a >> 1, sign[a & 1], b >> 1, sign[b & 1], c)
+        if sequences is None:
+            f.writelines("S\t%d\t*\tKC:i:%d\tkh:Z:%016x\n" % (i, c, h) for i, (h, c) in enumerate(zip(keys.tolist(), counts.tolist())))
+            f.writelines("L\t%d\t%s\t%d\t%s\t*\tRC:i:%d\n" % (a >> 1, sign[a & 1], b >> 1, sign[b & 1], c)
+                         for a, b, c in zip(su.tolist(), sv.tolist(), ec[sel].tolist()))
+            return
+        so, sl, rv = (np.asarray(sequences[x]).astype(np.int64).tolist() for x in ("seq_off", "seq_len", "rev"))
+        sh = (np.asarray(sequences["shift_fwd"]).astype(np.int64).tolist(), np.asarray(sequences["shift_rev"]).astype(np.int64).tolist())
+        pool = np.asarray(sequences["pool"], dtype=np.uint8).tobytes()
+        for i, (h, c) in enumerate(zip(keys.tolist(), counts.tolist())):  # orientation 0 of node i: B when rev == 0, else its reverse complement
+            b = pool[so[i]:so[i] + sl[i]]
+            f.write("S\t%d\t%s\tLN:i:%d\tKC:i:%d\tkh:Z:%016x\n" % (i, (revcomp(b) if rv[i] else b).decode("latin-1") or "*", sl[i], c, h))
+        f.writelines("L\t%d\t%s\t%d\t%s\t%dM\tRC:i:%d\n" % (a >> 1, sign[a & 1], b >> 1, sign[b & 1],
+                                                              sl[a >> 1] - sh[0 if (a & 1) == rv[a >> 1] else 1][a >> 1], c)
                      for a, b, c in zip(su.tolist(), sv.tolist(), ec[sel].tolist()))
 
 

@@ -35,100 +35,10 @@
 #include "../../include/s2k.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
+#include "s2k_table_dev.h"
 
 namespace s2k {
 namespace {
-
-constexpr int TB_THREADS = 256;
-constexpr int TB_Q = 8;                             // queries (items) per lane
-constexpr uint32_t TB_TILE = TB_THREADS * TB_Q;    // 2 048 items per workgroup of the filter
-constexpr int TB_WORDS = TB_TILE / 64;              // kept-mask words per tile
-constexpr uint64_t TB_KEYS_PER_BUCKET = 4;          // B = floor(log2(n / 4)): 4-7 keys per bucket on average
-constexpr uint32_t TB_MAX_BITS = 26;
-
-struct TableView {
-    const uint64_t *keys;
-    const uint32_t *counts; // NULL: membership table (count 1)
-    const uint32_t *dir;    // 2^bits + 1 entries
-    uint32_t n;
-    uint32_t shift;         // 64 - bits
-};
-
-// c[r] = count of q[r] in the table (0 if absent); with POS also rank[r] = its index in the table (0 if absent).  The look-up and
-// the filter use POS = false, the instantiation that compiles to the code they had before the ranks existed.
-template <bool POS>
-__device__ inline void lookup_many(const TableView &tv, const uint64_t (&q)[TB_Q], uint32_t (&c)[TB_Q], uint32_t *rank) {
-    if (tv.n == 0) {
-#pragma unroll
-        for (int r = 0; r < TB_Q; r++) {
-            c[r] = 0;
-            if (POS) rank[r] = 0;
-        }
-        return;
-    }
-    uint32_t lo[TB_Q], hi[TB_Q], pos[TB_Q];
-    bool hit[TB_Q];
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) { // every directory load in flight before the first use
-        const uint64_t p = q[r] >> tv.shift;
-        lo[r] = tv.dir[p];
-        hi[r] = tv.dir[p + 1];
-    }
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) {
-        hit[r] = false;
-        pos[r] = 0;
-    }
-    for (;;) { // TB_Q searches side by side; a finished one reloads its last key (a cache hit) instead of branching around the load
-        uint64_t kv[TB_Q];
-        uint32_t mid[TB_Q];
-#pragma unroll
-        for (int r = 0; r < TB_Q; r++) {
-            mid[r] = (lo[r] + hi[r]) >> 1;
-            kv[r] = tv.keys[std::min<uint32_t>(mid[r], tv.n - 1)];
-        }
-        bool more = false;
-#pragma unroll
-        for (int r = 0; r < TB_Q; r++) {
-            if (lo[r] < hi[r]) {
-                if (kv[r] < q[r]) lo[r] = mid[r] + 1;
-                else if (kv[r] > q[r]) hi[r] = mid[r];
-                else { // keys are strictly ascending: the one match
-                    hit[r] = true;
-                    pos[r] = mid[r];
-                    lo[r] = hi[r];
-                }
-                more |= lo[r] < hi[r];
-            }
-        }
-        if (!more) break;
-    }
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) c[r] = hit[r] ? (tv.counts ? tv.counts[pos[r]] : 1u) : 0u;
-    if (POS) {
-#pragma unroll
-        for (int r = 0; r < TB_Q; r++) rank[r] = pos[r];
-    }
-}
-
-// one query (the edge kernel's halo item): *c its count, *pos its index (both 0 if absent)
-__device__ inline void lookup_one(const TableView &tv, uint64_t q, uint32_t *c, uint32_t *pos) {
-    *c = *pos = 0;
-    if (tv.n == 0) return;
-    const uint64_t p = q >> tv.shift;
-    uint32_t lo = tv.dir[p], hi = tv.dir[p + 1];
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        const uint64_t k = tv.keys[mid];
-        if (k < q) lo = mid + 1;
-        else if (k > q) hi = mid;
-        else {
-            *c = tv.counts ? tv.counts[mid] : 1u;
-            *pos = mid;
-            return;
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void table_index_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint32_t shift, uint32_t bits,
                                                           uint32_t *__restrict__ dir, uint32_t *__restrict__ bad) {
@@ -452,16 +362,6 @@ uint32_t table_bits(uint64_t n) {
 } // namespace s2k
 
 using namespace s2k;
-
-struct s2k_table {
-    s2k_ctx *ctx;
-    const uint64_t *keys;
-    const uint32_t *counts;
-    uint64_t n;
-    uint32_t bits;
-    uint32_t *dir; // 2^bits + 1 entries, then the validation flag
-    TableView view() const { return TableView{keys, counts, dir, (uint32_t)n, 64u - bits}; }
-};
 
 extern "C" {
 
