@@ -364,6 +364,60 @@ s2k_status s2k_graph_unitig_edges(s2k_ctx *ctx, const uint64_t *d_row_off, const
  * of which ends in a host wait -- ms[0] check, ms[1] links + list ranking, ms[2] numbering, ms[3] lengths + scatter -- and the number
  * of jump rounds it ran (ranking, and for cycles the minimum rounds and the second ranking).  Not for concurrent callers. */
 void s2k_graph_unitigs_last_steps(double *ms, uint32_t *rounds);
+/* ---- simplification: tips clipped and simple bubbles popped on the unitig graph ---------------------------------
+ * Input: the compacted graph -- the CSR over the 2 T oriented unitigs (d_row_off, d_dst: what s2k_graph_adjacency writes from the
+ * keys of s2k_graph_unitig_edges; twin-symmetric), and per unitig t len[t] = uni_off[t + 1] - uni_off[t] (members) and cnt[t] (the
+ * summed counts of its nodes, uint64_t).  For an oriented unitig U = 2 t + s: succ(U) = its CSR row, out(U) = |succ(U)|, pred(U) =
+ * { X ^ 1 : X in succ(U ^ 1) }, in(U) = out(U ^ 1).  "The unitig of U" is U >> 1.
+ * Order "W beats U" (strict and total over distinct unitigs), decided by the first of these that differs: the higher mean count,
+ * cnt[W] * len[U] > cnt[U] * len[W], compared exactly as 128-bit products (no floating point); then more members; then the smaller
+ * unitig index.
+ * Tip: U is a tip candidate iff out(U) == 0, in(U) >= 1 and len[U] <= max_tip.  U is a removable tip iff it is a candidate and, for
+ * every P in pred(U): P is not of U's own unitig, and succ(P) holds some W of another unitig than U that is not a tip candidate or
+ * that beats U.  So the best branch at every junction stays, a tip that is some predecessor's only continuation stays, and an
+ * isolated unitig (in == out == 0) is no tip.
+ * Simple bubble: U is a removable bubble branch iff out(U) == in(U) == 1, len[U] <= max_bubble, its one predecessor P and its one
+ * successor S are both of other unitigs than U, and succ(P) holds a W of another unitig than U with out(W) == in(W) == 1, succ(W) ==
+ * { S } and W beats U.
+ * Removal: unitig t is removed iff 2 t or 2 t + 1 meets either rule; node i is removed iff its unitig is.  Both rules read the same
+ * input graph, so the result does not depend on an evaluation order.  max_tip == 0 / max_bubble == 0 switches that rule off (every
+ * unitig holds a member).
+ * Invariant: a kept oriented unitig with out >= 1 still has a kept successor, so one round creates no new dead end.  (The maximum
+ * under "beats" among the candidates of a junction is removable only beside a sibling that is no candidate; a class of parallel
+ * bubble branches keeps its maximum, which has out == 1 and so is no tip candidate.)
+ *
+ * s2k_graph_simplify_mask: d_remove[t] (one byte per unitig, 0 / 1; NULL: the totals only), *n_tips and *n_bubbles = the unitigs
+ * removed by each rule (one that meets both counts in both), *n_removed = the bytes set.  One lane per oriented unitig; a lane walks
+ * the short rows at its junctions (a hub is slow, never wrong).  Checked on the device before anything is written, one flag word read
+ * by the host, S2K_ERR_INVALID_ARG otherwise: row_off[0] == 0, non-decreasing, row_off[2 n_unitigs] == n_edges, every id below
+ * 2 n_unitigs, uni_off strictly ascending (every unitig holds a member).  Twin symmetry is trusted (s2k_graph_unitigs checks it).
+ * n_unitigs >= 2^31 is refused; n_unitigs == 0 needs n_edges == 0 and reads nothing.  d_dst may be NULL when n_edges == 0.  The
+ * three totals are integer sums: the outputs are a function of the input, bit-identical from call to call.  Workspace: 32 B of the
+ * context's grow-only count workspace.  Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_graph_simplify_mask(s2k_ctx *ctx, const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs,
+                                   const uint64_t *d_uni_off, const uint64_t *d_uni_count, uint32_t max_tip, uint32_t max_bubble,
+                                   uint8_t *d_remove, uint64_t *n_tips, uint64_t *n_bubbles, uint64_t *n_removed);
+/* The subgraph induced by the kept nodes of a graph (d_keys / d_counts: its node table, strictly ascending; d_edge_keys /
+ * d_edge_counts: its edges, u << 32 | v strictly ascending, as s2k_graph_adjacency takes them).  Which nodes are kept comes from one
+ * of two sources: d_node_keep (one byte per node, non-zero = kept), or, when d_node_keep is NULL, the unitig mask gathered inside
+ * the call, keep[i] = !d_remove[d_node_unitig[i]] (d_node_unitig of s2k_graph_unitigs, d_remove of s2k_graph_simplify_mask over
+ * n_unitigs unitigs; an entry >= n_unitigs is S2K_ERR_INVALID_ARG).
+ * d_new_id[i] (n_nodes entries) = the kept nodes before i (ids in ascending old order), 0xFFFFFFFF for a removed node.  The new node
+ * table is the kept (key, count) pairs: still strictly ascending, so s2k_table_create accepts it.  An edge is kept iff both its ends
+ * are; its key becomes (2 new_id[u >> 1] + (u & 1)) << 32 | (2 new_id[v >> 1] + (v & 1)), its count goes with it.  The map is
+ * monotone: the kept keys stay strictly ascending without a sort, and the subgraph of a twin-symmetric graph is twin-symmetric.
+ * *n_nodes_out and *n_edges_out are always set.  Every output array may be NULL (all NULL: the sizes only); d_counts / d_edge_counts
+ * may be NULL when their outputs are.  The arrays are written only when *n_nodes_out <= node_capacity (asked of d_keys_out /
+ * d_counts_out) and *n_edges_out <= edge_capacity (of d_edge_keys_out / d_edge_counts_out), otherwise S2K_ERR_CAPACITY and nothing is
+ * written.  An edge that names a node >= n_nodes is S2K_ERR_INVALID_ARG, found on the device before anything is written; the order
+ * of keys is trusted.  Outputs must not overlap inputs.  n_nodes >= 2^31 is refused.  Workspace (the context's grow-only count
+ * workspace): 0.2 B per node and per edge (a kept bit, and 4 B per 64 items and per tile of 2048 items), and 4 B per node when
+ * d_new_id is NULL and edge outputs are asked for.  Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_graph_induced(s2k_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_counts, uint64_t n_nodes, const uint64_t *d_edge_keys,
+                             const uint32_t *d_edge_counts, uint64_t n_edges, const uint8_t *d_node_keep, const uint32_t *d_node_unitig,
+                             const uint8_t *d_remove, uint64_t n_unitigs, uint32_t *d_new_id, uint64_t *d_keys_out, uint32_t *d_counts_out,
+                             uint64_t node_capacity, uint64_t *d_edge_keys_out, uint32_t *d_edge_counts_out, uint64_t edge_capacity,
+                             uint64_t *n_nodes_out, uint64_t *n_edges_out);
 /* ---- base-space sequences of the nodes and unitigs -----------------------------------------------------------
  * What rust-mdbg keeps per solid k-min-mer: the bases of one occurrence and two shifts; a unitig's sequence is each member's first
  * `shift` bases, then the whole last member.  Inputs per batch: what s2k_extract_device wrote WITH S2K_FLAG_WANT_MINIMIZERS (km_off,

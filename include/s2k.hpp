@@ -164,6 +164,36 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return n_out;
     }
+    // s2k_graph_simplify_mask: one round of tip clipping and simple-bubble popping on the unitig graph (CSR over 2 * n_unitigs oriented
+    // unitigs, d_uni_off, d_uni_count = the summed node counts); d_remove (one byte per unitig) may be nullptr: the totals only.
+    struct SimplifyTotals {
+        uint64_t tips, bubbles, removed;
+    };
+    SimplifyTotals graph_simplify_mask(const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs,
+                                       const uint64_t *d_uni_off, const uint64_t *d_uni_count, uint32_t max_tip, uint32_t max_bubble,
+                                       uint8_t *d_remove) {
+        SimplifyTotals t{};
+        s2k_status st = s2k_graph_simplify_mask(ctx_, d_row_off, d_dst, n_edges, n_unitigs, d_uni_off, d_uni_count, max_tip, max_bubble, d_remove,
+                                                &t.tips, &t.bubbles, &t.removed);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
+    // s2k_graph_induced: the subgraph of the kept nodes.  Kept = d_node_keep[i] != 0, or (d_node_keep nullptr) !d_remove[d_node_unitig[i]].
+    // Every output may be nullptr (all: the sizes only).  Returns {nodes, edges} kept; throws on S2K_ERR_CAPACITY too (nothing written).
+    struct InducedSizes {
+        uint64_t nodes, edges;
+    };
+    InducedSizes graph_induced(const uint64_t *d_keys, const uint32_t *d_counts, uint64_t n_nodes, const uint64_t *d_edge_keys,
+                               const uint32_t *d_edge_counts, uint64_t n_edges, const uint8_t *d_node_keep, const uint32_t *d_node_unitig,
+                               const uint8_t *d_remove, uint64_t n_unitigs, uint32_t *d_new_id, uint64_t *d_keys_out, uint32_t *d_counts_out,
+                               uint64_t node_capacity, uint64_t *d_edge_keys_out, uint32_t *d_edge_counts_out, uint64_t edge_capacity) {
+        InducedSizes n{};
+        s2k_status st = s2k_graph_induced(ctx_, d_keys, d_counts, n_nodes, d_edge_keys, d_edge_counts, n_edges, d_node_keep, d_node_unitig, d_remove,
+                                          n_unitigs, d_new_id, d_keys_out, d_counts_out, node_capacity, d_edge_keys_out, d_edge_counts_out,
+                                          edge_capacity, &n.nodes, &n.edges);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n;
+    }
     // s2k_unitig_sequences: the unitigs' base-space sequences stitched from the node records (s2k_node_seqs, filled by
     // Table::node_sequences); d_out_off (n_unitigs + 1), d_out (16-byte aligned) and d_overlap (2 * n_unitigs) may each be nullptr.
     // Returns the number of bases (throws on S2K_ERR_CAPACITY too: nothing is written then).

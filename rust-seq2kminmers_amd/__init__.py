@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "s2k_table_create", "s2k_table_destroy", "s2k_table_lookup", "s2k_table_filter", "s2k_table_edges", "s2k_graph_adjacency",
     "s2k_graph_unitigs", "s2k_graph_unitig_edges", "s2k_graph_unitigs_last_steps",
     "s2k_table_representatives", "s2k_table_node_sequences", "s2k_unitig_sequences",
+    "s2k_graph_simplify_mask", "s2k_graph_induced",
 ]
 
 
@@ -173,6 +174,11 @@ def load_library(path=None):
                                          C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_graph_unitigs_last_steps.restype = None
     L.s2k_graph_unitigs_last_steps.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.s2k_graph_simplify_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                          C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_graph_induced.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.s2k_table_representatives.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint64, C.c_void_p]
     L.s2k_table_node_sequences.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                            C.POINTER(NodeSeqs), C.c_uint64, C.POINTER(C.c_uint64)]
@@ -494,6 +500,59 @@ class Engine:
                                                     unitigs["n_unitigs"], C.c_void_p(keys.data_ptr()), C.c_void_p(src.data_ptr()), cap, C.byref(no)))
         return keys[:int(no.value)], src[:int(no.value)]
 
+    def graph_simplify_mask(self, unitig_graph, max_tip, max_bubble):
+        """One round of tip clipping and simple-bubble popping (s2k_graph_simplify_mask; the rules are in include/s2k.h) on a UnitigGraph:
+        a tip holds at most max_tip members, a bubble branch at most max_bubble; 0 switches a rule off -> dict: remove (uint8 GPU tensor,
+        one byte per unitig) and the ints n_tips, n_bubbles (a unitig that meets both rules counts in both), n_removed."""
+        import torch
+
+        ug = unitig_graph
+        t, ne, dev = ug.n_unitigs, ug.dst.numel(), ug.row_off.device
+        row_off, dst, uni_off, counts = ug.row_off.contiguous(), ug.dst.contiguous(), ug.uni_off.contiguous(), ug.counts.contiguous()
+        if counts.element_size() != 8 or counts.numel() != t or uni_off.numel() != t + 1 or row_off.numel() != 2 * t + 1:
+            raise ValueError("graph_simplify_mask wants a UnitigGraph: 64-bit counts, one per unitig, and the CSR over its oriented unitigs")
+        remove = torch.zeros(max(t, 1), dtype=torch.uint8, device=dev)
+        nt, nb, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_graph_simplify_mask(self.ctx, C.c_void_p(row_off.data_ptr()), C.c_void_p(dst.data_ptr() if ne else 0), ne, t,
+                                                     C.c_void_p(uni_off.data_ptr()), C.c_void_p(counts.data_ptr() if t else 0), int(max_tip),
+                                                     int(max_bubble), C.c_void_p(remove.data_ptr()), C.byref(nt), C.byref(nb), C.byref(nr)))
+        return {"remove": remove[:t], "n_tips": int(nt.value), "n_bubbles": int(nb.value), "n_removed": int(nr.value)}
+
+    def graph_induced(self, graph, node_keep=None, node_unitig=None, remove=None):
+        """The subgraph of a KminmerGraph that its kept nodes induce (s2k_graph_induced).  Kept: node_keep (uint8 GPU tensor, one byte per
+        node, non-zero = kept), or, without it, the nodes whose unitig is not removed: node_unitig (UnitigGraph.node_unitig) and remove
+        (graph_simplify_mask's).  -> dict of GPU tensors keys, counts, edge_keys, edge_counts (the kept ones, renumbered) and new_id (int32,
+        one per old node: its new id, -1 for a removed node)."""
+        import torch
+
+        n, ne, dev = graph.n_nodes, graph.n_edges, graph.keys.device
+        null = C.c_void_p(0)
+        if node_keep is not None:
+            node_keep = node_keep.contiguous()
+            if node_keep.numel() != n or node_keep.element_size() != 1:
+                raise ValueError("graph_induced: node_keep holds one byte per node")
+            mask_args = (C.c_void_p(node_keep.data_ptr()), null, null, 0)
+        elif node_unitig is not None and remove is not None:
+            node_unitig, remove = node_unitig.contiguous(), remove.contiguous()
+            if node_unitig.numel() != n or node_unitig.element_size() != 4 or remove.element_size() != 1:
+                raise ValueError("graph_induced: node_unitig holds one 32-bit unitig per node, remove one byte per unitig")
+            # the number of unitigs is the length of remove: the device refuses a node_unitig entry beyond it
+            mask_args = (null, C.c_void_p(node_unitig.data_ptr()), C.c_void_p(remove.data_ptr()), remove.numel())
+        else:
+            raise ValueError("graph_induced wants node_keep, or node_unitig and remove")
+        keys, counts, ek, ec = (x.contiguous() for x in (graph.keys, graph.counts, graph.edge_keys, graph.edge_counts))
+        new_id = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        ok, oc = torch.empty(max(n, 1), dtype=torch.int64, device=dev), torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        oek, oec = torch.empty(max(ne, 1), dtype=torch.int64, device=dev), torch.empty(max(ne, 1), dtype=torch.int32, device=dev)
+        nn, nne = C.c_uint64(0), C.c_uint64(0)
+        p = lambda t, m=1: C.c_void_p(t.data_ptr() if m else 0)  # noqa: E731
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_graph_induced(self.ctx, p(keys, n), p(counts, n), n, p(ek, ne), p(ec, ne), ne, *mask_args,
+                                               p(new_id), p(ok), p(oc), n, p(oek), p(oec), ne, C.byref(nn), C.byref(nne)))
+        a, b = int(nn.value), int(nne.value)
+        return {"keys": ok[:a], "counts": oc[:a], "edge_keys": oek[:b], "edge_counts": oec[:b], "new_id": new_id[:n]}
+
     def unitig_sequences(self, uni_off, members, circular, n_nodes, node_seqs):
         """The unitigs' base-space sequences (s2k_unitig_sequences) from the arrays graph_unitigs returned and a NodeSequences ->
         (out_off, out, overlap): int64 tensor of n_unitigs + 1 offsets, uint8 tensor of the bases (unitig t is out[out_off[t] :
@@ -721,6 +780,15 @@ class NodeSequences:
             d[f] = getattr(self, f).cpu().numpy().view(np.uint32)
         return d
 
+    def subset(self, node_map):
+        """The records of the nodes a simplification kept, under their new ids: node_map is what KminmerGraph.simplify returned (per old
+        node its new id, -1 for a removed one; new ids ascend with the old ones).  The record arrays are gathered, the pool is shared,
+        not copied."""
+        import torch
+
+        old = torch.nonzero(node_map >= 0)[:, 0]
+        return type(self)(*(getattr(self, f)[old] for f in ("rep",) + self.FIELDS), self.pool, self.n_bytes, self.k)
+
     @classmethod
     def build(cls, engine, table_or_graph, outs, k=None):
         """outs: per batch the GPU tensors extract_device wrote with FLAG_WANT_MINIMIZERS (km_off, hash, rev, mn_off, mn_j, mn_jend) plus
@@ -850,6 +918,32 @@ class KminmerGraph:
         ug = UnitigGraph(u["uni_off"], u["members"], u["node_unitig"], u["node_pos"], u["circular"], counts, ek, ec, row_off, dst, u["n_links"])
         ug.n_nodes = n
         return ug
+
+
+    def simplify(self, engine, max_tip, max_bubble, max_rounds=16):
+        """Clips tips of at most max_tip members and pops simple bubbles whose removed branch holds at most max_bubble members (the rules
+        are in include/s2k.h; 0 switches one off), round by round on the device -- unitigs, Engine.graph_simplify_mask,
+        Engine.graph_induced, Engine.graph_adjacency -- until a round removes nothing or max_rounds rounds have run.
+        -> (graph, node_map, stats): a new KminmerGraph over the kept nodes (self is untouched); node_map, an int32 GPU tensor with the
+        final id of every node of self, -1 for a removed one; stats, one dict per round (nodes and unitigs the round started from, tips,
+        bubbles and unitigs it removed), the last of which removed nothing when a fixed point was reached."""
+        import torch
+
+        g = KminmerGraph(self.keys, self.counts, self.edge_keys, self.edge_counts, self.row_off, self.dst)
+        node_map = torch.arange(self.n_nodes, dtype=torch.int32, device=self.keys.device)
+        stats = []
+        for _ in range(max_rounds):
+            ug = g.unitigs(engine)
+            m = engine.graph_simplify_mask(ug, max_tip, max_bubble)
+            stats.append({"nodes": g.n_nodes, "unitigs": ug.n_unitigs, "tips": m["n_tips"], "bubbles": m["n_bubbles"], "removed": m["n_removed"]})
+            if m["n_removed"] == 0:
+                break
+            ind = engine.graph_induced(g, node_unitig=ug.node_unitig, remove=m["remove"])
+            row_off, dst = engine.graph_adjacency(ind["edge_keys"], ind["keys"].numel())
+            g = KminmerGraph(ind["keys"], ind["counts"], ind["edge_keys"], ind["edge_counts"], row_off, dst)
+            alive = torch.nonzero(node_map >= 0)[:, 0]  # new_id holds -1 for a removed node: the composition keeps it
+            node_map[alive] = ind["new_id"][node_map[alive].long()]
+        return g, node_map, stats
 
 
 class UnitigGraph:
