@@ -1,0 +1,120 @@
+// s2k_compact_dev.h -- the stable stream compaction over tiles of TB_TILE items that the filter and the edges (s2k_table.hip,
+// DESIGN.md §3.8, §3.9) and the induced subgraph (s2k_simplify.hip, §3.12) share, and the one workgroup scan.
+//
+// Lane tid of a tile's workgroup holds items r * TB_THREADS + tid, r = 0 .. TB_Q - 1.  A count kernel ballots its items (word
+// r * 4 + wave of the tile), stores the mask and its popcount and ends in tile_prefixes; launch_scan_u32 over tile_kept gives
+// tile_off; a write kernel takes its slots from tile_slots, stages what it keeps in LDS at them and lets the run go with leave_run.
+#pragma once
+#include <algorithm>
+
+#include "s2k_call.h"
+#include "s2k_dev.h"
+
+namespace s2k {
+namespace {
+
+constexpr int TB_THREADS = 256;
+constexpr int TB_Q = 8;                          // items per lane
+constexpr uint32_t TB_TILE = TB_THREADS * TB_Q; // 2 048 items per workgroup
+constexpr int TB_WORDS = TB_TILE / 64;           // mask words per tile
+
+// exclusive scan over a workgroup of NW waves; *total = the sum; wsum: NW words of LDS
+template <int NW>
+__device__ inline uint32_t block_excl_scan(uint32_t x, uint32_t *wsum, uint32_t *total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t incl = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(incl, o);
+        if (lane >= o) incl += y;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        const uint32_t v = wsum[j];
+        pre += j < w ? v : 0u;
+        tot += v;
+    }
+    __syncthreads();
+    *total = tot;
+    return pre + incl - x;
+}
+
+struct CompactWs {
+    uint64_t *wmask;     // per 64 items: kept mask
+    uint32_t *wpre;      // per 64 items: kept items before the word inside its tile
+    uint32_t *tile_kept; // per tile
+    uint64_t *tile_off;  // n_tiles + 1
+};
+
+// after the TB_Q ballots of a tile (wc[r * 4 + wave] = the popcount of that word): the words' prefixes and the tile's total
+__device__ __forceinline__ void tile_prefixes(const uint32_t *wc, uint64_t t0, uint64_t n_items, const CompactWs &ws) {
+    const int tid = threadIdx.x;
+    if (tid < TB_WORDS) { // word k of the tile = items t0 + 64 k ..: r = k / 4, wave k % 4
+        uint32_t pre = 0;
+        for (int x = 0; x < tid; x++) pre += wc[x];
+        const uint64_t w0 = t0 + (uint64_t)tid * 64;
+        if (w0 < n_items) ws.wpre[w0 >> 6] = pre;
+        if (tid == TB_WORDS - 1) ws.tile_kept[blockIdx.x] = pre + wc[tid];
+    }
+}
+
+// the tile-relative slot of each of the lane's TB_Q items -> the bits of those that are kept
+__device__ __forceinline__ uint32_t tile_slots(const CompactWs &ws, uint64_t t0, uint64_t n_items, uint32_t slot[TB_Q]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t keep = 0;
+#pragma unroll
+    for (int r = 0; r < TB_Q; r++) {
+        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
+        const uint64_t m = w0 < n_items ? ws.wmask[w0 >> 6] : 0ull;
+        const uint32_t pre = w0 < n_items ? ws.wpre[w0 >> 6] : 0u;
+        slot[r] = pre + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        keep |= (uint32_t)((m >> lane) & 1ull) << r;
+    }
+    return keep;
+}
+
+// elements between p and the 16-byte boundary below it
+template <typename T>
+__device__ __forceinline__ uint32_t shift_of(const T *p) {
+    return (uint32_t)(((uintptr_t)p & 15u) / sizeof(T));
+}
+
+// lds[shift .. shift + tot) -> out[0 .. tot), out = the run's first output address and shift = shift_of(out): whole 16-byte pieces
+// where a piece lies inside the run, element by element at the two ends.  Ends with a barrier: lds may be staged again.
+template <typename T>
+__device__ __forceinline__ void leave_run(T *__restrict__ out, const T *lds, uint32_t shift, uint32_t tot) {
+    constexpr uint32_t V = 16 / sizeof(T);
+    const uint32_t lo = shift, hi = shift + tot;
+    const uint32_t vlo = std::min((lo + V - 1) & ~(V - 1), hi), vhi = std::max(hi & ~(V - 1), vlo);
+    T *o = out - shift; // o[i] <-> lds[i]; o + vlo is 16-byte aligned
+    for (uint32_t i = lo + threadIdx.x; i < vlo; i += TB_THREADS) o[i] = lds[i];
+    for (uint32_t i = vlo / V + threadIdx.x; i < vhi / V; i += TB_THREADS) ((uint4 *)o)[i] = ((const uint4 *)lds)[i];
+    for (uint32_t i = vhi + threadIdx.x; i < hi; i += TB_THREADS) o[i] = lds[i];
+    __syncthreads();
+}
+
+constexpr uint32_t STAGE_PAD = 2; // a run starts at most 15 bytes into its first 16-byte piece: one more 8-byte element, rounded up
+
+// the workspace of one stream of n items in n_tiles tiles, taken from a call's layout: the four arrays and the tile scan's block sums
+struct CompactPieces {
+    Layout::Piece<uint64_t> wmask;
+    Layout::Piece<uint32_t> wpre, tile_kept;
+    Layout::Piece<uint64_t> tile_off, scan_tmp;
+    CompactWs operator()(char *w) const { return CompactWs{wmask(w), wpre(w), tile_kept(w), tile_off(w)}; }
+};
+inline CompactPieces carve(Layout &L, uint64_t n, uint64_t n_tiles) {
+    const uint64_t words = (n + 63) / 64;
+    CompactPieces p;
+    p.wmask = L.take<uint64_t>(words);
+    p.wpre = L.take<uint32_t>(words);
+    p.tile_kept = L.take<uint32_t>(n_tiles);
+    p.tile_off = L.take<uint64_t>(n_tiles + 1);
+    p.scan_tmp = L.bytes<uint64_t>(scan_tmp_bytes(n_tiles));
+    return p;
+}
+
+} // namespace
+} // namespace s2k

@@ -13,6 +13,7 @@
 //    hash PREFIX) -- the send buffers of the one real exchange step of the multi-GPU version: an all-to-all after which
 //    rank p owns every occurrence of the hashes in its range and counts locally (rust-seq2kminmers_amd/sharding.py).
 #include "../../include/s2k.h"
+#include "s2k_call.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
 
@@ -137,39 +138,32 @@ extern "C" {
 s2k_status s2k_count_device(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n, uint64_t *d_keys, uint32_t *d_counts,
                             uint64_t capacity, uint64_t *n_distinct) {
     if (!ctx || (!d_hash && n) || !n_distinct) return S2K_ERR_INVALID_ARG;
-    hipStream_t st = ctx_stream(ctx);
+    Call c(ctx, "s2k_count_device");
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
     const uint64_t slots = (n + n / 2 + 1024 + 255) & ~(uint64_t)255; // load factor <= 2/3
     const size_t bytes = slots * 12 + 64;
     void *ws = ctx_count_table(ctx, bytes);
-    if (!ws) {
-        ctx_set_error(ctx, "s2k_count_device: table allocation");
-        return S2K_ERR_NOMEM;
-    }
+    if (!ws) return c.nomem("table allocation");
     uint64_t *tkeys = (uint64_t *)ws;
     uint32_t *tcnt = (uint32_t *)((char *)ws + slots * 8);
     unsigned long long *cursor = (unsigned long long *)((char *)ws + slots * 12);
     uint32_t *n_empty = (uint32_t *)((char *)ws + slots * 12 + 8);
-    hipError_t e = hipMemsetAsync(tkeys, 0xFF, slots * 8, st);
-    if (e == hipSuccess) e = hipMemsetAsync(tcnt, 0, slots * 4 + 64, st);
-    if (e == hipSuccess && n) {
+    c.fill(tkeys, 0xFF, slots * 8);
+    c.zero(tcnt, slots * 4 + 64);
+    if (c.ok() && n) {
         const uint64_t blocks = (n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536;
-        hipLaunchKernelGGL(count_insert_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_hash, n, tkeys, tcnt, slots, n_empty);
-        e = hipGetLastError();
+        hipLaunchKernelGGL(count_insert_kernel, dim3((unsigned)blocks), dim3(256), 0, c.st, d_hash, n, tkeys, tcnt, slots, n_empty);
+        c.launched();
     }
-    if (e == hipSuccess) {
+    if (c.ok()) {
         const uint64_t blocks = slots / 256 < 65536 ? slots / 256 : 65536;
-        hipLaunchKernelGGL(count_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, st, tkeys, tcnt, slots, d_keys, d_counts, capacity,
+        hipLaunchKernelGGL(count_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, c.st, tkeys, tcnt, slots, d_keys, d_counts, capacity,
                            cursor, n_empty);
-        e = hipGetLastError();
+        c.launched();
     }
     unsigned long long total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, cursor, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_count_device: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    c.fetch(&total, cursor, 8);
+    if (!c.sync()) return c.device_error();
     *n_distinct = total;
     return (total > capacity && (d_keys || d_counts)) ? S2K_ERR_CAPACITY : S2K_OK;
 }
@@ -177,26 +171,19 @@ s2k_status s2k_count_device(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n, ui
 s2k_status s2k_partition_device(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n, uint32_t n_parts, uint64_t *d_out,
                                 uint64_t *d_part_off) {
     if (!ctx || (!d_hash && n) || (!d_out && n) || !d_part_off || n_parts == 0 || n_parts > S2K_MAX_PARTS) return S2K_ERR_INVALID_ARG;
-    hipStream_t st = ctx_stream(ctx);
+    Call c(ctx, "s2k_partition_device");
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
     unsigned long long *ws = (unsigned long long *)ctx_count_table(ctx, 2 * S2K_MAX_PARTS * 8);
-    if (!ws) {
-        ctx_set_error(ctx, "s2k_partition_device: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    hipError_t e = hipMemsetAsync(ws, 0, 2 * S2K_MAX_PARTS * 8, st);
+    if (!ws) return c.nomem();
+    c.zero(ws, 2 * S2K_MAX_PARTS * 8);
     const uint64_t blocks = n ? ((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384) : 1;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(part_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_hash, n, n_parts, ws);
-        hipLaunchKernelGGL(part_scan_kernel, dim3(1), dim3(1), 0, st, ws, n_parts, d_part_off, ws + S2K_MAX_PARTS);
-        hipLaunchKernelGGL(part_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_hash, n, n_parts, ws + S2K_MAX_PARTS, d_out);
-        e = hipGetLastError();
+    if (c.ok()) {
+        hipLaunchKernelGGL(part_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, c.st, d_hash, n, n_parts, ws);
+        hipLaunchKernelGGL(part_scan_kernel, dim3(1), dim3(1), 0, c.st, ws, n_parts, d_part_off, ws + S2K_MAX_PARTS);
+        hipLaunchKernelGGL(part_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, c.st, d_hash, n, n_parts, ws + S2K_MAX_PARTS, d_out);
+        c.launched();
     }
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_partition_device: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 

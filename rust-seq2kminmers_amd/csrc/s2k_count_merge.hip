@@ -20,6 +20,8 @@
 #include <vector>
 
 #include "../../include/s2k.h"
+#include "s2k_call.h"
+#include "s2k_compact_dev.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
 
@@ -42,30 +44,6 @@ struct MergeMeta {
 __device__ inline uint32_t sat_add(uint32_t a, uint32_t b) {
     const uint64_t s = (uint64_t)a + b;
     return s > SAT ? SAT : (uint32_t)s;
-}
-
-// exclusive scan over the workgroup (MG_THREADS / 64 waves); *total = the sum; wsum: MG_THREADS / 64 words of LDS
-__device__ inline uint32_t mg_block_scan(uint32_t x, uint32_t *wsum, uint32_t *total) {
-    constexpr int NW = MG_THREADS / 64;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if (lane >= o) incl += y;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        const uint32_t v = wsum[j];
-        pre += j < w ? v : 0u;
-        tot += v;
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + incl - x;
 }
 
 // split[t] = A items among the first min(t * MG_TILE, na + nb) items of the merge (ties: A first), t = 0 .. n_tiles
@@ -180,10 +158,10 @@ __global__ __launch_bounds__(MG_THREADS) void merge_tile_kernel(const uint64_t *
     }
 
     uint32_t tot;
-    const uint32_t pos = mg_block_scan(n_keep, wsum, &tot); // (its barriers also end every lane's reads of the staged slices)
+    const uint32_t pos = block_excl_scan<MG_THREADS / 64>(n_keep, wsum, &tot); // (its barriers also end every lane's reads of the staged slices)
     if (!WRITE) {
         uint32_t dist_tot;
-        (void)mg_block_scan(n_dist, wsum, &dist_tot);
+        (void)block_excl_scan<MG_THREADS / 64>(n_dist, wsum, &dist_tot);
         if (tid == 0) {
             tile_kept[t] = tot;
             if (dist_tot) atomicAdd(&meta->n_distinct, (unsigned long long)dist_tot);
@@ -208,8 +186,6 @@ __global__ __launch_bounds__(MG_THREADS) void merge_tile_kernel(const uint64_t *
     }
 }
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Tab {
     const uint64_t *keys;
     const uint32_t *counts;
@@ -231,47 +207,33 @@ s2k_status merge_count(s2k_ctx *ctx, const Tab &a, const Tab &b, uint32_t minc, 
     ws->n_tiles = 0;
     if (n == 0) return S2K_OK;
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
+    Call c(ctx, "s2k_count_merge_device");
     const uint64_t nt = (n + MG_TILE - 1) / MG_TILE;
-    if (nt * MG_THREADS >= (1ull << 32)) { // the grid's thread count must fit 32 bits: 2^36 items
-        ctx_set_error(ctx, "s2k_count_merge_device: more than 2^36 items");
-        return S2K_ERR_INVALID_ARG;
-    }
-    size_t off = 0;
-    const size_t oS = off; off += al((nt + 1) * 8);
-    const size_t oO = off; off += al((nt + 1) * 8);
-    const size_t oK = off; off += al(nt * 4);
-    const size_t oT = off; off += al(scan_tmp_bytes(nt));
-    const size_t oM = off; off += al(sizeof(MergeMeta));
-    char *w = (char *)ctx_count_table(ctx, off);
-    if (!w) {
-        ctx_set_error(ctx, "s2k_count_merge_device: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
+    if (nt * MG_THREADS >= (1ull << 32)) return c.invalid("more than 2^36 items"); // the grid's thread count must fit 32 bits: 2^36 items
+    Layout L;
+    const auto split = L.take<uint64_t>(nt + 1), tile_off = L.take<uint64_t>(nt + 1);
+    const auto tile_kept = L.take<uint32_t>(nt);
+    const auto scan_tmp = L.bytes<uint64_t>(scan_tmp_bytes(nt));
+    const auto meta = L.take<MergeMeta>(1);
+    char *w = L.alloc(ctx);
+    if (!w) return c.nomem();
     ws->n_tiles = nt;
-    ws->split = (uint64_t *)(w + oS);
-    ws->tile_off = (uint64_t *)(w + oO);
-    ws->tile_kept = (uint32_t *)(w + oK);
-    ws->meta = (MergeMeta *)(w + oM);
-    hipError_t e = hipMemsetAsync(ws->meta, 0, sizeof(MergeMeta), st);
-    hipLaunchKernelGGL(merge_split_kernel, dim3((unsigned)((nt + 1 + 255) / 256)), dim3(256), 0, st, a.keys, a.n, b.keys, b.n, nt, ws->split);
-    hipLaunchKernelGGL(merge_tile_kernel<false>, dim3((unsigned)nt), dim3(MG_THREADS), 0, st, a.keys, a.counts, a.n, b.keys, b.counts, b.n,
+    ws->split = split(w);
+    ws->tile_off = tile_off(w);
+    ws->tile_kept = tile_kept(w);
+    ws->meta = meta(w);
+    c.zero(ws->meta, sizeof(MergeMeta));
+    hipLaunchKernelGGL(merge_split_kernel, dim3((unsigned)((nt + 1 + 255) / 256)), dim3(256), 0, c.st, a.keys, a.n, b.keys, b.n, nt, ws->split);
+    hipLaunchKernelGGL(merge_tile_kernel<false>, dim3((unsigned)nt), dim3(MG_THREADS), 0, c.st, a.keys, a.counts, a.n, b.keys, b.counts, b.n,
                        ws->split, minc, ws->tile_kept, (const uint64_t *)nullptr, ws->meta, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint64_t)0);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = launch_scan_u32(ws->tile_kept, nt, ws->tile_off, (uint64_t *)(w + oT), 0, st);
+    c.launched();
+    c.scan(ws->tile_kept, nt, ws->tile_off, scan_tmp(w));
     MergeMeta hm{};
     uint64_t kept = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&hm, ws->meta, sizeof hm, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&kept, ws->tile_off + nt, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_count_merge_device: HIP error");
-        return S2K_ERR_DEVICE;
-    }
-    if (hm.bad) {
-        ctx_set_error(ctx, "s2k_count_merge_device: an input table is not strictly ascending by key");
-        return S2K_ERR_INVALID_ARG;
-    }
+    c.fetch(&hm, ws->meta, sizeof hm);
+    c.fetch(&kept, ws->tile_off + nt, 8);
+    if (!c.sync()) return c.device_error();
+    if (hm.bad) return c.invalid("an input table is not strictly ascending by key");
     *n_distinct = hm.n_distinct;
     *n_kept = kept;
     return S2K_OK;
@@ -281,15 +243,11 @@ s2k_status merge_count(s2k_ctx *ctx, const Tab &a, const Tab &b, uint32_t minc, 
 s2k_status merge_write(s2k_ctx *ctx, const Tab &a, const Tab &b, uint32_t minc, const MergeWs &ws, uint64_t *o_keys, uint32_t *o_counts,
                        uint64_t n_kept) {
     if (ws.n_tiles == 0 || n_kept == 0 || (!o_keys && !o_counts)) return S2K_OK;
-    hipStream_t st = ctx_stream(ctx);
-    hipLaunchKernelGGL(merge_tile_kernel<true>, dim3((unsigned)ws.n_tiles), dim3(MG_THREADS), 0, st, a.keys, a.counts, a.n, b.keys, b.counts,
+    Call c(ctx, "s2k_count_merge_device");
+    hipLaunchKernelGGL(merge_tile_kernel<true>, dim3((unsigned)ws.n_tiles), dim3(MG_THREADS), 0, c.st, a.keys, a.counts, a.n, b.keys, b.counts,
                        b.n, ws.split, minc, ws.tile_kept, ws.tile_off, ws.meta, o_keys, o_counts, n_kept);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_count_merge_device: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    c.launched();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 
@@ -392,14 +350,12 @@ s2k_status counter_add_piece(s2k_counter *c, const uint64_t *d_hash, uint64_t n)
             ctx_set_error(c->ctx, "s2k_counter_add: run allocation");
             return S2K_ERR_NOMEM;
         }
-        hipStream_t st = ctx_stream(c->ctx);
-        hipError_t e = hipMemcpyAsync(r.keys, cur.keys, cur.n * 8, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(r.counts, cur.counts, cur.n * 4, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = ctx_sync(c->ctx);
-        if (e != hipSuccess) {
+        Call call(c->ctx, "s2k_counter_add");
+        call.copy(r.keys, cur.keys, cur.n * 8, hipMemcpyDeviceToDevice);
+        call.copy(r.counts, cur.counts, cur.n * 4, hipMemcpyDeviceToDevice);
+        if (!call.sync()) {
             run_free(r);
-            ctx_set_error(c->ctx, "s2k_counter_add: HIP error");
-            return S2K_ERR_DEVICE;
+            return call.device_error();
         }
         cur = r;
     }

@@ -21,6 +21,8 @@
 #include <vector>
 
 #include "../../include/s2k.h"
+#include "s2k_call.h"
+#include "s2k_compact_dev.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
 
@@ -51,30 +53,6 @@ __device__ inline uint32_t lds_slot(uint64_t k) { // the bucket's keys share the
     k ^= k >> 29;
     k *= 0xBF58476D1CE4E5B9ull;
     return (uint32_t)(k >> 52);
-}
-
-// exclusive scan over a workgroup of NW waves; *total = the sum; wsum: NW words of LDS
-template <int NW>
-__device__ inline uint32_t block_excl_scan(uint32_t x, uint32_t *wsum, uint32_t *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if (lane >= o) incl += y;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        const uint32_t v = wsum[j];
-        pre += j < w ? v : 0u;
-        tot += v;
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + incl - x;
 }
 
 // out[0..m] = exclusive prefix of f(in[0..m)), f = ceil(x / TILE) (tiles of a segment) or x; one workgroup
@@ -352,8 +330,6 @@ __global__ __launch_bounds__(256) void copy_pairs_kernel(const uint64_t *__restr
     }
 }
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 } // namespace
 } // namespace s2k
 
@@ -367,7 +343,7 @@ s2k_status s2k_count_device_ex(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n,
     *n_distinct = *n_kept = 0;
     if (n == 0) return S2K_OK;
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
+    Call c(ctx, "s2k_count_device_ex");
     const uint32_t minc = min_count ? min_count : 1u;
     const int sorted = (flags & S2K_COUNT_SORTED) ? 1 : 0;
     const bool want = d_keys || d_counts;
@@ -380,56 +356,46 @@ s2k_status s2k_count_device_ex(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n,
     while (bits2 < 10 && (n >> (8 + bits2)) > 512) bits2++;
     const uint32_t nb2 = 256u << bits2; // level-2 buckets
     const uint64_t maxchild = std::max<uint64_t>(nb2, 256 * nsegmax);
-    size_t off = 0;
-    const size_t oA = off; off += al(n * 8);
-    const size_t oB = off; off += al(n * 8);
-    const size_t oC = off; off += al(n * 4);
-    const size_t oSS = off; off += al(nsegmax * 4);
-    const size_t oSL = off; off += al(nsegmax * 4);
-    const size_t oTO = off; off += al((nsegmax + 1) * 4);
-    const size_t oCS = off; off += al(maxchild * 4);
-    const size_t oCL = off; off += al(maxchild * 4);
-    const size_t oCU = off; off += al(maxchild * 4);
-    const size_t oKE = off; off += al(maxchild * 4);
-    const size_t oDO = off; off += al((maxchild + 1) * 4);
-    const size_t oL1S = off; off += al(256 * 4);
-    const size_t oL1L = off; off += al(256 * 4);
-    const size_t oM = off; off += al(sizeof(Meta));
-    char *ws = (char *)ctx_count_table(ctx, off);
-    if (!ws) {
-        ctx_set_error(ctx, "s2k_count_device_ex: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    uint64_t *A = (uint64_t *)(ws + oA), *B = (uint64_t *)(ws + oB);
-    uint32_t *C = (uint32_t *)(ws + oC), *seg_s = (uint32_t *)(ws + oSS), *seg_l = (uint32_t *)(ws + oSL), *tile_off = (uint32_t *)(ws + oTO);
-    uint32_t *c_s = (uint32_t *)(ws + oCS), *c_l = (uint32_t *)(ws + oCL), *cur = (uint32_t *)(ws + oCU), *kept = (uint32_t *)(ws + oKE);
-    uint32_t *dst_off = (uint32_t *)(ws + oDO), *l1_s = (uint32_t *)(ws + oL1S), *l1_l = (uint32_t *)(ws + oL1L);
-    Meta *meta = (Meta *)(ws + oM);
+    Layout L;
+    const auto pA = L.take<uint64_t>(n), pB = L.take<uint64_t>(n);
+    const auto pC = L.take<uint32_t>(n);
+    const auto pSS = L.take<uint32_t>(nsegmax), pSL = L.take<uint32_t>(nsegmax), pTO = L.take<uint32_t>(nsegmax + 1);
+    const auto pCS = L.take<uint32_t>(maxchild), pCL = L.take<uint32_t>(maxchild), pCU = L.take<uint32_t>(maxchild), pKE = L.take<uint32_t>(maxchild);
+    const auto pDO = L.take<uint32_t>(maxchild + 1);
+    const auto pL1S = L.take<uint32_t>(256), pL1L = L.take<uint32_t>(256);
+    const auto pM = L.take<Meta>(1);
+    char *ws = L.alloc(ctx);
+    if (!ws) return c.nomem();
+    uint64_t *A = pA(ws), *B = pB(ws);
+    uint32_t *C = pC(ws), *seg_s = pSS(ws), *seg_l = pSL(ws), *tile_off = pTO(ws);
+    uint32_t *c_s = pCS(ws), *c_l = pCL(ws), *cur = pCU(ws), *kept = pKE(ws);
+    uint32_t *dst_off = pDO(ws), *l1_s = pL1S(ws), *l1_l = pL1L(ws);
+    Meta *meta = pM(ws);
+    hipStream_t st = c.st;
 
-    hipError_t e = hipSuccess;
     // one partition level: segments (ss, sl)[0..nseg) of src -> 256 children each (cs, cl) in dst
     auto level = [&](const uint64_t *src, uint64_t *dst, const uint32_t *ss, const uint32_t *sl, uint32_t nseg, uint64_t nkeys, int shift,
                      int bits, uint32_t *cs, uint32_t *cl) {
         const uint64_t tiles = nkeys / TILE + nseg; // bound; blocks past the real count return at once
         hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(1024), 0, st, sl, nseg, 1, tile_off);
-        if (e == hipSuccess) e = hipMemsetAsync(cl, 0, ((size_t)nseg << bits) * 4, st);
+        c.zero(cl, ((size_t)nseg << bits) * 4);
         hipLaunchKernelGGL(part_hist_tile_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, st, src, ss, sl, nseg, tile_off, shift, bits, cl);
         hipLaunchKernelGGL(part_children_kernel, dim3(nseg), dim3(256), 0, st, ss, cl, bits, cs, cur);
         hipLaunchKernelGGL(part_scatter_tile_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, st, src, ss, sl, nseg, tile_off, shift, bits, cur, dst);
-        if (e == hipSuccess) e = hipGetLastError();
+        c.launched();
     };
     auto count = [&](uint64_t *keys, uint32_t nchild) {
-        if (e == hipSuccess) e = hipMemsetAsync(&meta->n_next, 0, 4, st);
+        c.zero(&meta->n_next, 4);
         hipLaunchKernelGGL(count_bucket_kernel, dim3(nchild), dim3(CNT_THREADS), 0, st, keys, C, c_s, c_l, minc, sorted, kept, seg_s, seg_l, meta);
-        if (e == hipSuccess) e = hipGetLastError();
+        c.launched();
     };
     Meta hm{};
     auto read_meta = [&]() {
-        if (e == hipSuccess) e = hipMemcpyAsync(&hm, meta, sizeof(Meta), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = ctx_sync(ctx);
+        c.fetch(&hm, meta, sizeof(Meta));
+        c.sync();
     };
 
-    e = hipMemsetAsync(meta, 0, sizeof(Meta), st);
+    c.zero(meta, sizeof(Meta));
     hipLaunchKernelGGL(init_kernel, dim3(1), dim3(1), 0, st, seg_s, seg_l, (uint32_t)n);
     level(d_hash, B, seg_s, seg_l, 1, n, 56, 8, l1_s, l1_l);              // top byte
     level(B, A, l1_s, l1_l, 256, n, 56 - bits2, bits2, c_s, c_l);        // next bits2 bits: nb2 buckets in A
@@ -437,15 +403,15 @@ s2k_status s2k_count_device_ex(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n,
     read_meta();
 
     bool over = false;
-    if (e == hipSuccess && hm.n_next == 0) { // the usual case: every bucket fitted its LDS table
+    if (c.ok() && hm.n_next == 0) { // the usual case: every bucket fitted its LDS table
         over = hm.n_kept > capacity && want;
         if (want && !over && hm.n_kept) {
             hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(1024), 0, st, kept, nb2, 0, dst_off);
             hipLaunchKernelGGL(copy_pairs_kernel, dim3(nb2), dim3(256), 0, st, A, B, C, c_s, kept, dst_off, nullptr, d_keys, d_counts);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = ctx_sync(ctx);
+            c.launched();
+            c.sync();
         }
-    } else if (e == hipSuccess) { // re-partition the buckets that overflowed, one byte deeper per level; assemble in key order here
+    } else if (c.ok()) { // re-partition the buckets that overflowed, one byte deeper per level; assemble in key order here
         struct Fin {
             uint32_t start, len, which;
         };
@@ -454,16 +420,15 @@ s2k_status s2k_count_device_ex(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n,
         auto collect = [&](uint32_t nchild, uint32_t which) {
             hs.resize(nchild);
             hk.resize(nchild);
-            if (e == hipSuccess) e = hipMemcpyAsync(hs.data(), c_s, (size_t)nchild * 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(hk.data(), kept, (size_t)nchild * 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = ctx_sync(ctx);
-            if (e != hipSuccess) return;
+            c.fetch(hs.data(), c_s, (size_t)nchild * 4);
+            c.fetch(hk.data(), kept, (size_t)nchild * 4);
+            if (!c.sync()) return;
             for (uint32_t i = 0; i < nchild; i++)
                 if (hk[i] != KEPT_OVF && hk[i] != 0) fin.push_back({hs[i], hk[i], which});
         };
         if (want) collect(nb2, 0);
         uint64_t *src = A, *dst = B; // level L >= 3 reads what level L-1 wrote and writes the other array
-        for (int shift = 56 - bits2; shift > 0 && e == hipSuccess && hm.n_next;) {
+        for (int shift = 56 - bits2; shift > 0 && c.ok() && hm.n_next;) {
             const int bits = std::min(8, shift);
             shift -= bits;
             const uint32_t nseg = hm.n_next;
@@ -473,9 +438,9 @@ s2k_status s2k_count_device_ex(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n,
             if (want) collect(nseg << bits, dst == B ? 1u : 0u);
             std::swap(src, dst);
         }
-        if (e == hipSuccess && hm.n_next) e = hipErrorUnknown; // cannot happen: a last-level bucket has one distinct key
+        if (c.ok() && hm.n_next) c.e = hipErrorUnknown; // cannot happen: a last-level bucket has one distinct key
         over = hm.n_kept > capacity && want;
-        if (e == hipSuccess && want && !over && !fin.empty()) {
+        if (c.ok() && want && !over && !fin.empty()) {
             std::sort(fin.begin(), fin.end(), [](const Fin &a, const Fin &b) { return a.start < b.start; });
             std::vector<uint32_t> fs(fin.size()), fl(fin.size()), fd(fin.size()), fw(fin.size());
             uint32_t acc = 0;
@@ -486,24 +451,21 @@ s2k_status s2k_count_device_ex(s2k_ctx *ctx, const uint64_t *d_hash, uint64_t n,
                 fd[i] = acc;
                 acc += fin[i].len;
             }
-            for (size_t b0 = 0; b0 < fin.size() && e == hipSuccess; b0 += maxchild) { // the child arrays carry the list, in chunks
+            for (size_t b0 = 0; b0 < fin.size() && c.ok(); b0 += maxchild) { // the child arrays carry the list, in chunks
                 const size_t m = std::min<size_t>(maxchild, fin.size() - b0);
-                e = hipMemcpyAsync(c_s, fs.data() + b0, m * 4, hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) e = hipMemcpyAsync(c_l, fl.data() + b0, m * 4, hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) e = hipMemcpyAsync(kept, fd.data() + b0, m * 4, hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) e = hipMemcpyAsync(cur, fw.data() + b0, m * 4, hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) {
+                c.copy(c_s, fs.data() + b0, m * 4, hipMemcpyHostToDevice);
+                c.copy(c_l, fl.data() + b0, m * 4, hipMemcpyHostToDevice);
+                c.copy(kept, fd.data() + b0, m * 4, hipMemcpyHostToDevice);
+                c.copy(cur, fw.data() + b0, m * 4, hipMemcpyHostToDevice);
+                if (c.ok()) {
                     hipLaunchKernelGGL(copy_pairs_kernel, dim3((unsigned)m), dim3(256), 0, st, A, B, C, c_s, c_l, kept, cur, d_keys, d_counts);
-                    e = hipGetLastError();
+                    c.launched();
                 }
-                if (e == hipSuccess) e = ctx_sync(ctx); // the host lists are read by the copies: keep them until done
+                c.sync(); // the host lists are read by the copies: keep them until done
             }
         }
     }
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_count_device_ex: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    if (!c.ok()) return c.device_error();
     *n_distinct = hm.n_distinct;
     *n_kept = hm.n_kept;
     return over ? S2K_ERR_CAPACITY : S2K_OK;

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "../../include/s2k.h"
+#include "s2k_call.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
 
@@ -46,49 +47,24 @@ extern "C" {
 s2k_status s2k_graph_adjacency(s2k_ctx *ctx, const uint64_t *d_edge_keys, uint64_t n_edges, uint64_t n_nodes, uint64_t *d_row_off,
                                uint32_t *d_dst) {
     if (!ctx || !d_row_off || (n_edges && !d_edge_keys)) return S2K_ERR_INVALID_ARG;
-    if (n_nodes >= (1ull << 31)) {
-        ctx_set_error(ctx, "s2k_graph_adjacency: 2^31 nodes or more (oriented node ids are 32-bit)");
-        return S2K_ERR_INVALID_ARG;
-    }
+    Call c(ctx, "s2k_graph_adjacency");
+    if (n_nodes >= (1ull << 31)) return c.invalid("2^31 nodes or more (oriented node ids are 32-bit)");
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
     const uint64_t n_ids = 2 * n_nodes;
-    hipError_t e = hipSuccess;
     if (n_edges) {
         uint32_t *bad = (uint32_t *)ctx_count_table(ctx, 4);
-        if (!bad) {
-            ctx_set_error(ctx, "s2k_graph_adjacency: workspace allocation");
-            return S2K_ERR_NOMEM;
-        }
-        uint32_t hbad = 0;
-        e = hipMemsetAsync(bad, 0, 4, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(adj_check_kernel, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, st, d_edge_keys, n_edges, n_ids, bad);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = ctx_sync(ctx);
-        if (e != hipSuccess) {
-            ctx_set_error(ctx, "s2k_graph_adjacency: HIP error");
-            return S2K_ERR_DEVICE;
-        }
-        if (hbad) {
-            ctx_set_error(ctx, "s2k_graph_adjacency: the keys are not strictly ascending or name a node id >= 2 * n_nodes");
-            return S2K_ERR_INVALID_ARG;
-        }
+        if (!bad) return c.nomem();
+        const uint32_t hbad = c.check(bad, 4, bad, [&] {
+            hipLaunchKernelGGL(adj_check_kernel, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, c.st, d_edge_keys, n_edges, n_ids, bad);
+        });
+        if (!c.ok()) return c.device_error();
+        if (hbad) return c.invalid("the keys are not strictly ascending or name a node id >= 2 * n_nodes");
     }
     const uint64_t lanes = std::max<uint64_t>(n_edges, n_ids + 1);
-    if ((lanes + 255) / 256 >= (1ull << 32)) {
-        ctx_set_error(ctx, "s2k_graph_adjacency: too many edges for one call");
-        return S2K_ERR_INVALID_ARG;
-    }
-    hipLaunchKernelGGL(adj_write_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, d_edge_keys, n_edges, n_ids, d_row_off, d_dst);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_graph_adjacency: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    if ((lanes + 255) / 256 >= (1ull << 32)) return c.invalid("too many edges for one call");
+    hipLaunchKernelGGL(adj_write_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, c.st, d_edge_keys, n_edges, n_ids, d_row_off, d_dst);
+    c.launched();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 

@@ -35,6 +35,7 @@
 #include <algorithm>
 
 #include "../../include/s2k.h"
+#include "s2k_call.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
 #include "s2k_table_dev.h"
@@ -45,18 +46,6 @@ namespace {
 constexpr uint32_t SQ_NONE = 0xFFFFFFFFu;
 constexpr int SQ_T = 256;
 constexpr uint64_t B01 = 0x0101010101010101ull;
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the last read r in [lo, hi] with km_off[r] <= j (km_off[lo] <= j holds)
-__device__ inline uint64_t read_of(const uint64_t *__restrict__ km_off, uint64_t lo, uint64_t hi, uint64_t j) {
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (km_off[mid] <= j) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 // ---- 16 bytes in two registers pairs --------------------------------------------------------------------------------------------
 // bytes [p, p + 16) of memory in (lo, hi), little endian, of which the first n (1 .. 16) are wanted: only the aligned 8-byte words
@@ -364,22 +353,6 @@ __global__ __launch_bounds__(SQ_T) void stitch_kernel(const uint32_t *__restrict
         for (uint32_t x = 0; x < want; x++) o[x] = (uint8_t)((x < 8 ? lo >> (8 * x) : hi >> (8 * (x - 8))) & 0xFFu);
 }
 
-struct Ends {
-    uint64_t km0, n_items, mn0, n_triples;
-};
-// km_off[0], km_off[n_reads], mn_off[0], mn_off[n_reads] (mn_off may be NULL: zeros)
-hipError_t read_ends(s2k_ctx *ctx, const s2k_device_out *in, uint64_t n_reads, Ends *e) {
-    hipStream_t st = ctx_stream(ctx);
-    *e = Ends{0, 0, 0, 0};
-    S2K_HIP_CHECK(hipMemcpyAsync(&e->km0, in->km_off, 8, hipMemcpyDeviceToHost, st));
-    S2K_HIP_CHECK(hipMemcpyAsync(&e->n_items, in->km_off + n_reads, 8, hipMemcpyDeviceToHost, st));
-    if (in->mn_off) {
-        S2K_HIP_CHECK(hipMemcpyAsync(&e->mn0, in->mn_off, 8, hipMemcpyDeviceToHost, st));
-        S2K_HIP_CHECK(hipMemcpyAsync(&e->n_triples, in->mn_off + n_reads, 8, hipMemcpyDeviceToHost, st));
-    }
-    return ctx_sync(ctx);
-}
-
 } // namespace
 } // namespace s2k
 
@@ -389,31 +362,19 @@ extern "C" {
 
 s2k_status s2k_table_representatives(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint64_t ordinal_base, uint64_t *d_rep) {
     if (!t || !in || !in->km_off || !in->hash || (t->n && !d_rep)) return S2K_ERR_INVALID_ARG;
-    s2k_ctx *ctx = t->ctx;
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    Ends ends;
-    if (read_ends(ctx, in, n_reads, &ends) != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_representatives: HIP error");
-        return S2K_ERR_DEVICE;
-    }
-    if (ends.km0 != 0 || ordinal_base + ends.n_items < ordinal_base) {
-        ctx_set_error(ctx, "s2k_table_representatives: in->km_off must start at 0, and the ordinals must fit 64 bits");
-        return S2K_ERR_INVALID_ARG;
-    }
+    if (hipSetDevice(ctx_device(t->ctx)) != hipSuccess) return S2K_ERR_DEVICE;
+    Call c(t->ctx, "s2k_table_representatives");
+    const Ends ends = read_ends(c, in->km_off, in->mn_off, n_reads);
+    if (!c.ok()) return c.device_error();
+    if (ends.km0 != 0 || ordinal_base + ends.n_items < ordinal_base)
+        return c.invalid("in->km_off must start at 0, and the ordinals must fit 64 bits");
     if (ends.n_items == 0 || t->n == 0) return S2K_OK;
     const uint64_t nt = (ends.n_items + TB_TILE - 1) / TB_TILE;
-    if (nt >= (1ull << 32)) {
-        ctx_set_error(ctx, "s2k_table_representatives: too many items for one call");
-        return S2K_ERR_INVALID_ARG;
-    }
-    hipLaunchKernelGGL(rep_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, ctx_stream(ctx), t->view(), in->hash, ends.n_items, ordinal_base,
+    if (nt >= (1ull << 32)) return c.invalid("too many items for one call");
+    hipLaunchKernelGGL(rep_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, t->view(), in->hash, ends.n_items, ordinal_base,
                        (unsigned long long *)d_rep);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_representatives: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    c.launched();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 
@@ -424,91 +385,59 @@ s2k_status s2k_table_node_sequences(s2k_table *t, uint64_t n_reads, const s2k_de
     if (!t || !in || !n_bytes || !in->km_off || !in->hash || !in->rev || !in->mn_off || !in->mn_j || !in->mn_jend || !d_read_off ||
         (t->n && !d_rep))
         return S2K_ERR_INVALID_ARG;
-    s2k_ctx *ctx = t->ctx;
+    Call c(t->ctx, "s2k_table_node_sequences");
     const bool want = nodes && nodes->pool;
     if (want && (!nodes->seq_off || !nodes->seq_len || !nodes->shift_fwd || !nodes->shift_rev || !nodes->rev)) return S2K_ERR_INVALID_ARG;
-    if (k < 2 || k > 4096) {
-        ctx_set_error(ctx, "s2k_table_node_sequences: k < 2 (a node has no second minimizer) or k > 4096");
-        return S2K_ERR_INVALID_ARG;
-    }
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
-    const char *fail = "s2k_table_node_sequences: HIP error";
-#define SEQ_FAIL()                \
-    do {                          \
-        ctx_set_error(ctx, fail); \
-        return S2K_ERR_DEVICE;    \
-    } while (0)
-    Ends ends;
-    if (read_ends(ctx, in, n_reads, &ends) != hipSuccess) SEQ_FAIL();
-    if (ends.km0 != 0 || ends.mn0 != 0 || ends.n_triples > in->mn_capacity || ordinal_base + ends.n_items < ordinal_base) {
-        ctx_set_error(ctx, "s2k_table_node_sequences: km_off and mn_off must start at 0, and mn_capacity must cover mn_off[n_reads]");
-        return S2K_ERR_INVALID_ARG;
-    }
+    if (k < 2 || k > 4096) return c.invalid("k < 2 (a node has no second minimizer) or k > 4096");
+    if (hipSetDevice(ctx_device(t->ctx)) != hipSuccess) return S2K_ERR_DEVICE;
+    const Ends ends = read_ends(c, in->km_off, in->mn_off, n_reads);
+    if (!c.ok()) return c.device_error();
+    if (ends.km0 != 0 || ends.mn0 != 0 || ends.n_triples > in->mn_capacity || ordinal_base + ends.n_items < ordinal_base)
+        return c.invalid("km_off and mn_off must start at 0, and mn_capacity must cover mn_off[n_reads]");
     const uint64_t n_items = ends.n_items;
     const uint64_t nt = (n_items + TB_TILE - 1) / TB_TILE;
-    if (nt >= (1ull << 32) || n_reads >= (1ull << 40)) {
-        ctx_set_error(ctx, "s2k_table_node_sequences: too many items for one call");
-        return S2K_ERR_INVALID_ARG;
-    }
+    if (nt >= (1ull << 32) || n_reads >= (1ull << 40)) return c.invalid("too many items for one call");
     if (n_reads == 0) return S2K_OK;
-    size_t off = 0;
-    const size_t oB = off; off += al(16);
-    const size_t oL = off; off += al(n_items * 4);
-    const size_t oN = off; off += al(n_items * 4);
-    const size_t oO = off; off += al((n_items + 1) * 8);
-    const size_t oT = off; off += al(scan_tmp_bytes(n_items));
-    char *w = (char *)ctx_count_table(ctx, off);
-    if (!w) {
-        ctx_set_error(ctx, "s2k_table_node_sequences: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    uint32_t *bad = (uint32_t *)(w + oB), *len = (uint32_t *)(w + oL), *node = (uint32_t *)(w + oN);
-    uint64_t *item_off = (uint64_t *)(w + oO);
+    Layout L;
+    const auto flag = L.bytes<uint32_t>(16);
+    const auto len_p = L.take<uint32_t>(n_items), node_p = L.take<uint32_t>(n_items);
+    const auto off_p = L.take<uint64_t>(n_items + 1);
+    const auto tmp_p = L.bytes<uint64_t>(scan_tmp_bytes(n_items));
+    char *w = L.alloc(t->ctx);
+    if (!w) return c.nomem();
+    uint32_t *bad = flag(w), *len = len_p(w), *node = node_p(w);
+    uint64_t *item_off = off_p(w);
     const SeqIn si{in->km_off, in->hash, in->mn_off, in->mn_j, in->mn_jend, in->rev, d_read_off, n_reads, n_items, k};
     // 1. the count relation of every read, before a triple is indexed through it
-    uint32_t hbad = 0;
-    hipError_t e = hipMemsetAsync(bad, 0, 16, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(nodeseq_reads_kernel, dim3((unsigned)((n_reads + SQ_T - 1) / SQ_T)), dim3(SQ_T), 0, st, si, bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) SEQ_FAIL();
-    if (hbad) {
-        ctx_set_error(ctx, "s2k_table_node_sequences: a read with n > 0 items must have n + k - 1 minimizer triples (a wrong k, or triples of "
-                           "another call), and km_off / mn_off / read_off must not decrease");
-        return S2K_ERR_INVALID_ARG;
-    }
+    uint32_t hbad = c.check(bad, 16, bad, [&] {
+        hipLaunchKernelGGL(nodeseq_reads_kernel, dim3((unsigned)((n_reads + SQ_T - 1) / SQ_T)), dim3(SQ_T), 0, c.st, si, bad);
+    });
+    if (!c.ok()) return c.device_error();
+    if (hbad)
+        return c.invalid("a read with n > 0 items must have n + k - 1 minimizer triples (a wrong k, or triples of another call), and km_off / "
+                         "mn_off / read_off must not decrease");
     if (n_items == 0 || t->n == 0) return S2K_OK;
     // 2. lengths, 3. offsets
-    hipLaunchKernelGGL(nodeseq_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, t->view(), si, ordinal_base, (const unsigned long long *)d_rep,
-                       len, node, bad);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = launch_scan_u32(len, n_items, item_off, (uint64_t *)(w + oT), 0, st);
+    hipLaunchKernelGGL(nodeseq_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, t->view(), si, ordinal_base,
+                       (const unsigned long long *)d_rep, len, node, bad);
+    c.launched();
+    c.scan(len, n_items, item_off, tmp_p(w));
     uint64_t total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, item_off + n_items, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) SEQ_FAIL();
-    if (hbad) {
-        ctx_set_error(ctx, "s2k_table_node_sequences: a minimizer position lies outside its read or out of order");
-        return S2K_ERR_INVALID_ARG;
-    }
+    c.fetch(&total, item_off + n_items, 8);
+    c.fetch(&hbad, bad, 4);
+    if (!c.sync()) return c.device_error();
+    if (hbad) return c.invalid("a minimizer position lies outside its read or out of order");
     *n_bytes = total;
     if (!want || total == 0) return S2K_OK;
     if (pool_used > nodes->pool_capacity || total > nodes->pool_capacity - pool_used) return S2K_ERR_CAPACITY;
     if (!d_bases) return S2K_ERR_INVALID_ARG;
     // 4. records and bytes
     const NodeOut no{nodes->seq_off, nodes->seq_len, nodes->shift_fwd, nodes->shift_rev, nodes->rev, nodes->pool};
-    hipLaunchKernelGGL(nodeseq_write_kernel, dim3((unsigned)((n_items + SQ_T - 1) / SQ_T)), dim3(SQ_T), 0, st, si, d_bases, len, node, item_off, pool_used,
-                       no);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) SEQ_FAIL();
+    hipLaunchKernelGGL(nodeseq_write_kernel, dim3((unsigned)((n_items + SQ_T - 1) / SQ_T)), dim3(SQ_T), 0, c.st, si, d_bases, len, node, item_off,
+                       pool_used, no);
+    c.launched();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
-#undef SEQ_FAIL
 }
 
 s2k_status s2k_unitig_sequences(s2k_ctx *ctx, const uint64_t *d_uni_off, const uint32_t *d_members, const uint8_t *d_circular, uint64_t n_unitigs,
@@ -518,88 +447,60 @@ s2k_status s2k_unitig_sequences(s2k_ctx *ctx, const uint64_t *d_uni_off, const u
     if (!ctx || !n_bases || !d_uni_off || !nodes) return S2K_ERR_INVALID_ARG;
     if (n_unitigs && (!d_members || !d_circular || !nodes->seq_off || !nodes->seq_len || !nodes->shift_fwd || !nodes->shift_rev || !nodes->rev))
         return S2K_ERR_INVALID_ARG;
-    if (n_nodes >= (1ull << 31) || n_unitigs > n_nodes || ((uint64_t)d_out & 15u)) {
-        ctx_set_error(ctx, "s2k_unitig_sequences: 2^31 nodes or more, more unitigs than nodes, or d_out not 16-byte aligned");
-        return S2K_ERR_INVALID_ARG;
-    }
+    Call c(ctx, "s2k_unitig_sequences");
+    if (n_nodes >= (1ull << 31) || n_unitigs > n_nodes || ((uint64_t)d_out & 15u))
+        return c.invalid("2^31 nodes or more, more unitigs than nodes, or d_out not 16-byte aligned");
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
-    const char *fail = "s2k_unitig_sequences: HIP error";
-#define SEQ_FAIL()                \
-    do {                          \
-        ctx_set_error(ctx, fail); \
-        return S2K_ERR_DEVICE;    \
-    } while (0)
-    hipError_t e = hipSuccess;
     if (n_unitigs == 0) { // no unitigs: no nodes
         uint64_t first = 1;
-        e = hipMemcpyAsync(&first, d_uni_off, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = ctx_sync(ctx);
-        if (e != hipSuccess) SEQ_FAIL();
-        if (first != 0 || n_nodes != 0) {
-            ctx_set_error(ctx, "s2k_unitig_sequences: uni_off must start at 0 and end at n_nodes");
-            return S2K_ERR_INVALID_ARG;
-        }
+        c.fetch(&first, d_uni_off, 8);
+        if (!c.sync()) return c.device_error();
+        if (first != 0 || n_nodes != 0) return c.invalid("uni_off must start at 0 and end at n_nodes");
         if (d_out_off) {
-            e = hipMemsetAsync(d_out_off, 0, 8, st);
-            if (e == hipSuccess) e = ctx_sync(ctx);
-            if (e != hipSuccess) SEQ_FAIL();
+            c.zero(d_out_off, 8);
+            if (!c.sync()) return c.device_error();
         }
         return S2K_OK;
     }
     const uint64_t n_members = n_nodes;
-    size_t off = 0;
-    const size_t oB = off; off += al(16);
-    const size_t oL = off; off += al(n_members * 4);
-    const size_t oO = off; off += al((n_members + 1) * 8);
-    const size_t oT = off; off += al(scan_tmp_bytes(n_members));
-    char *w = (char *)ctx_count_table(ctx, off);
-    if (!w) {
-        ctx_set_error(ctx, "s2k_unitig_sequences: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    uint32_t *bad = (uint32_t *)(w + oB), *len = (uint32_t *)(w + oL);
-    uint64_t *piece_off = (uint64_t *)(w + oO);
+    Layout L;
+    const auto flag = L.bytes<uint32_t>(16);
+    const auto len_p = L.take<uint32_t>(n_members);
+    const auto off_p = L.take<uint64_t>(n_members + 1);
+    const auto tmp_p = L.bytes<uint64_t>(scan_tmp_bytes(n_members));
+    char *w = L.alloc(ctx);
+    if (!w) return c.nomem();
+    uint32_t *bad = flag(w), *len = len_p(w);
+    uint64_t *piece_off = off_p(w);
     const NodeView nv{nodes->seq_off, nodes->seq_len, nodes->shift_fwd, nodes->shift_rev, nodes->rev, nodes->pool, nodes->pool_capacity, n_nodes};
     const unsigned gm = (unsigned)((n_members + SQ_T - 1) / SQ_T), gu = (unsigned)((n_unitigs + 1 + SQ_T - 1) / SQ_T);
-    e = hipMemsetAsync(bad, 0, 16, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(piece_len_kernel, dim3(gm), dim3(SQ_T), 0, st, d_members, n_members, nv, len, bad);
-        hipLaunchKernelGGL(unitig_last_kernel, dim3(gu), dim3(SQ_T), 0, st, d_uni_off, d_members, d_circular, n_unitigs, n_members, nv, len, bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = launch_scan_u32(len, n_members, piece_off, (uint64_t *)(w + oT), 0, st);
     uint64_t total = 0;
-    uint32_t hbad = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, piece_off + n_members, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) SEQ_FAIL();
-    if (hbad) {
-        ctx_set_error(ctx, "s2k_unitig_sequences: uni_off is not the offsets of n_unitigs non-empty unitigs over n_nodes members, a member names a "
-                           "node >= n_nodes, or a node record is inconsistent (rev > 1, a shift above seq_len, bytes outside the pool)");
-        return S2K_ERR_INVALID_ARG;
-    }
+    const uint32_t hbad = c.check(bad, 16, bad, [&] {
+        hipLaunchKernelGGL(piece_len_kernel, dim3(gm), dim3(SQ_T), 0, c.st, d_members, n_members, nv, len, bad);
+        hipLaunchKernelGGL(unitig_last_kernel, dim3(gu), dim3(SQ_T), 0, c.st, d_uni_off, d_members, d_circular, n_unitigs, n_members, nv, len, bad);
+        c.launched();
+        c.scan(len, n_members, piece_off, tmp_p(w));
+        c.fetch(&total, piece_off + n_members, 8);
+    });
+    if (!c.ok()) return c.device_error();
+    if (hbad)
+        return c.invalid("uni_off is not the offsets of n_unitigs non-empty unitigs over n_nodes members, a member names a node >= n_nodes, or a "
+                         "node record is inconsistent (rev > 1, a shift above seq_len, bytes outside the pool)");
     *n_bases = total;
     if (d_out && total > capacity) return S2K_ERR_CAPACITY;
     if (d_out && total && !nodes->pool) return S2K_ERR_INVALID_ARG;
     if (d_out_off || d_overlap) {
-        hipLaunchKernelGGL(unitig_off_kernel, dim3(gu), dim3(SQ_T), 0, st, d_uni_off, d_members, n_unitigs, nv, piece_off, d_out_off, d_overlap);
-        e = hipGetLastError();
+        hipLaunchKernelGGL(unitig_off_kernel, dim3(gu), dim3(SQ_T), 0, c.st, d_uni_off, d_members, n_unitigs, nv, piece_off, d_out_off, d_overlap);
+        c.launched();
     }
-    if (e == hipSuccess && d_out && total) {
+    if (c.ok() && d_out && total) {
         const uint64_t nb = (total + SQ_T * 16 - 1) / (SQ_T * 16);
-        if (nb >= (1ull << 31)) {
-            ctx_set_error(ctx, "s2k_unitig_sequences: 2^43 bases or more");
-            return S2K_ERR_INVALID_ARG;
-        }
-        hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)nb), dim3(SQ_T), 0, st, d_members, n_members, piece_off, nv, d_out, total);
-        e = hipGetLastError();
+        if (nb >= (1ull << 31)) return c.invalid("2^43 bases or more");
+        hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)nb), dim3(SQ_T), 0, c.st, d_members, n_members, piece_off, nv, d_out, total);
+        c.launched();
     }
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) SEQ_FAIL();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
-#undef SEQ_FAIL
 }
 
 } // extern "C"

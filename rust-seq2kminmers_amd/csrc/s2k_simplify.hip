@@ -10,8 +10,8 @@
 //     the even lane writes remove[t].  The three totals: a block sum, then one integer atomic per block on a workspace word.
 //     "W beats U" compares cnt[W] * len[U] with cnt[U] * len[W] as 128-bit products (__umul64hi and the low product).
 //
-// s2k_graph_induced, the stable stream compaction of s2k_table.hip applied to two streams, tiles of TB_TILE items (lane tid holds
-// items r * 256 + tid):
+// s2k_graph_induced, the stable stream compaction of s2k_compact_dev.h applied to two streams, tiles of TB_TILE items (lane tid
+// holds items r * 256 + tid):
 //  1. node_count_kernel: keep[i] from d_node_keep, or gathered as !remove[node_unitig[i]]; per 64 nodes the kept mask (one wave's
 //     ballot) and the kept nodes before that word inside its tile; per tile the kept total.
 //  2. edge_count_kernel: an edge is kept iff the kept bits of both its nodes are set (two gathers from the node masks, 1 bit per
@@ -29,19 +29,14 @@
 #include <algorithm>
 
 #include "../../include/s2k.h"
+#include "s2k_call.h"
+#include "s2k_compact_dev.h"
 #include "s2k_dev.h"
+#include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
-#include "s2k_table_dev.h"
 
 namespace s2k {
 namespace {
-
-constexpr uint32_t NONE = 0xFFFFFFFFu;
-constexpr int UT = 256;           // threads per block of the mask call
-constexpr unsigned UB_MAX = 4096; // blocks of a grid-stride launch (one counter atomic per block and total)
-
-__host__ inline unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>((n + UT - 1) / UT, UB_MAX); }
-size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- the mask ---------------------------------------------------------------------------------------------------------------------
 struct UGraph {
@@ -103,8 +98,8 @@ __global__ __launch_bounds__(UT) void simplify_check_kernel(const uint64_t *__re
     bool ok = true;
     for (uint64_t u = (uint64_t)blockIdx.x * UT + threadIdx.x; u < n_ids; u += (uint64_t)gridDim.x * UT) {
         if (!(u & 1) && uni_off[u >> 1] >= uni_off[(u >> 1) + 1]) ok = false;
-        const uint64_t a = row_off[u], b = row_off[u + 1];
-        if ((u == 0 && a != 0) || (u == n_ids - 1 && b != n_edges) || a > b || b > n_edges) {
+        uint64_t a, b;
+        if (!csr_row_ok(row_off, u, n_ids, n_edges, &a, &b)) {
             ok = false;
             continue;
         }
@@ -114,61 +109,25 @@ __global__ __launch_bounds__(UT) void simplify_check_kernel(const uint64_t *__re
     if (!ok) atomicOr(bad, 1u);
 }
 
-// the sums of a, b and c over the block, each added to its word by one lane (nothing when it is 0)
-__device__ __forceinline__ void block_add3(uint32_t a, uint32_t b, uint32_t c, unsigned long long *words) {
-    __shared__ uint32_t part[UT / 64][3];
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_down(a, o, 64);
-        b += __shfl_down(b, o, 64);
-        c += __shfl_down(c, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][0] = a, part[threadIdx.x >> 6][1] = b, part[threadIdx.x >> 6][2] = c;
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        unsigned long long s = 0;
-        for (int w = 0; w < UT / 64; w++) s += part[w][threadIdx.x];
-        if (s) atomicAdd(words + threadIdx.x, s);
-    }
-}
-
 __global__ __launch_bounds__(UT) void simplify_mask_kernel(UGraph g, uint64_t n_ids, uint8_t *__restrict__ remove,
                                                            unsigned long long *__restrict__ totals /* tips, bubbles, removed */) {
-    uint32_t tips = 0, bubbles = 0, removed = 0;
+    uint32_t n[3] = {0, 0, 0}; // tips, bubbles, removed
     // n_ids is even and the stride a multiple of 64: lanes 2 j and 2 j + 1 of a wave hold U and U ^ 1, both in range or neither
     for (uint64_t u = (uint64_t)blockIdx.x * UT + threadIdx.x; u < n_ids; u += (uint64_t)gridDim.x * UT) {
         const uint32_t U = (uint32_t)u;
         uint32_t f = (removable_tip(g, U) ? 1u : 0u) | (removable_bubble(g, U) ? 2u : 0u);
         f |= __shfl_xor(f, 1, 64); // the verdict on the unitig: either strand
         if (!(U & 1u)) {
-            tips += f & 1u;
-            bubbles += (f >> 1) & 1u;
-            removed += f != 0;
+            n[0] += f & 1u;
+            n[1] += (f >> 1) & 1u;
+            n[2] += f != 0;
             if (remove) remove[U >> 1] = f != 0;
         }
     }
-    block_add3(tips, bubbles, removed, totals);
+    block_add(n, totals);
 }
 
 // ---- the induced subgraph: two stable stream compactions ---------------------------------------------------------------------------
-struct CompactWs {
-    uint64_t *wmask;     // per 64 items: kept mask
-    uint32_t *wpre;      // per 64 items: kept items before the word inside its tile
-    uint32_t *tile_kept; // per tile
-    uint64_t *tile_off;  // n_tiles + 1
-};
-
-// after the TB_Q ballots of a tile (wc[r * 4 + wave] = the popcount of that word): the words' prefixes and the tile's total
-__device__ __forceinline__ void tile_prefixes(const uint32_t *wc, uint64_t t0, uint64_t n_items, const CompactWs &ws) {
-    const int tid = threadIdx.x;
-    if (tid < TB_WORDS) { // word k of the tile = items t0 + 64 k ..: r = k / 4, wave k % 4
-        uint32_t pre = 0;
-        for (int x = 0; x < tid; x++) pre += wc[x];
-        const uint64_t w0 = t0 + (uint64_t)tid * 64;
-        if (w0 < n_items) ws.wpre[w0 >> 6] = pre;
-        if (tid == TB_WORDS - 1) ws.tile_kept[blockIdx.x] = pre + wc[tid];
-    }
-}
-
 __global__ __launch_bounds__(TB_THREADS) void node_count_kernel(const uint8_t *__restrict__ keep, const uint32_t *__restrict__ node_unitig,
                                                                 const uint8_t *__restrict__ remove, uint64_t n_unitigs, uint64_t n_nodes,
                                                                 CompactWs ws, uint32_t *__restrict__ bad) {
@@ -230,43 +189,6 @@ __global__ __launch_bounds__(TB_THREADS) void edge_count_kernel(const uint64_t *
     __syncthreads();
     tile_prefixes(wc, t0, n_edges, ws);
 }
-
-// the tile-relative slot of each of the lane's TB_Q items -> the bits of those that are kept
-__device__ __forceinline__ uint32_t tile_slots(const CompactWs &ws, uint64_t t0, uint64_t n_items, uint32_t slot[TB_Q]) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t keep = 0;
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) {
-        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
-        const uint64_t m = w0 < n_items ? ws.wmask[w0 >> 6] : 0ull;
-        const uint32_t pre = w0 < n_items ? ws.wpre[w0 >> 6] : 0u;
-        slot[r] = pre + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        keep |= (uint32_t)((m >> lane) & 1ull) << r;
-    }
-    return keep;
-}
-
-// elements between p and the 16-byte boundary below it
-template <typename T>
-__device__ __forceinline__ uint32_t shift_of(const T *p) {
-    return (uint32_t)(((uintptr_t)p & 15u) / sizeof(T));
-}
-
-// lds[shift .. shift + tot) -> out[0 .. tot), out = the run's first output address and shift = shift_of(out): whole 16-byte pieces
-// where a piece lies inside the run, element by element at the two ends.  Ends with a barrier: lds may be staged again.
-template <typename T>
-__device__ __forceinline__ void leave_run(T *__restrict__ out, const T *lds, uint32_t shift, uint32_t tot) {
-    constexpr uint32_t V = 16 / sizeof(T);
-    const uint32_t lo = shift, hi = shift + tot;
-    const uint32_t vlo = std::min((lo + V - 1) & ~(V - 1), hi), vhi = std::max(hi & ~(V - 1), vlo);
-    T *o = out - shift; // o[i] <-> lds[i]; o + vlo is 16-byte aligned
-    for (uint32_t i = lo + threadIdx.x; i < vlo; i += TB_THREADS) o[i] = lds[i];
-    for (uint32_t i = vlo / V + threadIdx.x; i < vhi / V; i += TB_THREADS) ((uint4 *)o)[i] = ((const uint4 *)lds)[i];
-    for (uint32_t i = vhi + threadIdx.x; i < hi; i += TB_THREADS) o[i] = lds[i];
-    __syncthreads();
-}
-
-constexpr uint32_t STAGE_PAD = 2; // a run starts at most 15 bytes into its first 16-byte piece: one more 8-byte element, rounded up
 
 __global__ __launch_bounds__(TB_THREADS) void node_write_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ counts, uint64_t n_nodes,
                                                                 CompactWs ws, uint32_t *__restrict__ new_id, uint64_t *__restrict__ o_keys,
@@ -344,22 +266,6 @@ __global__ __launch_bounds__(TB_THREADS) void edge_write_kernel(const uint64_t *
     }
 }
 
-size_t carve_bytes(uint64_t n, uint64_t n_tiles) {
-    const uint64_t words = (n + 63) / 64;
-    return al(words * 8) + al(words * 4) + al(n_tiles * 4) + al((n_tiles + 1) * 8) + al(scan_tmp_bytes(n_tiles));
-}
-// the workspace of one stream of n items (carve_bytes) at w + *off; *off moves past it
-CompactWs carve(char *w, size_t *off, uint64_t n, uint64_t n_tiles, uint64_t **scan_tmp) {
-    CompactWs ws;
-    const uint64_t words = (n + 63) / 64;
-    ws.wmask = (uint64_t *)(w + *off), *off += al(words * 8);
-    ws.wpre = (uint32_t *)(w + *off), *off += al(words * 4);
-    ws.tile_kept = (uint32_t *)(w + *off), *off += al(n_tiles * 4);
-    ws.tile_off = (uint64_t *)(w + *off), *off += al((n_tiles + 1) * 8);
-    *scan_tmp = (uint64_t *)(w + *off), *off += al(scan_tmp_bytes(n_tiles));
-    return ws;
-}
-
 } // namespace
 } // namespace s2k
 
@@ -374,54 +280,30 @@ s2k_status s2k_graph_simplify_mask(s2k_ctx *ctx, const uint64_t *d_row_off, cons
     if (n_bubbles) *n_bubbles = 0;
     if (n_removed) *n_removed = 0;
     if (!ctx || !n_tips || !n_bubbles || !n_removed) return S2K_ERR_INVALID_ARG;
-    if (n_unitigs >= (1ull << 31) || n_edges >= (1ull << 40)) {
-        ctx_set_error(ctx, "s2k_graph_simplify_mask: 2^31 unitigs or more (oriented ids are 32-bit), or 2^40 edges or more");
-        return S2K_ERR_INVALID_ARG;
-    }
-    if (n_unitigs == 0) {
-        if (n_edges == 0) return S2K_OK;
-        ctx_set_error(ctx, "s2k_graph_simplify_mask: edges without unitigs");
-        return S2K_ERR_INVALID_ARG;
-    }
+    Call c(ctx, "s2k_graph_simplify_mask");
+    if (n_unitigs >= (1ull << 31) || n_edges >= (1ull << 40))
+        return c.invalid("2^31 unitigs or more (oriented ids are 32-bit), or 2^40 edges or more");
+    if (n_unitigs == 0) return n_edges == 0 ? S2K_OK : c.invalid("edges without unitigs");
     if (!d_row_off || !d_uni_off || !d_uni_count || (n_edges && !d_dst)) return S2K_ERR_INVALID_ARG;
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
     unsigned long long *w = (unsigned long long *)ctx_count_table(ctx, 256);
-    if (!w) {
-        ctx_set_error(ctx, "s2k_graph_simplify_mask: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
+    if (!w) return c.nomem();
     unsigned long long *totals = w; // tips, bubbles, removed; then the check's flag
     uint32_t *bad = (uint32_t *)(w + 3);
     const uint64_t n_ids = 2 * n_unitigs;
     const unsigned grid = grid_for(n_ids);
-    uint32_t hbad = 0;
-    hipError_t e = hipMemsetAsync(w, 0, 32, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(simplify_check_kernel, dim3(grid), dim3(UT), 0, st, d_row_off, d_dst, d_uni_off, n_ids, n_edges, bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_graph_simplify_mask: HIP error");
-        return S2K_ERR_DEVICE;
-    }
-    if (hbad) {
-        ctx_set_error(ctx, "s2k_graph_simplify_mask: not a CSR of 2 * n_unitigs rows that ends at n_edges, an id >= 2 * n_unitigs, or a unitig "
-                           "without a member");
-        return S2K_ERR_INVALID_ARG;
-    }
+    const uint32_t hbad = c.check(w, 32, bad, [&] {
+        hipLaunchKernelGGL(simplify_check_kernel, dim3(grid), dim3(UT), 0, c.st, d_row_off, d_dst, d_uni_off, n_ids, n_edges, bad);
+    });
+    if (!c.ok()) return c.device_error();
+    if (hbad)
+        return c.invalid("not a CSR of 2 * n_unitigs rows that ends at n_edges, an id >= 2 * n_unitigs, or a unitig without a member");
     const UGraph g{d_row_off, d_dst, d_uni_off, d_uni_count, max_tip, max_bubble};
     unsigned long long h[3] = {0, 0, 0};
-    hipLaunchKernelGGL(simplify_mask_kernel, dim3(grid), dim3(UT), 0, st, g, n_ids, d_remove, totals);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, totals, sizeof(h), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_graph_simplify_mask: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    hipLaunchKernelGGL(simplify_mask_kernel, dim3(grid), dim3(UT), 0, c.st, g, n_ids, d_remove, totals);
+    c.launched();
+    c.fetch(h, totals, sizeof(h));
+    if (!c.sync()) return c.device_error();
     *n_tips = h[0];
     *n_bubbles = h[1];
     *n_removed = h[2];
@@ -436,78 +318,55 @@ s2k_status s2k_graph_induced(s2k_ctx *ctx, const uint64_t *d_keys, const uint32_
     if (n_nodes_out) *n_nodes_out = 0;
     if (n_edges_out) *n_edges_out = 0;
     if (!ctx || !n_nodes_out || !n_edges_out) return S2K_ERR_INVALID_ARG;
-    if (n_nodes >= (1ull << 31) || n_edges >= (1ull << 40)) {
-        ctx_set_error(ctx, "s2k_graph_induced: 2^31 nodes or more (oriented node ids are 32-bit), or 2^40 edges or more");
-        return S2K_ERR_INVALID_ARG;
-    }
-    if (n_nodes == 0) {
-        if (n_edges == 0) return S2K_OK;
-        ctx_set_error(ctx, "s2k_graph_induced: edges without nodes");
-        return S2K_ERR_INVALID_ARG;
-    }
+    Call c(ctx, "s2k_graph_induced");
+    if (n_nodes >= (1ull << 31) || n_edges >= (1ull << 40))
+        return c.invalid("2^31 nodes or more (oriented node ids are 32-bit), or 2^40 edges or more");
+    if (n_nodes == 0) return n_edges == 0 ? S2K_OK : c.invalid("edges without nodes");
     if (!d_node_keep && (!d_node_unitig || !d_remove)) return S2K_ERR_INVALID_ARG;
     if ((d_keys_out && !d_keys) || (d_counts_out && !d_counts) || (d_edge_counts_out && !d_edge_counts) || (n_edges && !d_edge_keys))
         return S2K_ERR_INVALID_ARG;
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
     const bool want_nodes = d_keys_out || d_counts_out, want_edges = n_edges && (d_edge_keys_out || d_edge_counts_out);
     const uint64_t node_tiles = (n_nodes + TB_TILE - 1) / TB_TILE, edge_tiles = (n_edges + TB_TILE - 1) / TB_TILE;
-    // the flag word, the two streams, new_id when the caller does not take it
-    const size_t o_id = al(64) + carve_bytes(n_nodes, node_tiles) + carve_bytes(n_edges, edge_tiles);
-    char *w = (char *)ctx_count_table(ctx, o_id + (!d_new_id && want_edges ? al(n_nodes * 4) : 0));
-    if (!w) {
-        ctx_set_error(ctx, "s2k_graph_induced: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    size_t off = al(64);
-    uint64_t *node_tmp = nullptr, *edge_tmp = nullptr;
-    const CompactWs nw = carve(w, &off, n_nodes, node_tiles, &node_tmp), ew = carve(w, &off, n_edges, edge_tiles, &edge_tmp);
-    uint32_t *bad = (uint32_t *)w;
-    uint32_t *new_id = d_new_id ? d_new_id : want_edges ? (uint32_t *)(w + o_id) : nullptr;
-    const char *fail = "s2k_graph_induced: HIP error";
-    uint32_t hbad = 0;
+    Layout L; // the flag word, the two streams, new_id when the caller does not take it
+    const auto flag = L.bytes<uint32_t>(64);
+    const auto nodes_ws = carve(L, n_nodes, node_tiles), edges_ws = carve(L, n_edges, edge_tiles);
+    const auto ids = L.take<uint32_t>(!d_new_id && want_edges ? n_nodes : 0);
+    char *w = L.alloc(ctx);
+    if (!w) return c.nomem();
+    const CompactWs nw = nodes_ws(w), ew = edges_ws(w);
+    uint32_t *bad = flag(w);
+    uint32_t *new_id = d_new_id ? d_new_id : want_edges ? ids(w) : nullptr;
     uint64_t nodes = 0, edges = 0;
-    hipError_t e = hipMemsetAsync(bad, 0, 4, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(node_count_kernel, dim3((unsigned)node_tiles), dim3(TB_THREADS), 0, st, d_node_keep, d_node_unitig, d_remove, n_unitigs,
-                           n_nodes, nw, bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = launch_scan_u32(nw.tile_kept, node_tiles, nw.tile_off, node_tmp, 0, st);
-    if (e == hipSuccess && n_edges) {
-        hipLaunchKernelGGL(edge_count_kernel, dim3((unsigned)edge_tiles), dim3(TB_THREADS), 0, st, d_edge_keys, n_edges, n_nodes, nw.wmask, ew, bad);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = launch_scan_u32(ew.tile_kept, edge_tiles, ew.tile_off, edge_tmp, 0, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&edges, ew.tile_off + edge_tiles, 8, hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&nodes, nw.tile_off + node_tiles, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, fail);
-        return S2K_ERR_DEVICE;
-    }
-    if (hbad) {
-        ctx_set_error(ctx, "s2k_graph_induced: a node_unitig entry >= n_unitigs, or an edge that names a node >= n_nodes");
-        return S2K_ERR_INVALID_ARG;
-    }
+    const uint32_t hbad = c.check(bad, 4, bad, [&] {
+        hipLaunchKernelGGL(node_count_kernel, dim3((unsigned)node_tiles), dim3(TB_THREADS), 0, c.st, d_node_keep, d_node_unitig, d_remove,
+                           n_unitigs, n_nodes, nw, bad);
+        c.launched();
+        c.scan(nw.tile_kept, node_tiles, nw.tile_off, nodes_ws.scan_tmp(w));
+        if (c.ok() && n_edges) {
+            hipLaunchKernelGGL(edge_count_kernel, dim3((unsigned)edge_tiles), dim3(TB_THREADS), 0, c.st, d_edge_keys, n_edges, n_nodes, nw.wmask,
+                               ew, bad);
+            c.launched();
+            c.scan(ew.tile_kept, edge_tiles, ew.tile_off, edges_ws.scan_tmp(w));
+            c.fetch(&edges, ew.tile_off + edge_tiles, 8);
+        }
+        c.fetch(&nodes, nw.tile_off + node_tiles, 8);
+    });
+    if (!c.ok()) return c.device_error();
+    if (hbad) return c.invalid("a node_unitig entry >= n_unitigs, or an edge that names a node >= n_nodes");
     *n_nodes_out = nodes;
     *n_edges_out = edges;
     if (!d_new_id && !want_nodes && !want_edges) return S2K_OK;
     if ((want_nodes && nodes > node_capacity) || (want_edges && edges > edge_capacity)) return S2K_ERR_CAPACITY;
-    hipLaunchKernelGGL(node_write_kernel, dim3((unsigned)node_tiles), dim3(TB_THREADS), 0, st, d_keys, d_counts, n_nodes, nw, new_id, d_keys_out,
+    hipLaunchKernelGGL(node_write_kernel, dim3((unsigned)node_tiles), dim3(TB_THREADS), 0, c.st, d_keys, d_counts, n_nodes, nw, new_id, d_keys_out,
                        d_counts_out);
-    e = hipGetLastError();
-    if (e == hipSuccess && want_edges) {
-        hipLaunchKernelGGL(edge_write_kernel, dim3((unsigned)edge_tiles), dim3(TB_THREADS), 0, st, d_edge_keys, d_edge_counts, n_edges, ew, new_id,
+    c.launched();
+    if (c.ok() && want_edges) {
+        hipLaunchKernelGGL(edge_write_kernel, dim3((unsigned)edge_tiles), dim3(TB_THREADS), 0, c.st, d_edge_keys, d_edge_counts, n_edges, ew, new_id,
                            d_edge_keys_out, d_edge_counts_out);
-        e = hipGetLastError();
+        c.launched();
     }
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, fail);
-        return S2K_ERR_DEVICE;
-    }
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 

@@ -33,6 +33,7 @@
 #include <new>
 
 #include "../../include/s2k.h"
+#include "s2k_call.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
 #include "s2k_table_dev.h"
@@ -73,11 +74,8 @@ __global__ __launch_bounds__(TB_THREADS) void table_lookup_kernel(TableView tv, 
 }
 
 struct FilterWs {
-    uint32_t *cnt;       // per item: its count
-    uint64_t *wmask;     // per 64 items: kept mask
-    uint32_t *wpre;      // per 64 items: kept items before the word inside its tile
-    uint32_t *tile_kept; // per tile
-    uint64_t *tile_off;  // n_tiles + 1
+    uint32_t *cnt; // per item: its count
+    CompactWs c;
 };
 
 __global__ __launch_bounds__(TB_THREADS) void filter_count_kernel(TableView tv, const uint64_t *__restrict__ hash, uint64_t n_items, uint32_t minc,
@@ -99,25 +97,19 @@ __global__ __launch_bounds__(TB_THREADS) void filter_count_kernel(TableView tv, 
         const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64; // first item of this wave's word
         if (lane == 0) {
             wc[r * 4 + wv] = (uint32_t)__popcll(m);
-            if (w0 < n_items) ws.wmask[w0 >> 6] = m;
+            if (w0 < n_items) ws.c.wmask[w0 >> 6] = m;
         }
     }
     __syncthreads();
-    if (tid < TB_WORDS) { // word k of the tile = items t0 + 64k ..: r = k / 4, wave k % 4
-        uint32_t pre = 0;
-        for (int x = 0; x < tid; x++) pre += wc[x];
-        const uint64_t w0 = t0 + (uint64_t)tid * 64;
-        if (w0 < n_items) ws.wpre[w0 >> 6] = pre;
-        if (tid == TB_WORDS - 1) ws.tile_kept[blockIdx.x] = pre + wc[tid];
-    }
+    tile_prefixes(wc, t0, n_items, ws.c);
 }
 
 // kept items before input index j (j <= n_items)
 __device__ inline uint64_t kept_before(const FilterWs &ws, uint64_t n_items, uint64_t n_tiles, uint64_t j) {
-    if (j >= n_items) return ws.tile_off[n_tiles];
+    if (j >= n_items) return ws.c.tile_off[n_tiles];
     const uint64_t w = j >> 6;
-    const uint64_t below = (j & 63) ? ws.wmask[w] & ((1ull << (j & 63)) - 1ull) : 0ull;
-    return ws.tile_off[j / TB_TILE] + ws.wpre[w] + (uint64_t)__popcll(below);
+    const uint64_t below = (j & 63) ? ws.c.wmask[w] & ((1ull << (j & 63)) - 1ull) : 0ull;
+    return ws.c.tile_off[j / TB_TILE] + ws.c.wpre[w] + (uint64_t)__popcll(below);
 }
 
 __global__ __launch_bounds__(256) void filter_offsets_kernel(const uint64_t *__restrict__ km_off, uint64_t n_reads, uint64_t n_items, uint64_t n_tiles,
@@ -125,16 +117,6 @@ __global__ __launch_bounds__(256) void filter_offsets_kernel(const uint64_t *__r
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r > n_reads) return;
     o_km_off[r] = kept_before(ws, n_items, n_tiles, km_off[r]);
-}
-
-// the last read r in [lo, hi] with km_off[r] <= j (km_off[lo] <= j holds)
-__device__ inline uint64_t read_of(const uint64_t *__restrict__ km_off, uint64_t lo, uint64_t hi, uint64_t j) {
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (km_off[mid] <= j) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
 }
 
 struct FilterIo {
@@ -156,7 +138,7 @@ __global__ __launch_bounds__(TB_THREADS) void filter_write_kernel(FilterIo io, u
     uint8_t *s8 = (uint8_t *)s64;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE, t1 = std::min<uint64_t>(t0 + TB_TILE, n_items);
-    const uint64_t base = ws.tile_off[blockIdx.x], tot = ws.tile_off[blockIdx.x + 1] - base;
+    const uint64_t base = ws.c.tile_off[blockIdx.x], tot = ws.c.tile_off[blockIdx.x + 1] - base;
     if (tot == 0) return;
     if (tid < 2 && io.o_offset) // the reads that hold the tile's first and last item
         sread[tid] = read_of(io.km_off, 0, io.n_reads - 1, tid == 0 ? t0 : t1 - 1);
@@ -169,7 +151,7 @@ __global__ __launch_bounds__(TB_THREADS) void filter_write_kernel(FilterIo io, u
         const bool kept = j < n_items && cnt[r] >= minc;
         const uint64_t m = __ballot(kept);
         const uint64_t w = (t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64) >> 6;
-        slot[r] = (kept ? ws.wpre[w] : 0u) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        slot[r] = (kept ? ws.c.wpre[w] : 0u) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
         keep |= kept ? 1u << r : 0u;
     }
     __syncthreads();
@@ -223,11 +205,8 @@ __global__ __launch_bounds__(TB_THREADS) void filter_write_kernel(FilterIo io, u
 constexpr uint32_t TB_NONE = 0xFFFFFFFFu; // an item that is not solid (oriented ids stay below 2^32 - 2: the table has < 2^31 keys)
 
 struct EdgeWs {
-    uint32_t *node;      // per item: its oriented node 2 * rank + rev, TB_NONE when it is not solid
-    uint64_t *wadj;      // per 64 items: the items j for which (j, j + 1) is an adjacency
-    uint32_t *wpre;      // per 64 items: keys emitted before the word inside its tile
-    uint32_t *tile_keys; // per tile
-    uint64_t *tile_off;  // n_tiles + 1
+    uint32_t *node; // per item: its oriented node 2 * rank + rev, TB_NONE when it is not solid
+    CompactWs c;    // wmask: the items j for which (j, j + 1) is an adjacency; wpre, tile_kept: keys emitted, not items
 };
 
 // the first r in [0, n_reads] with km_off[r] > x (n_reads + 1 if there is none)
@@ -297,17 +276,11 @@ __global__ __launch_bounds__(TB_THREADS) void edges_count_kernel(TableView tv, c
         const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
         if (lane == 0) {
             wc[r * 4 + wv] = (uint32_t)(__popcll(m1) + __popcll(m2));
-            if (w0 < n_items) ws.wadj[w0 >> 6] = m1;
+            if (w0 < n_items) ws.c.wmask[w0 >> 6] = m1;
         }
     }
     __syncthreads();
-    if (tid < TB_WORDS) {
-        uint32_t pre = 0;
-        for (int x = 0; x < tid; x++) pre += wc[x];
-        const uint64_t w0 = t0 + (uint64_t)tid * 64;
-        if (w0 < n_items) ws.wpre[w0 >> 6] = pre;
-        if (tid == TB_WORDS - 1) ws.tile_keys[blockIdx.x] = pre + wc[tid];
-    }
+    tile_prefixes(wc, t0, n_items, ws.c);
 }
 
 // each adjacency's key (u << 32 | v), then its twin's ((v ^ 1) << 32 | u ^ 1) unless it is its own, staged in LDS at tile-relative
@@ -316,13 +289,13 @@ __global__ __launch_bounds__(TB_THREADS) void edges_write_kernel(uint64_t n_item
     __shared__ uint64_t skey[2 * TB_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
-    const uint64_t base = ws.tile_off[blockIdx.x], tot = ws.tile_off[blockIdx.x + 1] - base;
+    const uint64_t base = ws.c.tile_off[blockIdx.x], tot = ws.c.tile_off[blockIdx.x + 1] - base;
     if (tot == 0) return;
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) {
         const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
         const uint64_t w = (t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64) >> 6;
-        const bool adj = j < n_items && ((ws.wadj[w] >> lane) & 1ull); // j + 1 < n_items whenever the bit is set
+        const bool adj = j < n_items && ((ws.c.wmask[w] >> lane) & 1ull); // j + 1 < n_items whenever the bit is set
         uint32_t u = 0, v = 0;
         if (adj) {
             u = ws.node[j];
@@ -332,7 +305,7 @@ __global__ __launch_bounds__(TB_THREADS) void edges_write_kernel(uint64_t n_item
         const uint64_t below = (1ull << lane) - 1ull;
         const uint64_t m1 = __ballot(adj), m2 = __ballot(two);
         if (adj) {
-            const uint32_t slot = ws.wpre[w] + (uint32_t)(__popcll(m1 & below) + __popcll(m2 & below));
+            const uint32_t slot = ws.c.wpre[w] + (uint32_t)(__popcll(m1 & below) + __popcll(m2 & below));
             skey[slot] = ((uint64_t)u << 32) | v;
             if (two) skey[slot + 1] = ((uint64_t)(v ^ 1u) << 32) | (u ^ 1u);
         }
@@ -343,8 +316,6 @@ __global__ __launch_bounds__(TB_THREADS) void edges_write_kernel(uint64_t n_item
         out[base + i] = skey[i];
     }
 }
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 uint32_t table_bits(uint64_t n) {
     uint32_t b = 1;
@@ -371,10 +342,8 @@ s2k_table *s2k_table_create(s2k_ctx *ctx, const uint64_t *d_keys, const uint32_t
         return nullptr;
     };
     if (!ctx || (n && !d_keys)) return fail(S2K_ERR_INVALID_ARG);
-    if (n >= (1ull << 32)) {
-        ctx_set_error(ctx, "s2k_table_create: 2^32 keys or more");
-        return fail(S2K_ERR_INVALID_ARG);
-    }
+    Call c(ctx, "s2k_table_create");
+    if (n >= (1ull << 32)) return fail(c.invalid("2^32 keys or more"));
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return fail(S2K_ERR_DEVICE);
     s2k_table *t = new (std::nothrow) s2k_table;
     if (!t) return fail(S2K_ERR_NOMEM);
@@ -386,32 +355,18 @@ s2k_table *s2k_table_create(s2k_ctx *ctx, const uint64_t *d_keys, const uint32_t
     const size_t dir_n = (1ull << t->bits) + 1;
     if (hipMalloc((void **)&t->dir, (dir_n + 1) * 4) != hipSuccess) {
         delete t;
-        ctx_set_error(ctx, "s2k_table_create: directory allocation");
-        return fail(S2K_ERR_NOMEM);
+        return fail(c.nomem("directory allocation"));
     }
     uint32_t *bad = t->dir + dir_n;
-    hipStream_t st = ctx_stream(ctx);
-    hipError_t e = hipMemsetAsync(t->dir, 0, (dir_n + 1) * 4, st); // n == 0: every bucket empty
-    if (e == hipSuccess && n) {
-        hipLaunchKernelGGL(table_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_keys, (uint32_t)n, 64u - t->bits, t->bits,
-                           t->dir, bad);
-        e = hipGetLastError();
-    }
-    uint32_t hbad = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    s2k_status s = S2K_OK;
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_create: HIP error");
-        s = S2K_ERR_DEVICE;
-    } else if (hbad) {
-        ctx_set_error(ctx, "s2k_table_create: the keys are not strictly ascending");
-        s = S2K_ERR_INVALID_ARG;
-    }
-    if (s != S2K_OK) {
+    const uint32_t hbad = c.check(t->dir, (dir_n + 1) * 4, bad, [&] { // n == 0: every bucket empty
+        if (n)
+            hipLaunchKernelGGL(table_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, d_keys, (uint32_t)n, 64u - t->bits,
+                               t->bits, t->dir, bad);
+    });
+    if (!c.ok() || hbad) {
         (void)hipFree(t->dir);
         delete t;
-        return fail(s);
+        return fail(!c.ok() ? c.device_error() : c.invalid("the keys are not strictly ascending"));
     }
     if (status) *status = S2K_OK;
     return t;
@@ -427,21 +382,13 @@ void s2k_table_destroy(s2k_table *t) {
 s2k_status s2k_table_lookup(s2k_table *t, const uint64_t *d_query, uint64_t n, uint32_t *d_out) {
     if (!t || (n && (!d_query || !d_out))) return S2K_ERR_INVALID_ARG;
     if (n == 0) return S2K_OK;
-    s2k_ctx *ctx = t->ctx;
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
+    if (hipSetDevice(ctx_device(t->ctx)) != hipSuccess) return S2K_ERR_DEVICE;
+    Call c(t->ctx, "s2k_table_lookup");
     const uint64_t nb = (n + TB_TILE - 1) / TB_TILE;
-    if (nb >= (1ull << 32)) {
-        ctx_set_error(ctx, "s2k_table_lookup: too many queries for one call");
-        return S2K_ERR_INVALID_ARG;
-    }
-    hipLaunchKernelGGL(table_lookup_kernel, dim3((unsigned)nb), dim3(TB_THREADS), 0, st, t->view(), d_query, n, d_out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_lookup: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    if (nb >= (1ull << 32)) return c.invalid("too many queries for one call");
+    hipLaunchKernelGGL(table_lookup_kernel, dim3((unsigned)nb), dim3(TB_THREADS), 0, c.st, t->view(), d_query, n, d_out);
+    c.launched();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 
@@ -451,78 +398,46 @@ s2k_status s2k_table_filter(s2k_table *t, uint64_t n_reads, const s2k_device_out
     if (!t || !in || !out || !n_kept || !in->km_off || !in->hash || !out->km_off || (out->start && !in->start) || (out->end && !in->end) ||
         (out->rev && !in->rev))
         return S2K_ERR_INVALID_ARG;
-    s2k_ctx *ctx = t->ctx;
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
-    uint64_t ends[2] = {0, 0};
-    hipError_t e = hipMemcpyAsync(&ends[0], in->km_off, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&ends[1], in->km_off + n_reads, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_filter: HIP error");
-        return S2K_ERR_DEVICE;
-    }
-    if (ends[0] != 0 || ends[1] < ends[0]) {
-        ctx_set_error(ctx, "s2k_table_filter: in->km_off must start at 0 and end at or after its start");
-        return S2K_ERR_INVALID_ARG;
-    }
-    const uint64_t n_items = ends[1];
+    if (hipSetDevice(ctx_device(t->ctx)) != hipSuccess) return S2K_ERR_DEVICE;
+    Call c(t->ctx, "s2k_table_filter");
+    const Ends ends = read_ends(c, in->km_off, nullptr, n_reads);
+    if (!c.ok()) return c.device_error();
+    if (ends.km0 != 0 || ends.n_items < ends.km0) return c.invalid("in->km_off must start at 0 and end at or after its start");
+    const uint64_t n_items = ends.n_items;
     if (n_items == 0) { // no items: every read is empty
-        e = hipMemsetAsync(out->km_off, 0, (n_reads + 1) * 8, st);
-        if (e == hipSuccess) e = ctx_sync(ctx);
-        if (e != hipSuccess) {
-            ctx_set_error(ctx, "s2k_table_filter: HIP error");
-            return S2K_ERR_DEVICE;
-        }
+        c.zero(out->km_off, (n_reads + 1) * 8);
+        if (!c.sync()) return c.device_error();
         return S2K_OK;
     }
-    const uint64_t nt = (n_items + TB_TILE - 1) / TB_TILE, nw = (n_items + 63) / 64;
-    if (nt >= (1ull << 32) || n_reads + 1 >= (1ull << 40)) {
-        ctx_set_error(ctx, "s2k_table_filter: too many items for one call");
-        return S2K_ERR_INVALID_ARG;
-    }
-    size_t off = 0;
-    const size_t oC = off; off += al(n_items * 4);
-    const size_t oM = off; off += al(nw * 8);
-    const size_t oP = off; off += al(nw * 4);
-    const size_t oK = off; off += al(nt * 4);
-    const size_t oO = off; off += al((nt + 1) * 8);
-    const size_t oT = off; off += al(scan_tmp_bytes(nt));
-    char *w = (char *)ctx_count_table(ctx, off);
-    if (!w) {
-        ctx_set_error(ctx, "s2k_table_filter: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    FilterWs ws{(uint32_t *)(w + oC), (uint64_t *)(w + oM), (uint32_t *)(w + oP), (uint32_t *)(w + oK), (uint64_t *)(w + oO)};
+    const uint64_t nt = (n_items + TB_TILE - 1) / TB_TILE;
+    if (nt >= (1ull << 32) || n_reads + 1 >= (1ull << 40)) return c.invalid("too many items for one call");
+    Layout L;
+    const auto cnt = L.take<uint32_t>(n_items);
+    const auto cw = carve(L, n_items, nt);
+    char *w = L.alloc(t->ctx);
+    if (!w) return c.nomem();
+    const FilterWs ws{cnt(w), cw(w)};
     const uint32_t minc = min_count ? min_count : 1u;
-    hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, t->view(), in->hash, n_items, minc, ws);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = launch_scan_u32(ws.tile_kept, nt, ws.tile_off, (uint64_t *)(w + oT), 0, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(filter_offsets_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, st, in->km_off, n_reads, n_items, nt, ws,
-                           out->km_off);
-        e = hipGetLastError();
+    hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, t->view(), in->hash, n_items, minc, ws);
+    c.launched();
+    c.scan(ws.c.tile_kept, nt, ws.c.tile_off, cw.scan_tmp(w));
+    if (c.ok()) {
+        hipLaunchKernelGGL(filter_offsets_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, c.st, in->km_off, n_reads, n_items, nt,
+                           ws, out->km_off);
+        c.launched();
     }
     uint64_t kept = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&kept, ws.tile_off + nt, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_filter: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    c.fetch(&kept, ws.c.tile_off + nt, 8);
+    if (!c.sync()) return c.device_error();
     *n_kept = kept;
     const bool want = out->hash || out->start || out->end || out->rev || out->offset || out->count;
     if (!want || kept == 0) return S2K_OK;
     if (kept > out->capacity) return S2K_ERR_CAPACITY;
     FilterIo io{in->km_off, n_reads, in->hash, in->start, in->end, in->rev, out->hash, out->start, out->end, out->offset, out->count, out->rev,
                 out->capacity};
-    hipLaunchKernelGGL(filter_write_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, io, n_items, minc, ws);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_filter: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    hipLaunchKernelGGL(filter_write_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, io, n_items, minc, ws);
+    c.launched();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 
@@ -530,67 +445,36 @@ s2k_status s2k_table_edges(s2k_table *t, uint64_t n_reads, const s2k_device_out 
                            uint64_t capacity, uint64_t *n_edges) {
     if (n_edges) *n_edges = 0;
     if (!t || !in || !n_edges || !in->km_off || !in->hash || !in->rev) return S2K_ERR_INVALID_ARG;
-    s2k_ctx *ctx = t->ctx;
-    if (t->n >= (1ull << 31)) {
-        ctx_set_error(ctx, "s2k_table_edges: 2^31 keys or more (oriented node ids are 32-bit)");
-        return S2K_ERR_INVALID_ARG;
-    }
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
-    uint64_t ends[2] = {0, 0};
-    hipError_t e = hipMemcpyAsync(&ends[0], in->km_off, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&ends[1], in->km_off + n_reads, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_edges: HIP error");
-        return S2K_ERR_DEVICE;
-    }
-    if (ends[0] != 0 || ends[1] < ends[0]) {
-        ctx_set_error(ctx, "s2k_table_edges: in->km_off must start at 0 and end at or after its start");
-        return S2K_ERR_INVALID_ARG;
-    }
-    const uint64_t n_items = ends[1];
+    Call c(t->ctx, "s2k_table_edges");
+    if (t->n >= (1ull << 31)) return c.invalid("2^31 keys or more (oriented node ids are 32-bit)");
+    if (hipSetDevice(ctx_device(t->ctx)) != hipSuccess) return S2K_ERR_DEVICE;
+    const Ends ends = read_ends(c, in->km_off, nullptr, n_reads);
+    if (!c.ok()) return c.device_error();
+    if (ends.km0 != 0 || ends.n_items < ends.km0) return c.invalid("in->km_off must start at 0 and end at or after its start");
+    const uint64_t n_items = ends.n_items;
     if (n_items == 0) return S2K_OK;
-    const uint64_t nt = (n_items + TB_TILE - 1) / TB_TILE, nw = (n_items + 63) / 64;
-    if (nt >= (1ull << 32)) {
-        ctx_set_error(ctx, "s2k_table_edges: too many items for one call");
-        return S2K_ERR_INVALID_ARG;
-    }
-    size_t off = 0;
-    const size_t oN = off; off += al(n_items * 4);
-    const size_t oA = off; off += al(nw * 8);
-    const size_t oP = off; off += al(nw * 4);
-    const size_t oK = off; off += al(nt * 4);
-    const size_t oO = off; off += al((nt + 1) * 8);
-    const size_t oT = off; off += al(scan_tmp_bytes(nt));
-    char *w = (char *)ctx_count_table(ctx, off);
-    if (!w) {
-        ctx_set_error(ctx, "s2k_table_edges: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    EdgeWs ws{(uint32_t *)(w + oN), (uint64_t *)(w + oA), (uint32_t *)(w + oP), (uint32_t *)(w + oK), (uint64_t *)(w + oO)};
+    const uint64_t nt = (n_items + TB_TILE - 1) / TB_TILE;
+    if (nt >= (1ull << 32)) return c.invalid("too many items for one call");
+    Layout L;
+    const auto node = L.take<uint32_t>(n_items);
+    const auto cw = carve(L, n_items, nt);
+    char *w = L.alloc(t->ctx);
+    if (!w) return c.nomem();
+    const EdgeWs ws{node(w), cw(w)};
     const uint32_t minc = min_count ? min_count : 1u;
-    hipLaunchKernelGGL(edges_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, t->view(), in->km_off, n_reads, in->hash, in->rev,
+    hipLaunchKernelGGL(edges_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, t->view(), in->km_off, n_reads, in->hash, in->rev,
                        n_items, minc, ws);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = launch_scan_u32(ws.tile_keys, nt, ws.tile_off, (uint64_t *)(w + oT), 0, st);
+    c.launched();
+    c.scan(ws.c.tile_kept, nt, ws.c.tile_off, cw.scan_tmp(w));
     uint64_t total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, ws.tile_off + nt, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_edges: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    c.fetch(&total, ws.c.tile_off + nt, 8);
+    if (!c.sync()) return c.device_error();
     *n_edges = total;
     if (!d_edge_keys || total == 0) return S2K_OK;
     if (total > capacity) return S2K_ERR_CAPACITY;
-    hipLaunchKernelGGL(edges_write_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, st, n_items, ws, d_edge_keys, capacity);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_table_edges: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    hipLaunchKernelGGL(edges_write_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, n_items, ws, d_edge_keys, capacity);
+    c.launched();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 

@@ -1,19 +1,17 @@
 // s2k_table_dev.h -- the count table's device view and its fused look-ups, shared by the translation units that search a table
-// (s2k_table.hip: look-up, filter, edges; s2k_seq.hip: representatives, node sequences).  DESIGN.md §3.8.
+// (s2k_table.hip: look-up, filter, edges; s2k_seq.hip: representatives, node sequences), and the search of km_off that maps an
+// item to its read.  The tile geometry (TB_THREADS, TB_Q, TB_TILE, TB_WORDS) comes from s2k_compact_dev.h.  DESIGN.md §3.8.
 #pragma once
 #include <algorithm>
 
 #include "../../include/s2k.h"
+#include "s2k_compact_dev.h"
 #include "s2k_dev.h"
 
 namespace s2k {
 namespace {
 
-constexpr int TB_THREADS = 256;
-constexpr int TB_Q = 8;                             // queries (items) per lane
-constexpr uint32_t TB_TILE = TB_THREADS * TB_Q;    // 2 048 items per workgroup of the filter
-constexpr int TB_WORDS = TB_TILE / 64;              // kept-mask words per tile
-constexpr uint64_t TB_KEYS_PER_BUCKET = 4;          // B = floor(log2(n / 4)): 4-7 keys per bucket on average
+constexpr uint64_t TB_KEYS_PER_BUCKET = 4; // B = floor(log2(n / 4)): 4-7 keys per bucket on average
 constexpr uint32_t TB_MAX_BITS = 26;
 
 struct TableView {
@@ -98,6 +96,16 @@ __device__ inline void lookup_one(const TableView &tv, uint64_t q, uint32_t *c, 
             return;
         }
     }
+}
+
+// the last read r in [lo, hi] with km_off[r] <= j (km_off[lo] <= j holds)
+__device__ inline uint64_t read_of(const uint64_t *__restrict__ km_off, uint64_t lo, uint64_t hi, uint64_t j) {
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (km_off[mid] <= j) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
 }
 
 } // namespace

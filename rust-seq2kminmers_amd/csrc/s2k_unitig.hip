@@ -41,36 +41,20 @@
 #include <chrono>
 
 #include "../../include/s2k.h"
+#include "s2k_call.h"
 #include "s2k_dev.h"
+#include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
 
 namespace s2k {
 namespace {
 
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t SET = 0x80000000u; // the low word of a settled ranking state: SET | position
-constexpr int UT = 256;               // threads per block
-constexpr unsigned UB_MAX = 4096;     // blocks of a grid-stride launch (one counter atomic per block)
 constexpr int MAX_ROUNDS = 32;        // a chain or a cut cycle has fewer than 2^31 members
 constexpr int CNT_WORDS = MAX_ROUNDS + 8;
 
-__host__ inline unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>((n + UT - 1) / UT, UB_MAX); }
-
 __device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned long long pack(uint32_t hi, uint32_t lo) { return ((unsigned long long)hi << 32) | lo; }
-
-// the sum of v over the block, added to *word by one lane (nothing when it is 0)
-__device__ __forceinline__ void block_add(unsigned long long v, unsigned long long *word) {
-    __shared__ unsigned long long part[UT / 64];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-        for (int w = 0; w < UT / 64; w++) s += part[w];
-        if (s) atomicAdd(word, s);
-    }
-}
 
 // out-degree of u and, when it is 1, the link target (NONE: no link).  The CSR was checked.
 __device__ __forceinline__ uint32_t link_of(const uint64_t *__restrict__ row_off, const uint32_t *__restrict__ dst, uint32_t u) {
@@ -86,8 +70,8 @@ __global__ __launch_bounds__(UT) void check_kernel(const uint64_t *__restrict__ 
                                                    uint64_t n_edges, uint32_t *__restrict__ bad) {
     bool ok = true;
     for (uint64_t u = (uint64_t)blockIdx.x * UT + threadIdx.x; u < n_ids; u += (uint64_t)gridDim.x * UT) {
-        const uint64_t a = row_off[u], b = row_off[u + 1];
-        if ((u == 0 && a != 0) || (u == n_ids - 1 && b != n_edges) || a > b || b > n_edges) {
+        uint64_t a, b;
+        if (!csr_row_ok(row_off, u, n_ids, n_edges, &a, &b)) {
             ok = false;
             continue;
         }
@@ -274,25 +258,22 @@ __global__ __launch_bounds__(UT) void uedge_write_kernel(UnitigView g, uint64_t 
     }
 }
 
-size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // Runs the ranking rounds on the ping-pong pair until no lane is unsettled (-> 0) or only cycles are left (-> 1); *cur names the
 // buffer that holds the result.  -1: a HIP error or more rounds than a valid input can need.
-int rank_rounds(s2k_ctx *ctx, unsigned long long *buf[2], int *cur, uint64_t n_ids, unsigned long long *cnt, uint32_t *rounds) {
-    hipStream_t st = ctx_stream(ctx);
+int rank_rounds(Call &c, unsigned long long *buf[2], int *cur, uint64_t n_ids, unsigned long long *cnt, uint32_t *rounds) {
     unsigned long long h[CNT_WORDS];
-    if (hipMemsetAsync(cnt, 0, sizeof(h), st) != hipSuccess) return -1;
+    c.zero(cnt, sizeof(h));
+    if (!c.ok()) return -1;
     int r = 0;
     for (int group = 1; r < MAX_ROUNDS; group = r < 8 ? 1 : r < 12 ? 2 : 4) {
         const int first = r;
         for (int i = 0; i < group && r < MAX_ROUNDS; i++, r++) {
-            hipLaunchKernelGGL(jump_kernel, dim3(grid_for(n_ids)), dim3(UT), 0, st, buf[*cur], buf[*cur ^ 1], n_ids, cnt + r);
+            hipLaunchKernelGGL(jump_kernel, dim3(grid_for(n_ids)), dim3(UT), 0, c.st, buf[*cur], buf[*cur ^ 1], n_ids, cnt + r);
             *cur ^= 1;
         }
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = ctx_sync(ctx);
-        if (e != hipSuccess) return -1;
+        c.launched();
+        c.fetch(h, cnt, sizeof(h));
+        if (!c.sync()) return -1;
         *rounds += (uint32_t)(r - first);
         for (int i = first; i < r; i++) {
             if (h[i] == 0) return 0;
@@ -321,147 +302,115 @@ s2k_status s2k_graph_unitigs(s2k_ctx *ctx, const uint64_t *d_row_off, const uint
     if (n_unitigs) *n_unitigs = 0;
     if (n_links) *n_links = 0;
     if (!ctx || !d_row_off || !n_unitigs || !n_links || (n_edges && !d_dst)) return S2K_ERR_INVALID_ARG;
-    if (n_nodes >= (1ull << 31) || n_edges >= (1ull << 40)) {
-        ctx_set_error(ctx, "s2k_graph_unitigs: 2^31 nodes or more (oriented node ids are 32-bit), or 2^40 edges or more");
-        return S2K_ERR_INVALID_ARG;
-    }
+    Call c(ctx, "s2k_graph_unitigs");
+    if (n_nodes >= (1ull << 31) || n_edges >= (1ull << 40))
+        return c.invalid("2^31 nodes or more (oriented node ids are 32-bit), or 2^40 edges or more");
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
     const uint64_t n_ids = 2 * n_nodes;
     const bool want = out && (out->uni_off || out->members || out->node_unitig || out->node_pos || out->circular);
-    const char *fail = "s2k_graph_unitigs: HIP error";
-    hipError_t e = hipSuccess;
     g_rounds = 0;
     g_step_ms[0] = g_step_ms[1] = g_step_ms[2] = g_step_ms[3] = 0;
     double t0 = now_ms(), t1;
 #define STEP(i) (t1 = now_ms(), g_step_ms[i] = t1 - t0, t0 = t1)
-#define UNITIG_FAIL()                 \
-    do {                              \
-        ctx_set_error(ctx, fail);     \
-        return S2K_ERR_DEVICE;        \
-    } while (0)
     if (n_nodes == 0) {
         uint64_t first = 1;
-        e = hipMemcpyAsync(&first, d_row_off, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = ctx_sync(ctx);
-        if (e != hipSuccess) UNITIG_FAIL();
-        if (first != 0 || n_edges != 0) {
-            ctx_set_error(ctx, "s2k_graph_unitigs: row_off must start at 0 and end at n_edges");
-            return S2K_ERR_INVALID_ARG;
-        }
+        c.fetch(&first, d_row_off, 8);
+        if (!c.sync()) return c.device_error();
+        if (first != 0 || n_edges != 0) return c.invalid("row_off must start at 0 and end at n_edges");
         if (want && out->uni_off) {
-            e = hipMemsetAsync(out->uni_off, 0, 8, st);
-            if (e == hipSuccess) e = ctx_sync(ctx);
-            if (e != hipSuccess) UNITIG_FAIL();
+            c.zero(out->uni_off, 8);
+            if (!c.sync()) return c.device_error();
         }
         return S2K_OK;
     }
-    size_t off = 0;
-    const size_t oC = off; off += al(CNT_WORDS * 8 + 16);
-    const size_t oN = off; off += al(n_ids * 4);
-    const size_t oA = off; off += al((n_ids + 1) * 8);
-    const size_t oB = off; off += al((n_ids + 1) * 8);
-    const size_t oF = off; off += al(n_ids * 4);
-    const size_t oU = off; off += al((n_nodes + 1) * 8);
-    const size_t oL = off; off += al(n_nodes * 4);
-    const size_t oT = off; off += al(scan_tmp_bytes(n_ids));
-    char *w = (char *)ctx_count_table(ctx, off);
-    if (!w) {
-        ctx_set_error(ctx, "s2k_graph_unitigs: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    unsigned long long *cnt = (unsigned long long *)(w + oC); // CNT_WORDS round counters, then n_links, then the check's flag
+    Layout L;
+    const auto counters = L.bytes<unsigned long long>(CNT_WORDS * 8 + 16);
+    const auto next_p = L.take<uint32_t>(n_ids);
+    const auto buf_a = L.take<unsigned long long>(n_ids + 1), buf_b = L.take<unsigned long long>(n_ids + 1);
+    const auto flag_p = L.take<uint32_t>(n_ids);
+    const auto uoff_p = L.take<uint64_t>(n_nodes + 1);
+    const auto len_p = L.take<uint32_t>(n_nodes);
+    const auto tmp_p = L.bytes<uint64_t>(scan_tmp_bytes(n_ids));
+    char *w = L.alloc(ctx);
+    if (!w) return c.nomem();
+    unsigned long long *cnt = counters(w); // CNT_WORDS round counters, then n_links, then the check's flag
     unsigned long long *d_links = cnt + CNT_WORDS;
     uint32_t *bad = (uint32_t *)(cnt + CNT_WORDS + 1);
-    uint32_t *next = (uint32_t *)(w + oN), *flag = (uint32_t *)(w + oF), *len = (uint32_t *)(w + oL);
-    unsigned long long *buf[2] = {(unsigned long long *)(w + oA), (unsigned long long *)(w + oB)};
-    uint64_t *uoff = (uint64_t *)(w + oU), *scan_tmp = (uint64_t *)(w + oT);
+    uint32_t *next = next_p(w), *flag = flag_p(w), *len = len_p(w);
+    unsigned long long *buf[2] = {buf_a(w), buf_b(w)};
+    uint64_t *uoff = uoff_p(w), *scan_tmp = tmp_p(w);
     const unsigned grid = grid_for(n_ids);
 
     // 1. the input
-    uint32_t hbad = 0;
-    e = hipMemsetAsync(cnt, 0, CNT_WORDS * 8 + 16, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(check_kernel, dim3(grid), dim3(UT), 0, st, d_row_off, d_dst, n_ids, n_edges, bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) UNITIG_FAIL();
+    const uint32_t hbad = c.check(cnt, CNT_WORDS * 8 + 16, bad, [&] {
+        hipLaunchKernelGGL(check_kernel, dim3(grid), dim3(UT), 0, c.st, d_row_off, d_dst, n_ids, n_edges, bad);
+    });
+    if (!c.ok()) return c.device_error();
     STEP(0);
-    if (hbad) {
-        ctx_set_error(ctx, "s2k_graph_unitigs: not a CSR of 2 * n_nodes rows that ends at n_edges, a row that is not strictly ascending or names an id "
-                           ">= 2 * n_nodes, or an edge whose twin is missing");
-        return S2K_ERR_INVALID_ARG;
-    }
+    if (hbad)
+        return c.invalid("not a CSR of 2 * n_nodes rows that ends at n_edges, a row that is not strictly ascending or names an id >= 2 * n_nodes, "
+                         "or an edge whose twin is missing");
     // 2. links, 3. ranking
-    hipLaunchKernelGGL(link_kernel, dim3(grid), dim3(UT), 0, st, d_row_off, d_dst, n_ids, next, buf[0], d_links);
-    if (hipGetLastError() != hipSuccess) UNITIG_FAIL();
+    hipLaunchKernelGGL(link_kernel, dim3(grid), dim3(UT), 0, c.st, d_row_off, d_dst, n_ids, next, buf[0], d_links);
+    c.launched();
+    if (!c.ok()) return c.device_error();
     int cur = 0;
     uint32_t rounds = 0;
-    int left = rank_rounds(ctx, buf, &cur, n_ids, cnt, &rounds);
+    int left = rank_rounds(c, buf, &cur, n_ids, cnt, &rounds);
     if (left == 1) { // 4. cycles: cut each at its smallest member, rank again
-        hipLaunchKernelGGL(cyc_init_kernel, dim3(grid), dim3(UT), 0, st, buf[cur], next, n_ids);
-        e = hipMemsetAsync(cnt, 0, CNT_WORDS * 8, st);
+        hipLaunchKernelGGL(cyc_init_kernel, dim3(grid), dim3(UT), 0, c.st, buf[cur], next, n_ids);
+        c.zero(cnt, CNT_WORDS * 8);
         bool still = true;
-        for (int r = 0; still && e == hipSuccess && r < MAX_ROUNDS;) {
+        for (int r = 0; still && c.ok() && r < MAX_ROUNDS;) {
             unsigned long long h[4];
             const int first = r;
             for (int i = 0; i < 4 && r < MAX_ROUNDS; i++, r++) {
-                hipLaunchKernelGGL(cyc_min_kernel, dim3(grid), dim3(UT), 0, st, buf[cur], buf[cur ^ 1], n_ids, cnt + r);
+                hipLaunchKernelGGL(cyc_min_kernel, dim3(grid), dim3(UT), 0, c.st, buf[cur], buf[cur ^ 1], n_ids, cnt + r);
                 cur ^= 1;
             }
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(h, cnt + first, (size_t)(r - first) * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = ctx_sync(ctx);
+            c.launched();
+            c.fetch(h, cnt + first, (size_t)(r - first) * 8);
+            c.sync();
             rounds += (uint32_t)(r - first);
-            for (int i = 0; e == hipSuccess && i < r - first; i++) still = still && h[i] != 0;
+            for (int i = 0; c.ok() && i < r - first; i++) still = still && h[i] != 0;
         }
-        if (e != hipSuccess || still) UNITIG_FAIL();
-        hipLaunchKernelGGL(cyc_cut_kernel, dim3(grid), dim3(UT), 0, st, buf[cur], next, n_ids);
-        if (hipGetLastError() != hipSuccess) UNITIG_FAIL();
-        left = rank_rounds(ctx, buf, &cur, n_ids, cnt, &rounds);
+        if (!c.ok() || still) return c.device_error();
+        hipLaunchKernelGGL(cyc_cut_kernel, dim3(grid), dim3(UT), 0, c.st, buf[cur], next, n_ids);
+        c.launched();
+        if (!c.ok()) return c.device_error();
+        left = rank_rounds(c, buf, &cur, n_ids, cnt, &rounds);
     }
-    if (left != 0) {
-        fail = "s2k_graph_unitigs: the list ranking did not end";
-        UNITIG_FAIL();
-    }
+    if (left != 0) return c.device_error("the list ranking did not end");
     g_rounds = rounds;
     STEP(1);
     // 5. numbering
     const unsigned long long *rank = buf[cur];
     uint64_t *number = (uint64_t *)buf[cur ^ 1];
-    hipLaunchKernelGGL(head_kernel, dim3(grid), dim3(UT), 0, st, rank, next, n_ids, flag);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = launch_scan_u32(flag, n_ids, number, scan_tmp, 0, st);
+    hipLaunchKernelGGL(head_kernel, dim3(grid), dim3(UT), 0, c.st, rank, next, n_ids, flag);
+    c.launched();
+    c.scan(flag, n_ids, number, scan_tmp);
     uint64_t total = 0, links = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, number + n_ids, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&links, d_links, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) UNITIG_FAIL();
+    c.fetch(&total, number + n_ids, 8);
+    c.fetch(&links, d_links, 8);
+    if (!c.sync()) return c.device_error();
     STEP(2);
-    if (total > n_nodes) { // every unitig holds a node
-        fail = "s2k_graph_unitigs: internal error (more unitigs than nodes)";
-        UNITIG_FAIL();
-    }
+    if (total > n_nodes) return c.device_error("internal error (more unitigs than nodes)"); // every unitig holds a node
     *n_unitigs = total;
     *n_links = links;
     if (!want) return S2K_OK;
     if (total > out->capacity) return S2K_ERR_CAPACITY;
-    hipLaunchKernelGGL(len_kernel, dim3(grid), dim3(UT), 0, st, rank, next, n_ids, flag, number, len);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = launch_scan_u32(len, total, uoff, scan_tmp, 0, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(scatter_kernel, dim3(grid), dim3(UT), 0, st, rank, next, n_ids, number, uoff, out->members, out->node_unitig, out->node_pos,
-                           out->circular);
-        e = hipGetLastError();
+    hipLaunchKernelGGL(len_kernel, dim3(grid), dim3(UT), 0, c.st, rank, next, n_ids, flag, number, len);
+    c.launched();
+    c.scan(len, total, uoff, scan_tmp);
+    if (c.ok()) {
+        hipLaunchKernelGGL(scatter_kernel, dim3(grid), dim3(UT), 0, c.st, rank, next, n_ids, number, uoff, out->members, out->node_unitig,
+                           out->node_pos, out->circular);
+        c.launched();
     }
-    if (e == hipSuccess && out->uni_off) e = hipMemcpyAsync(out->uni_off, uoff, (total + 1) * 8, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) UNITIG_FAIL();
+    if (out->uni_off) c.copy(out->uni_off, uoff, (total + 1) * 8, hipMemcpyDeviceToDevice);
+    if (!c.sync()) return c.device_error();
     STEP(3);
     return S2K_OK;
-#undef UNITIG_FAIL
 #undef STEP
 }
 
@@ -476,47 +425,33 @@ s2k_status s2k_graph_unitig_edges(s2k_ctx *ctx, const uint64_t *d_row_off, const
     if (n_out) *n_out = 0;
     if (!ctx || !n_out || !d_row_off || !d_uni_off || (n_edges && !d_dst)) return S2K_ERR_INVALID_ARG;
     if (n_unitigs && (!d_members || !d_node_unitig || !d_node_pos)) return S2K_ERR_INVALID_ARG;
-    if (n_nodes >= (1ull << 31) || n_unitigs > n_nodes) {
-        ctx_set_error(ctx, "s2k_graph_unitig_edges: 2^31 nodes or more, or more unitigs than nodes");
-        return S2K_ERR_INVALID_ARG;
-    }
+    Call c(ctx, "s2k_graph_unitig_edges");
+    if (n_nodes >= (1ull << 31) || n_unitigs > n_nodes) return c.invalid("2^31 nodes or more, or more unitigs than nodes");
     if (n_unitigs == 0 || n_edges == 0) return S2K_OK;
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
-    hipStream_t st = ctx_stream(ctx);
     const uint64_t n_orient = 2 * n_unitigs;
-    size_t off = 0;
-    const size_t oC = off; off += al(n_orient * 4);
-    const size_t oO = off; off += al((n_orient + 1) * 8);
-    const size_t oT = off; off += al(scan_tmp_bytes(n_orient));
-    char *w = (char *)ctx_count_table(ctx, off);
-    if (!w) {
-        ctx_set_error(ctx, "s2k_graph_unitig_edges: workspace allocation");
-        return S2K_ERR_NOMEM;
-    }
-    uint32_t *cnt = (uint32_t *)(w + oC);
-    uint64_t *eoff = (uint64_t *)(w + oO);
+    Layout L;
+    const auto cnt_p = L.take<uint32_t>(n_orient);
+    const auto off_p = L.take<uint64_t>(n_orient + 1);
+    const auto tmp_p = L.bytes<uint64_t>(scan_tmp_bytes(n_orient));
+    char *w = L.alloc(ctx);
+    if (!w) return c.nomem();
+    uint32_t *cnt = cnt_p(w);
+    uint64_t *eoff = off_p(w);
     const UnitigView g{d_row_off, d_dst, d_uni_off, d_members, d_node_unitig, d_node_pos};
     const unsigned grid = grid_for(n_orient);
-    hipLaunchKernelGGL(uedge_count_kernel, dim3(grid), dim3(UT), 0, st, g, n_orient, cnt);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = launch_scan_u32(cnt, n_orient, eoff, (uint64_t *)(w + oT), 0, st);
+    hipLaunchKernelGGL(uedge_count_kernel, dim3(grid), dim3(UT), 0, c.st, g, n_orient, cnt);
+    c.launched();
+    c.scan(cnt, n_orient, eoff, tmp_p(w));
     uint64_t total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, eoff + n_orient, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_graph_unitig_edges: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    c.fetch(&total, eoff + n_orient, 8);
+    if (!c.sync()) return c.device_error();
     *n_out = total;
     if (!d_keys || total == 0) return S2K_OK;
     if (total > capacity) return S2K_ERR_CAPACITY;
-    hipLaunchKernelGGL(uedge_write_kernel, dim3(grid), dim3(UT), 0, st, g, n_orient, cnt, eoff, d_keys, d_src_edge);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = ctx_sync(ctx);
-    if (e != hipSuccess) {
-        ctx_set_error(ctx, "s2k_graph_unitig_edges: HIP error");
-        return S2K_ERR_DEVICE;
-    }
+    hipLaunchKernelGGL(uedge_write_kernel, dim3(grid), dim3(UT), 0, c.st, g, n_orient, cnt, eoff, d_keys, d_src_edge);
+    c.launched();
+    if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
 
