@@ -478,6 +478,66 @@ s2k_status s2k_table_node_sequences(s2k_table *t, uint64_t n_reads, const s2k_de
 s2k_status s2k_unitig_sequences(s2k_ctx *ctx, const uint64_t *d_uni_off, const uint32_t *d_members, const uint8_t *d_circular,
                                 uint64_t n_unitigs, uint64_t n_nodes, const s2k_node_seqs *nodes, uint64_t *d_out_off, uint8_t *d_out,
                                 uint32_t *d_overlap, uint64_t capacity, uint64_t *n_bases);
+/* ---- read paths: the reads threaded through the unitig graph ------------------------------------------------------
+ * Node place.  For node i of a unitig decomposition (what s2k_graph_unitigs wrote) let t = node_unitig[i], p = node_pos[i], len =
+ * uni_off[t + 1] - uni_off[t] and o = members[uni_off[t] + p] & 1.  The forward oriented node 2 i lies on the oriented unitig U0 =
+ * 2 t + o at position q0 = o ? len - 1 - p : p; node 2 i + 1 lies on U0 ^ 1 at len - 1 - q0.  The record of node i is
+ * { unitig = U0, pos = q0, len, circular = circular[t] }, 16 bytes.
+ * Item place.  Item j of a read (hash h, strand rev) is solid iff h is in the table with a count of at least max(min_count, 1), the
+ * rule of s2k_table_filter and s2k_table_edges.  Its place, from the record of node index(h): U = U0 ^ rev, q = rev ? len - 1 - q0 :
+ * q0.
+ * Step.  Item j + 1 continues item j iff they are consecutive items of the same read, both are solid, U(j + 1) == U(j), and either
+ * q(j + 1) == q(j) + 1, or the unitig is circular, q(j) == len - 1 and q(j + 1) == 0.  A step is a maximal run of items each of which
+ * continues the one before it; a read's path is its steps in item order; a non-solid item belongs to no step.  (A loop on a unitig of
+ * one member gives two steps: a unitig of length 1 is never circular.)
+ * Step record, one entry per array: unitig = U; pos = q of the first item; count = the number of items; item = the first item's
+ * index in its read before filtering (the convention of s2k_solid_out.offset); flags bit 0 S2K_STEP_LINKED = the step's first item
+ * is consecutive with a solid item of the same read: the read crosses a graph adjacency into this step, not a gap; start = in->start
+ * of the first item, end = in->end of the last.
+ * Paths are in minimizer space: the base-space alignment of a read to a unitig's sequence is out of scope.
+ *
+ * Threading through a simplified graph needs no node map: make a table over the simplified graph's node keys (s2k_graph_induced
+ * writes them strictly ascending, so s2k_table_create accepts them), take its unitigs and their places, and thread against those --
+ * an item whose node was removed is not in that table and breaks the path like any other non-solid item. */
+typedef struct s2k_node_place {
+    uint32_t unitig;   /* the oriented unitig of the oriented node 2 i */
+    uint32_t pos;      /* its position there */
+    uint32_t len;      /* members of the unitig */
+    uint32_t circular; /* 0 / 1 */
+} s2k_node_place;
+/* d_place[i] (n_nodes records, 16-byte aligned) from the arrays s2k_graph_unitigs wrote over n_nodes nodes and n_unitigs unitigs.
+ * Checked on the device before anything is written, one flag word read by the host, S2K_ERR_INVALID_ARG otherwise: node_unitig[i] <
+ * n_unitigs, the unitig's members lie inside [0, n_nodes] and it holds one, node_pos[i] < len, members[uni_off[t] + p] >> 1 == i.
+ * n_nodes >= 2^31 is refused; n_nodes == 0 reads and writes nothing.  Workspace: 4 B of the context's grow-only count workspace.  Runs
+ * on the context's stream; returns when the records are written. */
+s2k_status s2k_unitig_node_places(s2k_ctx *ctx, const uint64_t *d_uni_off, const uint32_t *d_members, const uint32_t *d_node_unitig,
+                                  const uint32_t *d_node_pos, const uint8_t *d_circular, uint64_t n_nodes, uint64_t n_unitigs,
+                                  s2k_node_place *d_place);
+#define S2K_STEP_LINKED 1u
+typedef struct s2k_thread_out { /* device pointers; capacity in steps */
+    uint64_t capacity;
+    uint64_t *path_off; /* n_reads + 1, required: the steps of read r are [path_off[r], path_off[r + 1]) */
+    uint32_t *unitig;   /* every step array may be NULL */
+    uint32_t *pos;
+    uint32_t *count;
+    uint32_t *item;
+    uint32_t *flags;
+    uint32_t *start;
+    uint32_t *end;
+} s2k_thread_out;
+/* The paths of the reads of `in` (km_off, hash and rev required, km_off[0] == 0; start / end optional: out->start / out->end must be
+ * NULL when theirs is) through the unitigs whose places are d_place[0..n_nodes); node i is key i of the table, so n_nodes must equal
+ * the table's number of keys (S2K_ERR_INVALID_ARG otherwise; a table of 2^31 keys or more is refused).  *n_steps is always set and
+ * out->path_off always written; the step arrays are written only when *n_steps <= out->capacity, otherwise S2K_ERR_CAPACITY and
+ * nothing is written to them; all NULL asks for the sizes only.  d_uni_items (may be NULL; one uint64_t per unitig, n_unitigs of
+ * them): d_uni_items[U >> 1] += count for every step, by every call that returns S2K_OK (a sizes-only call included) -- the items
+ * each unitig carries; the caller zeroes it, and it accumulates over batches.  One integer atomic per step: sums do not depend on
+ * their order, so every output is a function of the input, bit-identical from call to call.  Checked on the device before anything
+ * is written (S2K_ERR_INVALID_ARG): every record a solid item uses names a unitig below n_unitigs and a position inside it.  d_place
+ * is otherwise trusted to be what s2k_unitig_node_places wrote.  Uses the context's grow-only count workspace (shared with
+ * s2k_count_device_ex): about 8.4 B per input item.  Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_table_thread(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t min_count, const s2k_node_place *d_place,
+                            uint64_t n_nodes, const s2k_thread_out *out, uint64_t *d_uni_items, uint64_t n_unitigs, uint64_t *n_steps);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

@@ -206,6 +206,13 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return n_bases;
     }
+    // s2k_unitig_node_places: d_place[i] (n_nodes 16-byte records) = where node i lies on the oriented unitigs, from the arrays
+    // graph_unitigs wrote.  Throws Error(S2K_ERR_INVALID_ARG) for arrays that are not a decomposition of the n_nodes nodes.
+    void unitig_node_places(const uint64_t *d_uni_off, const uint32_t *d_members, const uint32_t *d_node_unitig, const uint32_t *d_node_pos,
+                            const uint8_t *d_circular, uint64_t n_nodes, uint64_t n_unitigs, s2k_node_place *d_place) {
+        s2k_status st = s2k_unitig_node_places(ctx_, d_uni_off, d_members, d_node_unitig, d_node_pos, d_circular, n_nodes, n_unitigs, d_place);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:
@@ -279,6 +286,15 @@ class Table {
         uint64_t n_bytes = 0;
         check(s2k_table_node_sequences(t_, n_reads, &in, k, d_bases, d_read_off, ordinal_base, d_rep, nodes, pool_used, &n_bytes));
         return n_bytes;
+    }
+    // s2k_table_thread: each read's path through the unitigs whose node places are d_place (Engine::unitig_node_places; n_nodes = the
+    // table's keys): out.path_off always, the step arrays of `out` when they fit (all nullptr: the sizes only); d_uni_items (may be
+    // nullptr, one uint64_t per unitig) gains every step's count.  Returns the number of steps (throws on S2K_ERR_CAPACITY too).
+    uint64_t thread(uint64_t n_reads, const s2k_device_out &in, uint32_t min_count, const s2k_node_place *d_place, uint64_t n_nodes,
+                    const s2k_thread_out &out, uint64_t n_unitigs, uint64_t *d_uni_items = nullptr) {
+        uint64_t n_steps = 0;
+        check(s2k_table_thread(t_, n_reads, &in, min_count, d_place, n_nodes, &out, d_uni_items, n_unitigs, &n_steps));
+        return n_steps;
     }
     s2k_table *raw() { return t_; }
 

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "s2k_graph_unitigs", "s2k_graph_unitig_edges", "s2k_graph_unitigs_last_steps",
     "s2k_table_representatives", "s2k_table_node_sequences", "s2k_unitig_sequences",
     "s2k_graph_simplify_mask", "s2k_graph_induced",
+    "s2k_unitig_node_places", "s2k_table_thread",
 ]
 
 
@@ -48,6 +49,7 @@ FLAG_LEGACY_PATH = 8  # round-2 records (16 B with the read index, per-read scan
 FLAG_NO_PACK2 = 4  # s2k_extract: bases as ASCII over PCIe instead of 2-bit packed + exception list
 HPC_RLE_ALPHABET = 1  # s2k_hpc_device_ex: the run rule of encode_rle (src/hpc.rs:14)
 COUNT_SORTED = 1  # s2k_count_device_ex: pairs in ascending order of key
+STEP_LINKED = 1  # s2k_thread_out.flags: the step's first item follows a solid item of the same read
 
 
 class S2kError(RuntimeError):
@@ -96,6 +98,15 @@ class UnitigOut(C.Structure):
 class NodeSeqs(C.Structure):
     _fields_ = [("seq_off", C.c_void_p), ("seq_len", C.c_void_p), ("shift_fwd", C.c_void_p), ("shift_rev", C.c_void_p), ("rev", C.c_void_p),
                 ("pool", C.c_void_p), ("pool_capacity", C.c_uint64)]
+
+
+class ThreadOut(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("path_off", C.c_void_p), ("unitig", C.c_void_p), ("pos", C.c_void_p), ("count", C.c_void_p),
+                ("item", C.c_void_p), ("flags", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p)]
+
+
+# s2k_node_place: where the forward oriented node 2 i lies on the oriented unitigs
+NodePlace = np.dtype([("unitig", np.uint32), ("pos", np.uint32), ("len", np.uint32), ("circular", np.uint32)])
 
 
 _lib = None
@@ -184,6 +195,9 @@ def load_library(path=None):
                                            C.POINTER(NodeSeqs), C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_unitig_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(NodeSeqs), C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.s2k_unitig_node_places.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.s2k_table_thread.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(ThreadOut), C.c_void_p,
+                                   C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -575,6 +589,23 @@ class Engine:
             self._check(self.lib.s2k_unitig_sequences(*args, C.c_void_p(out.data_ptr()), C.c_void_p(overlap.data_ptr()), total, C.byref(nb)))
         return out_off, out[:total], overlap[:2 * t]
 
+    def unitig_node_places(self, uni_off, members, node_unitig, node_pos, circular):
+        """Where every node lies on the oriented unitigs (s2k_unitig_node_places), from the arrays graph_unitigs returned -> int32 GPU
+        tensor of shape (n_nodes, 4): row i is the NodePlace record (unitig, pos, len, circular) of the forward oriented node 2 i.
+        S2kError(1) when the arrays are not a decomposition of the nodes."""
+        import torch
+
+        uni_off, members, node_unitig, node_pos, circular = (x.contiguous() for x in (uni_off, members, node_unitig, node_pos, circular))
+        n, t, dev = node_unitig.numel(), circular.numel(), uni_off.device
+        if uni_off.numel() != t + 1 or members.numel() != n or node_pos.numel() != n or uni_off.element_size() != 8 or members.element_size() != 4:
+            raise ValueError("unitig_node_places wants uni_off (n_unitigs + 1, 64-bit), members / node_unitig / node_pos (n_nodes, 32-bit), circular")
+        place = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_unitig_node_places(self.ctx, *(C.c_void_p(x.data_ptr() if x.numel() else 0) for x in (uni_off, members, node_unitig,
+                                                                                                                      node_pos, circular)),
+                                                    n, t, C.c_void_p(place.data_ptr())))
+        return place[:n]
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -738,6 +769,32 @@ class CountTable:
         self.engine._check(self.lib.s2k_table_edges(self.handle, n_reads, C.byref(i), int(min_count), C.c_void_p(keys.data_ptr()), cap,
                                                     C.byref(ne)))
         return keys[:int(ne.value)]
+
+
+    def thread(self, out_tensors, n_reads, place, n_unitigs, out, min_count=2, uni_items=None):
+        """The reads' paths through a unitig decomposition of this table's keys (s2k_table_thread; the definitions are in include/s2k.h).
+        out_tensors: the GPU tensors extract_device wrote (km_off, hash, rev; start / end when `out` asks for them); place: what
+        Engine.unitig_node_places returned for the decomposition; out: a ThreadOut naming the arrays to fill (path_off required; all step
+        arrays 0: the sizes only); uni_items: int64 GPU tensor, one entry per unitig, that gains every step's count.  -> the number of
+        steps.  S2kError(7) when out.capacity is short: nothing was written to the step arrays."""
+        import torch
+
+        dev = out_tensors["km_off"].device
+        if place.numel() != 4 * self.n or place.element_size() != 4 or not place.is_contiguous():
+            raise ValueError("thread wants the (n_keys, 4) 32-bit place tensor of Engine.unitig_node_places")
+        if uni_items is not None and (uni_items.numel() != int(n_unitigs) or uni_items.element_size() != 8 or not uni_items.is_contiguous()):
+            raise ValueError("uni_items holds one 64-bit entry per unitig")
+        i = DeviceOut()
+        i.km_capacity = int(out_tensors["km_off"][n_reads].item()) if n_reads else 0
+        for f in ("km_off", "hash", "rev", "start", "end"):
+            if out_tensors.get(f) is not None:
+                setattr(i, f, out_tensors[f].data_ptr())
+        ns = C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self.engine._check(self.lib.s2k_table_thread(self.handle, n_reads, C.byref(i), int(min_count), C.c_void_p(place.data_ptr() if self.n else 0),
+                                                     self.n, C.byref(out), C.c_void_p(uni_items.data_ptr() if uni_items is not None and n_unitigs else 0),
+                                                     int(n_unitigs), C.byref(ns)))
+        return int(ns.value)
 
 
 def _seq_in(o, n_reads):
@@ -972,6 +1029,36 @@ class UnitigGraph:
         out_off, out, self.overlap = engine.unitig_sequences(self.uni_off, self.members, self.circular, n, node_seqs)
         return out_off, out
 
+    def places(self, engine):
+        """Where every node of the compacted graph lies on the oriented unitigs (Engine.unitig_node_places), computed once and kept"""
+        if getattr(self, "_places", None) is None:
+            self._places = engine.unitig_node_places(self.uni_off, self.members, self.node_unitig, self.node_pos, self.circular)
+        return self._places
+
+    def thread(self, engine, table, outs, n_reads, min_count=2, coverage=None):
+        """One batch of reads threaded through this graph on the device (CountTable.thread) -> ReadPaths.  table: the CountTable over the
+        node keys of the KminmerGraph this one was compacted from; outs: the GPU tensors extract_device wrote for the batch (km_off,
+        hash, rev; start / end are carried into the steps when present); min_count: the cutoff the graph was built with; coverage: an
+        int64 GPU tensor of n_unitigs zeros that gains the items every unitig carries, batch after batch.  Two calls: the sizes, then
+        the arrays.
+        Through a simplified graph, with no node map: sg, _, _ = graph.simplify(...); t = CountTable(engine, sg.keys, sg.counts);
+        sg.unitigs(engine).thread(engine, t, outs, n_reads) -- an item whose node was removed is not in t and breaks the path like any
+        non-solid item."""
+        import torch
+
+        dev = outs["km_off"].device
+        place = self.places(engine)
+        o = ThreadOut()
+        path_off = torch.empty(n_reads + 1, dtype=torch.int64, device=dev)
+        o.path_off = path_off.data_ptr()
+        n = table.thread(outs, n_reads, place, self.n_unitigs, o, min_count)
+        res = {f: torch.empty(max(n, 1), dtype=torch.int32, device=dev) for f in ReadPaths.STEP_FIELDS if f not in ("start", "end") or outs.get(f) is not None}
+        o.capacity = n
+        for f, t in res.items():
+            setattr(o, f, t.data_ptr())
+        table.thread(outs, n_reads, place, self.n_unitigs, o, min_count, uni_items=coverage)
+        return ReadPaths(path_off, **{f: t[:n] for f, t in res.items()})
+
     def write_gfa(self, path, members=False, sequences=None):
         """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
         members=True an nd:Z: tag that lists node index and orientation in path order) and an L line per twin pair of edges, by the rule
@@ -984,6 +1071,50 @@ class UnitigGraph:
             seq = (sequences[0].cpu().numpy().view(np.uint64), sequences[1].cpu().numpy(), self.overlap.cpu().numpy().view(np.uint32))
         write_unitig_gfa(path, self.uni_off.cpu().numpy().view(np.uint64), self.members.cpu().numpy().view(np.uint32), self.counts.cpu().numpy(),
                          self.edge_keys.cpu().numpy().view(np.uint64), self.edge_counts.cpu().numpy().view(np.uint32), members=members, sequences=seq)
+
+
+class ReadPaths:
+    """The paths of one batch of reads (UnitigGraph.thread; include/s2k.h: s2k_table_thread): the steps of read r are path_off[r] ..
+    path_off[r + 1]; step s runs along the oriented unitig unitig[s] (2 t + strand) from position pos[s] over count[s] items, its first
+    item is item[s] of the read, flags[s] & STEP_LINKED tells that the read entered it over a graph adjacency (not a gap), start[s] /
+    end[s] (None when the extraction kept none) are the read's bases it covers.  GPU tensors: path_off int64, the rest int32 holding
+    the uint32 values."""
+
+    STEP_FIELDS = ("unitig", "pos", "count", "item", "flags", "start", "end")
+
+    def __init__(self, path_off, unitig, pos, count, item, flags, start=None, end=None):
+        self.path_off, self.unitig, self.pos, self.count, self.item, self.flags, self.start, self.end = path_off, unitig, pos, count, item, flags, start, end
+
+    @property
+    def n_steps(self):
+        return self.unitig.numel()
+
+    def host(self):
+        """-> dict of numpy arrays: path_off uint64, the step arrays uint32 (start / end only when present)"""
+        d = {"path_off": self.path_off.cpu().numpy().view(np.uint64)}
+        for f in self.STEP_FIELDS:
+            if getattr(self, f) is not None:
+                d[f] = getattr(self, f).cpu().numpy().view(np.uint32)
+        return d
+
+    def write_paths(self, path, first_read=0):
+        """One line per read (write_read_paths): read_index <tab> n_steps <tab> path; first_read = the index of the batch's first read"""
+        h = self.host()
+        write_read_paths(path, h["path_off"], h["unitig"], h["pos"], h["count"], h["flags"], first_read=first_read)
+
+
+def write_read_paths(path, path_off, unitig, pos, count, flags, first_read=0):
+    """ReadPaths.write_paths on host arrays.  One line per read: first_read + r, its number of steps, and its steps concatenated, each
+    >t (oriented unitig 2 t) or <t (2 t + 1) followed by :pos+count; a step the read did not enter over a graph adjacency (no
+    STEP_LINKED) is preceded by *, except the read's first.  A read without steps gets an empty path."""
+    off = np.asarray(path_off).astype(np.int64).tolist()
+    u, p, c, f = (np.asarray(x).astype(np.int64).tolist() for x in (unitig, pos, count, flags))
+    with open(path, "w") as out:
+        for r in range(len(off) - 1):
+            a, b = off[r], off[r + 1]
+            steps = "".join("%s%s%d:%d+%d" % ("" if s == a or f[s] & STEP_LINKED else "*", "<" if u[s] & 1 else ">", u[s] >> 1, p[s], c[s])
+                            for s in range(a, b))
+            out.write("%d\t%d\t%s\n" % (first_read + r, b - a, steps))
 
 
 _REVCOMP = np.arange(256, dtype=np.uint8)

@@ -76,6 +76,14 @@ __device__ __forceinline__ uint32_t tile_slots(const CompactWs &ws, uint64_t t0,
     return keep;
 }
 
+// kept items before input index j (j <= n_items), once launch_scan_u32 has written tile_off
+__device__ inline uint64_t kept_before(const CompactWs &ws, uint64_t n_items, uint64_t n_tiles, uint64_t j) {
+    if (j >= n_items) return ws.tile_off[n_tiles];
+    const uint64_t w = j >> 6;
+    const uint64_t below = (j & 63) ? ws.wmask[w] & ((1ull << (j & 63)) - 1ull) : 0ull;
+    return ws.tile_off[j / TB_TILE] + ws.wpre[w] + (uint64_t)__popcll(below);
+}
+
 // elements between p and the 16-byte boundary below it
 template <typename T>
 __device__ __forceinline__ uint32_t shift_of(const T *p) {

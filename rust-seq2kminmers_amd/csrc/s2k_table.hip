@@ -104,19 +104,11 @@ __global__ __launch_bounds__(TB_THREADS) void filter_count_kernel(TableView tv, 
     tile_prefixes(wc, t0, n_items, ws.c);
 }
 
-// kept items before input index j (j <= n_items)
-__device__ inline uint64_t kept_before(const FilterWs &ws, uint64_t n_items, uint64_t n_tiles, uint64_t j) {
-    if (j >= n_items) return ws.c.tile_off[n_tiles];
-    const uint64_t w = j >> 6;
-    const uint64_t below = (j & 63) ? ws.c.wmask[w] & ((1ull << (j & 63)) - 1ull) : 0ull;
-    return ws.c.tile_off[j / TB_TILE] + ws.c.wpre[w] + (uint64_t)__popcll(below);
-}
-
 __global__ __launch_bounds__(256) void filter_offsets_kernel(const uint64_t *__restrict__ km_off, uint64_t n_reads, uint64_t n_items, uint64_t n_tiles,
                                                              FilterWs ws, uint64_t *__restrict__ o_km_off) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r > n_reads) return;
-    o_km_off[r] = kept_before(ws, n_items, n_tiles, km_off[r]);
+    o_km_off[r] = kept_before(ws.c, n_items, n_tiles, km_off[r]);
 }
 
 struct FilterIo {
@@ -208,17 +200,6 @@ struct EdgeWs {
     uint32_t *node; // per item: its oriented node 2 * rank + rev, TB_NONE when it is not solid
     CompactWs c;    // wmask: the items j for which (j, j + 1) is an adjacency; wpre, tile_kept: keys emitted, not items
 };
-
-// the first r in [0, n_reads] with km_off[r] > x (n_reads + 1 if there is none)
-__device__ inline uint64_t reads_upto(const uint64_t *__restrict__ km_off, uint64_t n_reads, uint64_t x) {
-    uint64_t lo = 0, hi = n_reads + 1;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (km_off[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // Items j and j + 1 form an adjacency when both are solid and j + 1 starts no read.  The tile's items and one halo item (the next
 // tile's first, looked up by lane 0) go to LDS as oriented nodes; the read starts inside (t0, t0 + TB_TILE] are marked from the reads

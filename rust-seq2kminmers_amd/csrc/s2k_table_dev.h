@@ -1,6 +1,6 @@
 // s2k_table_dev.h -- the count table's device view and its fused look-ups, shared by the translation units that search a table
-// (s2k_table.hip: look-up, filter, edges; s2k_seq.hip: representatives, node sequences), and the search of km_off that maps an
-// item to its read.  The tile geometry (TB_THREADS, TB_Q, TB_TILE, TB_WORDS) comes from s2k_compact_dev.h.  DESIGN.md §3.8.
+// (s2k_table.hip: look-up, filter, edges; s2k_seq.hip: representatives, node sequences; s2k_thread.hip: read paths), and the searches
+// of km_off that map an item to its read and a tile to the reads that start in it.  The tile geometry (TB_THREADS, TB_Q, TB_TILE, TB_WORDS) comes from s2k_compact_dev.h.  DESIGN.md §3.8.
 #pragma once
 #include <algorithm>
 
@@ -104,6 +104,17 @@ __device__ inline uint64_t read_of(const uint64_t *__restrict__ km_off, uint64_t
         const uint64_t mid = (lo + hi + 1) >> 1;
         if (km_off[mid] <= j) lo = mid;
         else hi = mid - 1;
+    }
+    return lo;
+}
+
+// the first r in [0, n_reads] with km_off[r] > x (n_reads + 1 if there is none)
+__device__ inline uint64_t reads_upto(const uint64_t *__restrict__ km_off, uint64_t n_reads, uint64_t x) {
+    uint64_t lo = 0, hi = n_reads + 1;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (km_off[mid] <= x) lo = mid + 1;
+        else hi = mid;
     }
     return lo;
 }
