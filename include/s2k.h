@@ -46,6 +46,7 @@ extern "C" {
  * (s2k_graph_unitigs, s2k_graph_unitig_edges, s2k_graph_unitigs_last_steps and the struct s2k_unitig_out were added the same way:
  * added entry points and one new struct, the version stays 2.)
  * (s2k_table_representatives, s2k_table_node_sequences, s2k_unitig_sequences and the struct s2k_node_seqs were added the same way.)
+ * (s2k_paths_spans and s2k_graph_resolve_mask were added the same way: added entry points, the version stays 2.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -538,6 +539,55 @@ typedef struct s2k_thread_out { /* device pointers; capacity in steps */
  * s2k_count_device_ex): about 8.4 B per input item.  Runs on the context's stream; returns when the outputs are written. */
 s2k_status s2k_table_thread(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t min_count, const s2k_node_place *d_place,
                             uint64_t n_nodes, const s2k_thread_out *out, uint64_t *d_uni_items, uint64_t n_unitigs, uint64_t *n_steps);
+/* ---- junction spans: which reads cross a unitig, and which repeats they resolve ------------------------------------
+ * Inputs: the path arrays s2k_table_thread wrote (path_off, unitig, pos, count, flags of an s2k_thread_out; n_reads, n_steps), the CSR
+ * over the 2 T oriented unitigs (d_row_off, d_dst, n_edges: what s2k_graph_adjacency writes from the keys of s2k_graph_unitig_edges;
+ * twin-symmetric, every row strictly ascending) and d_uni_off, len[t] = uni_off[t + 1] - uni_off[t].
+ * Edge index: the index of an edge in d_dst.  find(A, B) = the index of B in the row of A, or none.  For e = (A -> B), tw(e) =
+ * find(B ^ 1, A ^ 1): the same adjacency read on the other strand.
+ * Step s follows edge e iff all of these hold: s > path_off[r] (it is not its read's first step); flags[s] & S2K_STEP_LINKED; pos[s]
+ * == 0; pos[s - 1] + count[s - 1] == len[unitig[s - 1] >> 1]; e = find(unitig[s - 1], unitig[s]) exists.  A linked step that follows
+ * no edge is off-graph (a jump inside a unitig, or paths threaded against another graph than this CSR): it is counted, never an
+ * error.  A circular unitig has an empty row in a valid graph, so it never qualifies.
+ * Edge support: d_edge_support[e] += 1 for every step that follows e, and d_edge_support[tw(e)] += 1 when tw(e) != e (a hairpin is
+ * its own twin: counted once).  On the reads a graph was built from, with the same min_count and min_edge_count 1, it equals the
+ * graph's edge counts entry for entry.
+ * Span: step s spans its unitig V = unitig[s] iff it follows an edge a, step s + 1 is of the same read and follows an edge b, and
+ * count[s] == len[V >> 1] (V was traversed whole).  The span gives the key a << 32 | b and then the key of its twin, tw(b) << 32 |
+ * tw(a): the same read on the other strand.  A span is never its own twin (tw(a) leaves V ^ 1, b leaves V), so every span gives
+ * exactly two keys.  Keys come in step order, bit-identical from call to call.  Counting them (s2k_count_device_ex sorted, or an
+ * s2k_counter over batches) gives the span table, count(a, b) == count(tw b, tw a).
+ *
+ * s2k_paths_spans: *n_keys, *n_followed (steps that follow an edge) and *n_off_graph are always set.  d_span_keys NULL asks for the
+ * sizes only; *n_keys > capacity is S2K_ERR_CAPACITY and nothing is written, to the keys or to d_edge_support.  d_edge_support (may be
+ * NULL; n_edges uint64_t) is the caller's: zeroed before the first batch, it accumulates over the calls that return S2K_OK (a
+ * sizes-only call included).  Checked on the device before anything is written, one flag word read by the host, S2K_ERR_INVALID_ARG
+ * otherwise: path_off[0] == 0, non-decreasing, path_off[n_reads] == n_steps; every unitig[s] < 2 n_unitigs; the row_off rules of
+ * s2k_graph_simplify_mask, every id below 2 n_unitigs; uni_off strictly ascending.  paths->path_off is required, and with n_steps > 0
+ * paths->unitig, pos, count and flags.  n_unitigs >= 2^31 and n_edges >= 2^32 (a key holds two edge indices) are refused.  Twin
+ * symmetry and the order inside a row are trusted.  Slots come from ballots and scans and the only atomics are integer sums: every
+ * output is a function of the input.  Uses the context's grow-only count workspace: about 4.2 B per step.  Runs on the context's
+ * stream; returns when the outputs are written. */
+s2k_status s2k_paths_spans(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *paths, uint64_t n_steps, const uint64_t *d_row_off,
+                           const uint32_t *d_dst, uint64_t n_edges, const uint64_t *d_uni_off, uint64_t n_unitigs, uint64_t *d_span_keys,
+                           uint64_t capacity, uint64_t *d_edge_support, uint64_t *n_keys, uint64_t *n_followed, uint64_t *n_off_graph);
+/* Resolution, decided per oriented unitig V from a span table (d_span_keys strictly ascending, d_span_counts) and min_support (0 and
+ * 1 both mean 1).  sup(a, b) = the count of the key a << 32 | b, or 0; a pair is supported iff sup >= min_support.  in(V) = out(V ^
+ * 1); the in-edges of V are the twins of the edges that leave V ^ 1.  V is a candidate iff in(V) >= 2 and out(V) >= 2.  V is resolved
+ * iff it is a candidate, in(V) == out(V), no predecessor or successor is of V's own unitig, and the supported pairs are a perfect
+ * matching: every in-edge has exactly one supported out-edge and every out-edge exactly one supported in-edge.  Unitig t is resolved
+ * iff both 2 t and 2 t + 1 are (with a twin-symmetric span table they agree).
+ * d_resolved[t] (may be NULL): one byte per unitig, 0 / 1.  d_partner[e] (may be NULL; n_edges entries): the out-edge matched to e
+ * when e enters a resolved oriented unitig, S2K_NO_PARTNER otherwise; partner[tw(partner[a])] == tw(a).  *n_candidates and
+ * *n_resolved, counted in unitigs, are always set.  Checked on the device before anything is written (S2K_ERR_INVALID_ARG): the
+ * row_off rules and ids as above; span keys strictly ascending, both halves < n_edges, the out half in the row of the unitig that
+ * the in half enters.  n_unitigs >= 2^31 and n_edges >= 2^32 are refused.  One lane per oriented unitig; a hub is slow (quadratic in
+ * its degree), never wrong.  Workspace: 32 B of the context's grow-only count workspace.  Runs on the context's stream; returns when
+ * the outputs are written.  Duplicating a resolved unitig (the graph surgery) is not part of this call. */
+#define S2K_NO_PARTNER 0xFFFFFFFFu
+s2k_status s2k_graph_resolve_mask(s2k_ctx *ctx, const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs,
+                                  const uint64_t *d_span_keys, const uint32_t *d_span_counts, uint64_t n_spans, uint32_t min_support,
+                                  uint8_t *d_resolved, uint32_t *d_partner, uint64_t *n_candidates, uint64_t *n_resolved);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

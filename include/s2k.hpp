@@ -213,6 +213,35 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         s2k_status st = s2k_unitig_node_places(ctx_, d_uni_off, d_members, d_node_unitig, d_node_pos, d_circular, n_nodes, n_unitigs, d_place);
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
     }
+    // s2k_paths_spans: the span keys of the paths of one batch (the arrays of Table::thread) over the CSR of the oriented unitigs; d_span_keys
+    // nullptr: the sizes only; d_edge_support (may be nullptr, one uint64_t per edge) gains the steps that follow every edge and its twin.
+    // Throws on S2K_ERR_CAPACITY too (nothing written).
+    struct SpanTotals {
+        uint64_t keys, followed, off_graph;
+    };
+    SpanTotals paths_spans(uint64_t n_reads, const s2k_thread_out &paths, uint64_t n_steps, const uint64_t *d_row_off, const uint32_t *d_dst,
+                           uint64_t n_edges, const uint64_t *d_uni_off, uint64_t n_unitigs, uint64_t *d_span_keys = nullptr, uint64_t capacity = 0,
+                           uint64_t *d_edge_support = nullptr) {
+        SpanTotals t{};
+        s2k_status st = s2k_paths_spans(ctx_, n_reads, &paths, n_steps, d_row_off, d_dst, n_edges, d_uni_off, n_unitigs, d_span_keys, capacity,
+                                        d_edge_support, &t.keys, &t.followed, &t.off_graph);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
+    // s2k_graph_resolve_mask: the unitigs whose in- and out-edges a span table (keys strictly ascending, counts) pairs one to one;
+    // d_resolved (one byte per unitig) and d_partner (one uint32_t per edge, S2K_NO_PARTNER where there is none) may be nullptr.
+    struct ResolveTotals {
+        uint64_t candidates, resolved;
+    };
+    ResolveTotals graph_resolve_mask(const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs,
+                                     const uint64_t *d_span_keys, const uint32_t *d_span_counts, uint64_t n_spans, uint32_t min_support,
+                                     uint8_t *d_resolved, uint32_t *d_partner) {
+        ResolveTotals t{};
+        s2k_status st = s2k_graph_resolve_mask(ctx_, d_row_off, d_dst, n_edges, n_unitigs, d_span_keys, d_span_counts, n_spans, min_support,
+                                               d_resolved, d_partner, &t.candidates, &t.resolved);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "s2k_table_representatives", "s2k_table_node_sequences", "s2k_unitig_sequences",
     "s2k_graph_simplify_mask", "s2k_graph_induced",
     "s2k_unitig_node_places", "s2k_table_thread",
+    "s2k_paths_spans", "s2k_graph_resolve_mask",
 ]
 
 
@@ -50,6 +51,7 @@ FLAG_NO_PACK2 = 4  # s2k_extract: bases as ASCII over PCIe instead of 2-bit pack
 HPC_RLE_ALPHABET = 1  # s2k_hpc_device_ex: the run rule of encode_rle (src/hpc.rs:14)
 COUNT_SORTED = 1  # s2k_count_device_ex: pairs in ascending order of key
 STEP_LINKED = 1  # s2k_thread_out.flags: the step's first item follows a solid item of the same read
+NO_PARTNER = 0xFFFFFFFF  # s2k_graph_resolve_mask: d_partner of an edge that enters no resolved unitig
 
 
 class S2kError(RuntimeError):
@@ -198,6 +200,10 @@ def load_library(path=None):
     L.s2k_unitig_node_places.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_table_thread.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(ThreadOut), C.c_void_p,
                                    C.c_uint64, C.POINTER(C.c_uint64)]
+    L.s2k_paths_spans.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ThreadOut), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_graph_resolve_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -605,6 +611,60 @@ class Engine:
                                                                                                                       node_pos, circular)),
                                                     n, t, C.c_void_p(place.data_ptr())))
         return place[:n]
+
+    def paths_spans(self, unitig_graph, paths, edge_support=None):
+        """The span keys of one batch's ReadPaths over a UnitigGraph (s2k_paths_spans; the definitions are in include/s2k.h): for every
+        step that crosses its whole unitig from an in-edge a to an out-edge b the key a << 32 | b, then its twin's.  Two calls: the
+        sizes, then the keys.  edge_support: an int64 GPU tensor of n_edges entries (zeroed by the caller) that gains the steps that
+        follow every edge and its twin.  -> (keys, n_followed, n_off_graph): int64 GPU tensor in step order, and the linked steps that
+        follow an edge / follow none."""
+        import torch
+
+        ug, dev = unitig_graph, paths.path_off.device
+        t, ne, ns, nr = ug.n_unitigs, ug.dst.numel(), paths.n_steps, paths.path_off.numel() - 1
+        row_off, dst, uni_off = ug.row_off.contiguous(), ug.dst.contiguous(), ug.uni_off.contiguous()
+        if row_off.numel() != 2 * t + 1 or row_off.element_size() != 8 or dst.element_size() != 4 or uni_off.numel() != t + 1:
+            raise ValueError("paths_spans wants a UnitigGraph: the CSR over its oriented unitigs and uni_off")
+        if edge_support is not None and (edge_support.numel() != ne or edge_support.element_size() != 8 or not edge_support.is_contiguous()):
+            raise ValueError("edge_support holds one 64-bit entry per edge")
+        o = ThreadOut()
+        o.capacity = ns
+        keep = {f: getattr(paths, f).contiguous() for f in ("path_off", "unitig", "pos", "count", "flags")}
+        for f, x in keep.items():
+            setattr(o, f, x.data_ptr() if x.numel() else 0)
+        nk, nf, no = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        args = (self.ctx, nr, C.byref(o), ns, C.c_void_p(row_off.data_ptr()), C.c_void_p(dst.data_ptr() if ne else 0), ne,
+                C.c_void_p(uni_off.data_ptr()), t)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_paths_spans(*args, None, 0, None, C.byref(nk), C.byref(nf), C.byref(no)))
+        n = int(nk.value)
+        keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_paths_spans(*args, C.c_void_p(keys.data_ptr()), n, C.c_void_p(edge_support.data_ptr() if edge_support is not None and ne else 0),
+                                             C.byref(nk), C.byref(nf), C.byref(no)))
+        return keys[:n], int(nf.value), int(no.value)
+
+    def graph_resolve_mask(self, unitig_graph, span_keys, span_counts, min_support=2):
+        """Which unitigs of a UnitigGraph a span table resolves (s2k_graph_resolve_mask; the rule is in include/s2k.h): span_keys (64-bit,
+        strictly ascending as uint64) and span_counts (32-bit) on the GPU -> dict: resolved (uint8 GPU tensor, one byte per unitig),
+        partner (int32 GPU tensor, one entry per edge: the out-edge matched to an edge that enters a resolved unitig, -1 = NO_PARTNER
+        otherwise) and the ints n_candidates, n_resolved."""
+        import torch
+
+        ug = unitig_graph
+        t, ne, dev = ug.n_unitigs, ug.dst.numel(), ug.row_off.device
+        row_off, dst, sk, sc = ug.row_off.contiguous(), ug.dst.contiguous(), span_keys.contiguous(), span_counts.contiguous()
+        n = sk.numel()
+        if row_off.numel() != 2 * t + 1 or sk.element_size() != 8 or sc.element_size() != 4 or sc.numel() != n:
+            raise ValueError("graph_resolve_mask wants a UnitigGraph and a span table: 64-bit keys, 32-bit counts of the same length")
+        resolved = torch.zeros(max(t, 1), dtype=torch.uint8, device=dev)
+        partner = torch.full((max(ne, 1),), -1, dtype=torch.int32, device=dev)
+        nc, nr = C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_graph_resolve_mask(self.ctx, C.c_void_p(row_off.data_ptr()), C.c_void_p(dst.data_ptr() if ne else 0), ne, t,
+                                                    C.c_void_p(sk.data_ptr() if n else 0), C.c_void_p(sc.data_ptr() if n else 0), n, int(min_support),
+                                                    C.c_void_p(resolved.data_ptr()), C.c_void_p(partner.data_ptr()), C.byref(nc), C.byref(nr)))
+        return {"resolved": resolved[:t], "partner": partner[:ne], "n_candidates": int(nc.value), "n_resolved": int(nr.value)}
 
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
@@ -1059,6 +1119,31 @@ class UnitigGraph:
         table.thread(outs, n_reads, place, self.n_unitigs, o, min_count, uni_items=coverage)
         return ReadPaths(path_off, **{f: t[:n] for f, t in res.items()})
 
+    def spans(self, engine, paths, edge_support=None):
+        """The span keys of one batch's ReadPaths (Engine.paths_spans) -> (keys, (n_followed, n_off_graph)); edge_support: an int64 GPU
+        tensor of n_edges zeros that gains the read support of every edge, batch after batch -- on the reads the graph was built
+        from it ends equal to edge_counts."""
+        keys, nf, no = engine.paths_spans(self, paths, edge_support)
+        return keys, (nf, no)
+
+    def span_table(self, engine, list_of_paths, min_count=1):
+        """The span table of several batches' ReadPaths: their span keys counted by a KminmerCounter (which counts any 64-bit keys) ->
+        SpanTable(keys, counts), keys strictly ascending, count(a, b) == count(tw b, tw a)."""
+        ctr = KminmerCounter(engine)
+        try:
+            for paths in list_of_paths:
+                ctr.add_tensor(self.spans(engine, paths)[0])
+            return SpanTable(*ctr.finish(min_count))
+        finally:
+            ctr.close()
+
+    def resolve(self, engine, span_table, min_support=2):
+        """Which repeat unitigs the spans resolve (Engine.graph_resolve_mask) -> (resolved, partner, stats): a uint8 GPU tensor with one
+        byte per unitig, an int32 GPU tensor with the matched out-edge of every edge that enters a resolved unitig (-1 otherwise), and
+        {"candidates", "resolved"} counted in unitigs.  Duplicating a resolved unitig is left to the caller."""
+        m = engine.graph_resolve_mask(self, span_table.keys, span_table.counts, min_support)
+        return m["resolved"], m["partner"], {"candidates": m["n_candidates"], "resolved": m["n_resolved"]}
+
     def write_gfa(self, path, members=False, sequences=None):
         """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
         members=True an nd:Z: tag that lists node index and orientation in path order) and an L line per twin pair of edges, by the rule
@@ -1115,6 +1200,37 @@ def write_read_paths(path, path_off, unitig, pos, count, flags, first_read=0):
             steps = "".join("%s%s%d:%d+%d" % ("" if s == a or f[s] & STEP_LINKED else "*", "<" if u[s] & 1 else ">", u[s] >> 1, p[s], c[s])
                             for s in range(a, b))
             out.write("%d\t%d\t%s\n" % (first_read + r, b - a, steps))
+
+
+class SpanTable:
+    """The counted span keys of a read set over a UnitigGraph (UnitigGraph.span_table): keys[i] = a << 32 | b (as uint64, strictly
+    ascending; a and b index the graph's edges: a enters the spanned unitig, b leaves it) was seen counts[i] times.  GPU tensors."""
+
+    def __init__(self, keys, counts):
+        self.keys, self.counts = keys, counts
+
+    @property
+    def n_spans(self):
+        return self.keys.numel()
+
+    def write(self, path, edge_keys):
+        write_spans(path, self.keys.cpu().numpy().view(np.uint64), self.counts.cpu().numpy().view(np.uint32),
+                    (edge_keys.cpu().numpy() if hasattr(edge_keys, "cpu") else np.asarray(edge_keys)).view(np.uint64))
+
+
+def write_spans(path, span_keys, span_counts, edge_keys):
+    """A span table on host arrays, one line per twin pair of spans (the one with a < tw(b)): the three oriented unitigs A, V, C of
+    the spanning read, each >t (oriented unitig 2 t) or <t (2 t + 1) as in write_read_paths, and the count, separated by tabs.
+    edge_keys: the unitig edge keys U << 32 | V, strictly ascending, that the span keys' halves index."""
+    ek = np.asarray(edge_keys, dtype=np.uint64)
+    sk, sc = np.asarray(span_keys, dtype=np.uint64), np.asarray(span_counts, dtype=np.uint32)
+    src, dst = (ek >> np.uint64(32)).astype(np.int64), (ek & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    a, b = (sk >> np.uint64(32)).astype(np.int64), (sk & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    twin_of_b = np.searchsorted(ek, ((dst[b] ^ 1).astype(np.uint64) << np.uint64(32)) | (src[b] ^ 1).astype(np.uint64))
+    name = lambda u: "%s%d" % ("<" if u & 1 else ">", u >> 1)  # noqa: E731
+    with open(path, "w") as f:
+        for i in np.nonzero(a < twin_of_b)[0].tolist():
+            f.write("%s\t%s\t%s\t%d\n" % (name(int(src[a[i]])), name(int(dst[a[i]])), name(int(dst[b[i]])), int(sc[i])))
 
 
 _REVCOMP = np.arange(256, dtype=np.uint8)
