@@ -583,11 +583,71 @@ s2k_status s2k_paths_spans(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out 
  * row_off rules and ids as above; span keys strictly ascending, both halves < n_edges, the out half in the row of the unitig that
  * the in half enters.  n_unitigs >= 2^31 and n_edges >= 2^32 are refused.  One lane per oriented unitig; a hub is slow (quadratic in
  * its degree), never wrong.  Workspace: 32 B of the context's grow-only count workspace.  Runs on the context's stream; returns when
- * the outputs are written.  Duplicating a resolved unitig (the graph surgery) is not part of this call. */
+ * the outputs are written.  Duplicating a resolved unitig (the graph surgery) is s2k_graph_untangle, below. */
 #define S2K_NO_PARTNER 0xFFFFFFFFu
 s2k_status s2k_graph_resolve_mask(s2k_ctx *ctx, const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs,
                                   const uint64_t *d_span_keys, const uint32_t *d_span_counts, uint64_t n_spans, uint32_t min_support,
                                   uint8_t *d_resolved, uint32_t *d_partner, uint64_t *n_candidates, uint64_t *n_resolved);
+/* ---- untangling: resolved unitigs duplicated, the contigs expanded to node members -------------------------------------
+ * Input: the CSR over the 2 T oriented unitigs (d_row_off, d_dst, n_edges) with d_resolved[T] and d_partner[n_edges] as
+ * s2k_graph_resolve_mask wrote them for that CSR; tw(e) as above.
+ * Copies: deg(t) = out(2 t) for a resolved t (it equals in(2 t)); ncopies(t) = deg(t) if t is resolved, otherwise 1; copy_off[t] = the
+ * copies of all unitigs below t (T + 1 entries); T' = copy_off[T]; origin[c] = t for copy_off[t] <= c < copy_off[t + 1]; oriented copy
+ * C = 2 c + s.
+ * Which copy an edge uses.  For a resolved t let base = row_off[2 t + 1].  Copy j is the copy whose reverse strand leaves over edge
+ * base + j, the j-th entry of the row of 2 t + 1: its forward strand is entered by a_j = tw(base + j) and leaves over partner[a_j],
+ * its reverse strand is entered by tw(partner[a_j]).  An edge e = (A -> B) picks copy index jA of its source unitig, 0 when A >> 1 is
+ * not resolved; A odd: jA = e - base(A >> 1); A even: jA = partner[tw(e)] - base(A >> 1) (from partner[tw(partner[a])] == tw(a)).  It
+ * picks copy index jB of its destination unitig, 0 when B >> 1 is not resolved; B even: jB = tw(e) - base(B >> 1); B odd: jB =
+ * partner[e] - base(B >> 1).  Every old edge becomes exactly one new edge: A' = 2 (copy_off[A >> 1] + jA) + (A & 1), B' likewise,
+ * key A' << 32 | B'.  The new graph has n_edges edges over T' copies and is twin-symmetric; each strand of a copy of a resolved unitig
+ * has in = out = 1, so the compaction (s2k_graph_unitigs over the T' copies) joins it to what it was matched with.
+ * Copy count (written only when d_uni_count, d_edge_counts and d_copy_count are all given): an unresolved unitig keeps cnt[t]; copy j
+ * of a resolved t gets floor(cnt[t] * w_j / S), w_j = edge_counts[a_j], S = the sum of the w_i -- exact, no floating point: (cnt / S)
+ * * w_j + ((cnt % S) * w_j) / S with a 128-bit product; S == 0 gives 0.  The copies' counts add up to at most deg - 1 less than cnt[t].
+ *
+ * s2k_graph_untangle: d_copy_off (T + 1), d_origin (T'), d_copy_count (T'), d_keys (n_edges, strictly ascending:
+ * s2k_graph_adjacency(d_keys, n_edges, T') takes them as they are) and d_src_edge (n_edges; the old edge key j came from: the caller
+ * gathers edge counts with it); each may be NULL.  *n_copies = T' and *n_duplicated (the resolved unitigs) are always set.  The arrays
+ * are written only when *n_copies <= capacity, otherwise S2K_ERR_CAPACITY and nothing is written; all NULL asks for the sizes only.
+ * One lane per unitig and a scan give copy_off, one lane per new oriented copy and a scan the new row offsets, one lane per new
+ * oriented copy writes its row: a copy strand of a resolved unitig its one edge, an unresolved A its old row with every destination
+ * mapped.  The map is monotone between unitigs but not inside a row (edges of A to both 2 t and 2 t + 1 of a resolved t can swap), so
+ * a row's keys are placed by repeated selection (quadratic in a hub's degree: slow, never wrong).  No sort, no atomic on an output:
+ * every output is a function of the input, bit-identical from call to call.  A graph with nothing resolved gives the identity:
+ * origin[c] = c, the keys equal to the input's.
+ * Checked on the device before anything is written, one flag word read by the host, S2K_ERR_INVALID_ARG otherwise: the row_off rules
+ * of s2k_graph_simplify_mask, every id below 2 n_unitigs; d_resolved bytes 0 or 1; a resolved t has out(2 t) == out(2 t + 1) >= 2;
+ * each in-edge of 2 t and of 2 t + 1 has its partner in the row of the strand it enters; no two in-edges share a partner;
+ * partner[tw(partner[a])] == tw(a).  Twin symmetry elsewhere and the order inside a row are trusted.  n_unitigs >= 2^31, n_edges >=
+ * 2^32 and T' >= 2^31 are refused; n_unitigs == 0 needs n_edges == 0 and reads nothing.  d_dst and d_partner may be NULL when n_edges
+ * == 0.  Outputs must not overlap inputs.  Workspace (the context's grow-only count workspace), sized by T' <= T + n_edges / 2: 40 B
+ * per unitig and 14 B per edge.  Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_graph_untangle(s2k_ctx *ctx, const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs,
+                              const uint8_t *d_resolved, const uint32_t *d_partner, const uint64_t *d_uni_count, const uint32_t *d_edge_counts,
+                              uint64_t *d_copy_off, uint32_t *d_origin, uint64_t *d_copy_count, uint64_t *d_keys, uint64_t *d_src_edge,
+                              uint64_t capacity, uint64_t *n_copies, uint64_t *n_duplicated);
+/* The contigs of the untangled graph as node members.  Input: the outer decomposition (d_outer_off, d_outer_members,
+ * d_outer_circular: the uni_off / members / circular that s2k_graph_unitigs wrote with the n_copies copies as its nodes, n_contigs
+ * unitigs), d_origin of s2k_graph_untangle, and the inner decomposition (d_uni_off, d_members, d_circular of the n_unitigs unitigs
+ * over n_nodes nodes).
+ * Every output member slot m is a node instance.  An outer member C = 2 c + s contributes the members of unitig origin[c]: in order
+ * for s == 0, reversed and each ^ 1 for s == 1; so instance ids run in path order.  d_node_origin[m] = the old node id;
+ * d_members_out[m] = 2 m + (the old oriented node's orientation bit); d_node_unitig[m] = its contig; d_node_pos[m] = its position in
+ * the contig; d_uni_off_out has n_contigs + 1 entries, the last one M, the total of instances; d_circular_out[t] = outer circular, or
+ * the contig is a single copy whose origin is circular.  The result is a valid input of s2k_unitig_sequences, s2k_unitig_node_places
+ * and the GFA writers with n_nodes = M, the node records gathered through d_node_origin.
+ * *n_members = M is always set; every output may be NULL (all NULL: the size only); the arrays are written only when M <= capacity,
+ * otherwise S2K_ERR_CAPACITY and nothing is written.  Checked on the device before anything is written (S2K_ERR_INVALID_ARG): both
+ * uni_off arrays ascend strictly from 0 to n_copies / n_nodes; every outer member is below 2 n_copies; every origin it names is
+ * below n_unitigs.  n_copies, n_nodes or M >= 2^31 are refused; n_copies == 0 reads nothing.  Piece lengths by one lane per outer
+ * member, a scan, then an output-ordered write: consecutive lanes take consecutive slots.  Workspace: 16 B per copy.  Runs on the
+ * context's stream; returns when the outputs are written. */
+s2k_status s2k_unitig_expand(s2k_ctx *ctx, const uint64_t *d_outer_off, const uint32_t *d_outer_members, const uint8_t *d_outer_circular,
+                             uint64_t n_contigs, uint64_t n_copies, const uint32_t *d_origin, const uint64_t *d_uni_off, const uint32_t *d_members,
+                             const uint8_t *d_circular, uint64_t n_unitigs, uint64_t n_nodes, uint64_t *d_uni_off_out, uint32_t *d_members_out,
+                             uint32_t *d_node_unitig, uint32_t *d_node_pos, uint8_t *d_circular_out, uint32_t *d_node_origin, uint64_t capacity,
+                             uint64_t *n_members);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

@@ -242,6 +242,36 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return t;
     }
+    // s2k_graph_untangle: every resolved unitig (d_resolved, d_partner of graph_resolve_mask) duplicated once per matched pair of edges:
+    // d_copy_off (n_unitigs + 1), d_origin and d_copy_count (one per copy; the counts only with d_uni_count and d_edge_counts), d_keys
+    // (n_edges, strictly ascending: graph_adjacency takes them over `copies` nodes) and d_src_edge; all nullptr: the sizes only.  Throws
+    // on S2K_ERR_CAPACITY too (more copies than `capacity`; nothing written).
+    struct UntangleTotals {
+        uint64_t copies, duplicated;
+    };
+    UntangleTotals graph_untangle(const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs, const uint8_t *d_resolved,
+                                  const uint32_t *d_partner, const uint64_t *d_uni_count = nullptr, const uint32_t *d_edge_counts = nullptr,
+                                  uint64_t *d_copy_off = nullptr, uint32_t *d_origin = nullptr, uint64_t *d_copy_count = nullptr,
+                                  uint64_t *d_keys = nullptr, uint64_t *d_src_edge = nullptr, uint64_t capacity = 0) {
+        UntangleTotals t{};
+        s2k_status st = s2k_graph_untangle(ctx_, d_row_off, d_dst, n_edges, n_unitigs, d_resolved, d_partner, d_uni_count, d_edge_counts, d_copy_off,
+                                           d_origin, d_copy_count, d_keys, d_src_edge, capacity, &t.copies, &t.duplicated);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
+    // s2k_unitig_expand: the contigs (`outer`: uni_off, members and circular of graph_unitigs over the n_copies copies; outer.capacity =
+    // their number) as node members, through d_origin and the inner decomposition (`inner`, inner.capacity = n_unitigs, over n_nodes
+    // nodes).  `out` receives uni_off, members, node_unitig, node_pos and circular, d_node_origin the old node of every instance;
+    // out.capacity = the instances they hold.  Returns the number of instances (throws on S2K_ERR_CAPACITY too).
+    uint64_t unitig_expand(const s2k_unitig_out &outer, uint64_t n_copies, const uint32_t *d_origin, const s2k_unitig_out &inner, uint64_t n_nodes,
+                           const s2k_unitig_out &out, uint32_t *d_node_origin = nullptr) {
+        uint64_t n_members = 0;
+        s2k_status st = s2k_unitig_expand(ctx_, outer.uni_off, outer.members, outer.circular, outer.capacity, n_copies, d_origin, inner.uni_off,
+                                          inner.members, inner.circular, inner.capacity, n_nodes, out.uni_off, out.members, out.node_unitig,
+                                          out.node_pos, out.circular, d_node_origin, out.capacity, &n_members);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_members;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "s2k_graph_simplify_mask", "s2k_graph_induced",
     "s2k_unitig_node_places", "s2k_table_thread",
     "s2k_paths_spans", "s2k_graph_resolve_mask",
+    "s2k_graph_untangle", "s2k_unitig_expand",
 ]
 
 
@@ -204,6 +205,12 @@ def load_library(path=None):
                                   C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.s2k_graph_resolve_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_graph_untangle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)]
+    L.s2k_unitig_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -666,6 +673,68 @@ class Engine:
                                                     C.c_void_p(resolved.data_ptr()), C.c_void_p(partner.data_ptr()), C.byref(nc), C.byref(nr)))
         return {"resolved": resolved[:t], "partner": partner[:ne], "n_candidates": int(nc.value), "n_resolved": int(nr.value)}
 
+    def graph_untangle(self, unitig_graph, resolved, partner):
+        """Every resolved unitig of a UnitigGraph duplicated once per matched in-edge / out-edge pair (s2k_graph_untangle; the
+        definitions are in include/s2k.h): resolved (uint8, one byte per unitig) and partner (int32, one entry per edge) as
+        graph_resolve_mask returned them.  Two calls: the sizes, then the arrays.  -> dict of GPU tensors copy_off (int64, n_unitigs + 1),
+        origin (int32, the unitig of every copy), copy_count (int64, the unitig's count shared among its copies by edge count), keys
+        (int64, the n_edges edges over the oriented copies, strictly ascending as uint64: graph_adjacency takes them) and src_edge
+        (int64, the old edge of every key), and the ints n_copies, n_duplicated."""
+        import torch
+
+        ug = unitig_graph
+        t, ne, dev = ug.n_unitigs, ug.dst.numel(), ug.row_off.device
+        row_off, dst, counts, ec = ug.row_off.contiguous(), ug.dst.contiguous(), ug.counts.contiguous(), ug.edge_counts.contiguous()
+        resolved, partner = resolved.contiguous(), partner.contiguous()
+        if (row_off.numel() != 2 * t + 1 or row_off.element_size() != 8 or dst.element_size() != 4 or resolved.numel() != t or resolved.element_size() != 1
+                or partner.numel() != ne or partner.element_size() != 4 or counts.numel() != t or counts.element_size() != 8 or ec.numel() != ne
+                or ec.element_size() != 4):
+            raise ValueError("graph_untangle wants a UnitigGraph, one resolved byte per unitig and one 32-bit partner per edge")
+        p = lambda x, n=1: C.c_void_p(x.data_ptr() if n else 0)  # noqa: E731
+        args = (self.ctx, p(row_off), p(dst, ne), ne, t, p(resolved, t), p(partner, ne), p(counts, t), p(ec, ne))
+        nc, nd = C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_graph_untangle(*args, None, None, None, None, None, 0, C.byref(nc), C.byref(nd)))
+        n = int(nc.value)
+        copy_off = torch.zeros(t + 1, dtype=torch.int64, device=dev)
+        origin = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        copy_count = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        keys, src = torch.empty(max(ne, 1), dtype=torch.int64, device=dev), torch.empty(max(ne, 1), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_graph_untangle(*args, p(copy_off), p(origin), p(copy_count), p(keys), p(src), n, C.byref(nc), C.byref(nd)))
+        return {"copy_off": copy_off, "origin": origin[:n], "copy_count": copy_count[:n], "keys": keys[:ne], "src_edge": src[:ne], "n_copies": n,
+                "n_duplicated": int(nd.value)}
+
+    def unitig_expand(self, outer, origin, uni_off, members, circular):
+        """The contigs of an untangled graph as node members (s2k_unitig_expand): outer = what graph_unitigs returned with the copies
+        as its nodes, origin = graph_untangle's, and uni_off / members / circular = the decomposition the copies came from.  Two
+        calls: the size, then the arrays.  -> dict of GPU tensors uni_off (int64, n_contigs + 1), members, node_unitig, node_pos (int32,
+        one per node instance; instance m is the oriented node 2 m + its old orientation bit), circular (uint8) and node_origin (int32,
+        the old node of every instance), and the int n_members."""
+        import torch
+
+        oo, om, oc, origin = (x.contiguous() for x in (outer["uni_off"], outer["members"], outer["circular"], origin))
+        uni_off, members, circular = uni_off.contiguous(), members.contiguous(), circular.contiguous()
+        nt, ncp, t, n, dev = oc.numel(), origin.numel(), circular.numel(), members.numel(), uni_off.device
+        if (oo.numel() != nt + 1 or om.numel() != ncp or uni_off.numel() != t + 1 or oo.element_size() != 8 or uni_off.element_size() != 8
+                or om.element_size() != 4 or origin.element_size() != 4 or members.element_size() != 4):
+            raise ValueError("unitig_expand wants the outer decomposition over the copies, one 32-bit origin per copy, and the inner decomposition")
+        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
+        args = (self.ctx, p(oo), p(om, ncp), p(oc, nt), nt, ncp, p(origin, ncp), p(uni_off), p(members, n), p(circular, t), t, n)
+        nm = C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_unitig_expand(*args, None, None, None, None, None, None, 0, C.byref(nm)))
+        m = int(nm.value)
+        res = {"uni_off": torch.zeros(nt + 1, dtype=torch.int64, device=dev), "members": torch.empty(max(m, 1), dtype=torch.int32, device=dev),
+               "node_unitig": torch.empty(max(m, 1), dtype=torch.int32, device=dev), "node_pos": torch.empty(max(m, 1), dtype=torch.int32, device=dev),
+               "circular": torch.empty(max(nt, 1), dtype=torch.uint8, device=dev), "node_origin": torch.empty(max(m, 1), dtype=torch.int32, device=dev)}
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_unitig_expand(*args, *(p(res[f]) for f in ("uni_off", "members", "node_unitig", "node_pos", "circular", "node_origin")),
+                                               m, C.byref(nm)))
+        out = {f: res[f][:m] for f in ("members", "node_unitig", "node_pos", "node_origin")}
+        out.update(uni_off=res["uni_off"], circular=res["circular"][:nt], n_members=m)
+        return out
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -906,6 +975,13 @@ class NodeSequences:
         old = torch.nonzero(node_map >= 0)[:, 0]
         return type(self)(*(getattr(self, f)[old] for f in ("rep",) + self.FIELDS), self.pool, self.n_bytes, self.k)
 
+    def take(self, node_origin):
+        """The records of the node instances of an untangled graph: node_origin is what UnitigGraph.untangle returned (per instance
+        its old node).  The counterpart of subset: the record arrays are gathered to the instance ids -- a node of a duplicated unitig
+        occurs once per copy -- and the pool is shared, not copied."""
+        old = node_origin.long()
+        return type(self)(*(getattr(self, f)[old] for f in ("rep",) + self.FIELDS), self.pool, self.n_bytes, self.k)
+
     @classmethod
     def build(cls, engine, table_or_graph, outs, k=None):
         """outs: per batch the GPU tensors extract_device wrote with FLAG_WANT_MINIMIZERS (km_off, hash, rev, mn_off, mn_j, mn_jend) plus
@@ -1140,9 +1216,40 @@ class UnitigGraph:
     def resolve(self, engine, span_table, min_support=2):
         """Which repeat unitigs the spans resolve (Engine.graph_resolve_mask) -> (resolved, partner, stats): a uint8 GPU tensor with one
         byte per unitig, an int32 GPU tensor with the matched out-edge of every edge that enters a resolved unitig (-1 otherwise), and
-        {"candidates", "resolved"} counted in unitigs.  Duplicating a resolved unitig is left to the caller."""
+        {"candidates", "resolved"} counted in unitigs.  self.untangle(engine, resolved, partner) duplicates the resolved unitigs and
+        compacts the result into contigs."""
         m = engine.graph_resolve_mask(self, span_table.keys, span_table.counts, min_support)
         return m["resolved"], m["partner"], {"candidates": m["n_candidates"], "resolved": m["n_resolved"]}
+
+    def untangle(self, engine, resolved, partner):
+        """One round of untangling on the device: every resolved unitig is duplicated once per matched pair of edges
+        (Engine.graph_untangle), the untangled graph over the copies is compacted again (graph_adjacency, graph_unitigs,
+        graph_unitig_edges, graph_adjacency) and its contigs are expanded back to node members (Engine.unitig_expand).  resolved and
+        partner are what self.resolve returned.
+        -> (contigs, node_origin, stats): contigs, a UnitigGraph whose nodes are node instances (n_nodes = their number; a node of a
+        duplicated unitig has one instance per copy), counts = the summed copy counts, edge counts gathered from self's; node_origin, an
+        int32 GPU tensor with the old node of every instance -- contigs.sequences(engine, node_seqs.take(node_origin)), write_gfa and
+        write_fasta then work as they are; stats = {"copies", "duplicated", "contigs"}.  self is untouched.
+        One round only: the contigs' own repeats would need the reads threaded through them, and a count table keyed by hash cannot
+        hold two instances of one k-min-mer."""
+        import torch
+
+        u = engine.graph_untangle(self, resolved, partner)
+        tc, dev = u["n_copies"], self.row_off.device
+        ec = self.edge_counts[u["src_edge"]] if self.n_edges else self.edge_counts[:0]
+        row_off, dst = engine.graph_adjacency(u["keys"], tc)
+        o = engine.graph_unitigs(row_off, dst, tc)
+        ek, src = engine.graph_unitig_edges(row_off, dst, tc, o)
+        ec = ec[src] if ek.numel() else ec[:0]
+        c_row_off, c_dst = engine.graph_adjacency(ek, o["n_unitigs"])
+        x = engine.unitig_expand(o, u["origin"], self.uni_off, self.members, self.circular)
+        csum = torch.zeros(tc + 1, dtype=torch.int64, device=dev)
+        if tc:  # per contig the sum of its copies' counts, in member order
+            csum[1:] = torch.cumsum(u["copy_count"][(o["members"] >> 1).long()], 0)
+        counts = csum[o["uni_off"][1:]] - csum[o["uni_off"][:-1]]
+        contigs = UnitigGraph(x["uni_off"], x["members"], x["node_unitig"], x["node_pos"], x["circular"], counts, ek, ec, c_row_off, c_dst, o["n_links"])
+        contigs.n_nodes = x["n_members"]
+        return contigs, x["node_origin"], {"copies": tc, "duplicated": u["n_duplicated"], "contigs": o["n_unitigs"]}
 
     def write_gfa(self, path, members=False, sequences=None):
         """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
