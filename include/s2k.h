@@ -495,7 +495,8 @@ s2k_status s2k_unitig_sequences(s2k_ctx *ctx, const uint64_t *d_uni_off, const u
  * index in its read before filtering (the convention of s2k_solid_out.offset); flags bit 0 S2K_STEP_LINKED = the step's first item
  * is consecutive with a solid item of the same read: the read crosses a graph adjacency into this step, not a gap; start = in->start
  * of the first item, end = in->end of the last.
- * Paths are in minimizer space: the base-space alignment of a read to a unitig's sequence is out of scope.
+ * Paths are in minimizer space: the base-level alignment of a read to a unitig's sequence (a CIGAR) is out of scope; the coordinate
+ * lift of a path to bases is s2k_paths_walks, below.
  *
  * Threading through a simplified graph needs no node map: make a table over the simplified graph's node keys (s2k_graph_induced
  * writes them strictly ascending, so s2k_table_create accepts them), take its unitigs and their places, and thread against those --
@@ -648,6 +649,71 @@ s2k_status s2k_unitig_expand(s2k_ctx *ctx, const uint64_t *d_outer_off, const ui
                              const uint8_t *d_circular, uint64_t n_unitigs, uint64_t n_nodes, uint64_t *d_uni_off_out, uint32_t *d_members_out,
                              uint32_t *d_node_unitig, uint32_t *d_node_pos, uint8_t *d_circular_out, uint32_t *d_node_origin, uint64_t capacity,
                              uint64_t *n_members);
+/* ---- read walks with base coordinates: the coordinate lift of the minimizer-space paths -------------------------------
+ * Member offsets.  For the unitigs (d_uni_off, d_members, d_circular) over nodes with records `nodes`, member_off[x] (one uint64_t per
+ * member slot x, n_nodes of them) is where the piece of slot x starts in the concatenated output of s2k_unitig_sequences; out_off[t] is
+ * as that call writes it, L[t] = out_off[t + 1] - out_off[t]; for slot p of unitig t with oriented node m, o_p = member_off[uni_off[t] +
+ * p] - out_off[t] and e_p = o_p + seq_len(m >> 1).
+ * Base interval [lo, hi) of position q of the oriented unitig U = 2 t + s, len = the members of t, on the strand of U:
+ *   s == 0: p = q, lo = o_p, hi = min(e_p, L[t]) (representatives of erroneous reads need not be consistent: the min keeps hi inside);
+ *   s == 1: p = len - 1 - q, lo = L[t] - min(e_p, L[t]), hi = L[t] - o_p (the twin strand is the reverse complement by definition).
+ * On a circular unitig no min is applied, so hi may pass L[t]: the last members reach round into the first.  There, on s == 1, L[t] -
+ * e_p would be negative where e_p > L[t]; lo and hi are both raised by w = the multiple of L[t] that brings lo into [0, L[t]) (w = e_p
+ * when L[t] == 0), w = 0 elsewhere.
+ * Walk.  A walk is a maximal run of consecutive steps of one read in which every step after the first follows an edge, "follows an
+ * edge" exactly as for s2k_paths_spans above, against the CSR over the oriented unitigs.  A step that is not linked, is linked but
+ * off-graph, or is its read's first step starts a walk; every step belongs to exactly one walk; a read's walks are in step order.
+ * Walk record, one entry per array: first_step, n_steps; items = the sum of count over its steps; qstart = start of the first step;
+ * qend = end of the last step + 1 -- in->end is the index of the last base an item covers (inclusive, s2k_kminmer.end), the record is
+ * half-open; adv(U) = L[U >> 1] - min(overlap[U], L[U >> 1]) with overlap the d_overlap of s2k_unitig_sequences; path_len = the sum
+ * of adv(U) over all steps but the last + L of the last; path_start = lo of (U, pos) of the first step; path_end = the same sum of
+ * adv + hi of (U, pos + count - 1) of the last step; flags bit 0 S2K_WALK_CIRCULAR = the walk lies on a circular unitig.  Such a walk
+ * is one step (a circular unitig has no edges) and may go round more than once: with last = pos + count - 1, path_end = w(pos) + (last /
+ * len) * L + the unraised hi of (U, last % len), i.e. path_start + the stitched length of its items; it may exceed path_len = L.
+ * Elsewhere path_start <= path_end <= path_len.  The stitched path of a walk is the unitig sequences on the walk's strands, each after
+ * the first without the overlap[U] bases of the one before it; on error-free reads read[qstart, qend) equals its bases [path_start,
+ * path_end).  This is exact arithmetic on records, not an alignment: there is no CIGAR. */
+s2k_status s2k_unitig_member_offsets(s2k_ctx *ctx, const uint64_t *d_uni_off, const uint32_t *d_members, const uint8_t *d_circular,
+                                     uint64_t n_unitigs, uint64_t n_nodes, const s2k_node_seqs *nodes, uint64_t *d_member_off,
+                                     uint64_t *d_out_off, uint32_t *d_overlap, uint64_t *n_bases);
+/* The passes of s2k_unitig_sequences up to its copy kernel: d_member_off (n_nodes entries), d_out_off (n_unitigs + 1) and d_overlap (2
+ * n_unitigs) as defined above, each may be NULL; *n_bases is always set; nodes->pool is not read.  The same inputs are checked in the
+ * same way (S2K_ERR_INVALID_ARG, nothing written).  Workspace: 12 B per member. */
+#define S2K_WALK_CIRCULAR 1u
+#define S2K_NO_EDGE 0xFFFFFFFFu
+typedef struct s2k_walk_out { /* device pointers, each may be NULL; capacity in walks */
+    uint64_t capacity;
+    uint64_t *walk_off;   /* n_reads + 1: the walks of read r are [walk_off[r], walk_off[r + 1]) */
+    uint64_t *first_step;
+    uint32_t *n_steps;
+    uint64_t *items;
+    uint32_t *qstart;
+    uint32_t *qend;
+    uint64_t *path_len;
+    uint64_t *path_start;
+    uint64_t *path_end;
+    uint32_t *flags;
+    uint32_t *edge;       /* n_steps entries, one per STEP: the index of the edge the step follows, S2K_NO_EDGE when none */
+} s2k_walk_out;
+/* The walks of the paths s2k_table_thread wrote (path_off, unitig, pos, count, flags; start / end when out->qstart / out->qend are
+ * wanted) over the CSR of the oriented unitigs, lifted with d_member_off, d_out_off, d_overlap (s2k_unitig_member_offsets), d_seq_len
+ * (the seq_len of the node records) and d_members.  d_circular is needed beside the arrays of the issue's draft: a step on a circular
+ * unitig may pass its last member.  *n_walks, *n_followed and *n_off_graph (as s2k_paths_spans) are always set.  out NULL, or none of
+ * the record arrays given, asks for the sizes; walk_off and edge are written whenever the call returns S2K_OK; *n_walks >
+ * out->capacity with a record array given is S2K_ERR_CAPACITY and nothing at all is written.  Checked on the device before anything is
+ * written, one flag word read by the host, S2K_ERR_INVALID_ARG otherwise: the rules of s2k_paths_spans; every step has count >= 1,
+ * pos < len and, unless its unitig is circular, pos + count <= len; uni_off ascends strictly from 0 to n_nodes; every member < 2
+ * n_nodes; out_off does not decrease; every member_off lies inside [out_off[t], out_off[t + 1]] of its unitig; L[t] < 2^32 (advances
+ * are scanned as 32-bit inputs; a path's 64-bit sums are never narrowed).  n_unitigs >= 2^31, n_edges >= 2^32 and n_nodes >= 2^31 are
+ * refused.  d_seq_len and the contents of d_overlap are trusted.  qend wraps for an end of 2^32 - 1, which no read of s2k_extract has.
+ * Heads and tails of walks come from ballots and scans, sums from prefix differences; there is no atomic on an output: every output
+ * is a function of the input, bit-identical from call to call.  Uses the context's grow-only count workspace: about 24.4 B per step.
+ * Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_paths_walks(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *paths, uint64_t n_steps, const uint64_t *d_row_off,
+                           const uint32_t *d_dst, uint64_t n_edges, const uint64_t *d_uni_off, const uint8_t *d_circular, uint64_t n_unitigs,
+                           const uint64_t *d_member_off, const uint64_t *d_out_off, const uint32_t *d_overlap, const uint32_t *d_seq_len,
+                           const uint32_t *d_members, uint64_t n_nodes, const s2k_walk_out *out, uint64_t *n_walks, uint64_t *n_followed,
+                           uint64_t *n_off_graph);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

@@ -272,6 +272,31 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return n_members;
     }
+    // s2k_unitig_member_offsets: where every member's piece starts in the stitched unitigs (d_member_off, n_nodes entries), with d_out_off
+    // and d_overlap as unitig_sequences writes them; each may be nullptr.  Returns the bases of all unitigs.
+    uint64_t unitig_member_offsets(const uint64_t *d_uni_off, const uint32_t *d_members, const uint8_t *d_circular, uint64_t n_unitigs, uint64_t n_nodes,
+                                   const s2k_node_seqs &nodes, uint64_t *d_member_off, uint64_t *d_out_off = nullptr, uint32_t *d_overlap = nullptr) {
+        uint64_t n_bases = 0;
+        s2k_status st = s2k_unitig_member_offsets(ctx_, d_uni_off, d_members, d_circular, n_unitigs, n_nodes, &nodes, d_member_off, d_out_off, d_overlap,
+                                                  &n_bases);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_bases;
+    }
+    // s2k_paths_walks: the walks of one batch's paths along the edges of the CSR, with base coordinates (`lift`: uni_off, members and
+    // circular of the decomposition, lift.capacity = n_unitigs).  out nullptr: the sizes only.  Throws on S2K_ERR_CAPACITY too (nothing
+    // written).
+    struct WalkTotals {
+        uint64_t walks, followed, off_graph;
+    };
+    WalkTotals paths_walks(uint64_t n_reads, const s2k_thread_out &paths, uint64_t n_steps, const uint64_t *d_row_off, const uint32_t *d_dst,
+                           uint64_t n_edges, const s2k_unitig_out &lift, uint64_t n_nodes, const uint64_t *d_member_off, const uint64_t *d_out_off,
+                           const uint32_t *d_overlap, const uint32_t *d_seq_len, const s2k_walk_out *out = nullptr) {
+        WalkTotals t{};
+        s2k_status st = s2k_paths_walks(ctx_, n_reads, &paths, n_steps, d_row_off, d_dst, n_edges, lift.uni_off, lift.circular, lift.capacity,
+                                        d_member_off, d_out_off, d_overlap, d_seq_len, lift.members, n_nodes, out, &t.walks, &t.followed, &t.off_graph);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "s2k_unitig_node_places", "s2k_table_thread",
     "s2k_paths_spans", "s2k_graph_resolve_mask",
     "s2k_graph_untangle", "s2k_unitig_expand",
+    "s2k_unitig_member_offsets", "s2k_paths_walks",
 ]
 
 
@@ -52,6 +53,8 @@ FLAG_NO_PACK2 = 4  # s2k_extract: bases as ASCII over PCIe instead of 2-bit pack
 HPC_RLE_ALPHABET = 1  # s2k_hpc_device_ex: the run rule of encode_rle (src/hpc.rs:14)
 COUNT_SORTED = 1  # s2k_count_device_ex: pairs in ascending order of key
 STEP_LINKED = 1  # s2k_thread_out.flags: the step's first item follows a solid item of the same read
+WALK_CIRCULAR = 1  # s2k_walk_out.flags: the walk lies on a circular unitig
+NO_EDGE = 0xFFFFFFFF  # s2k_walk_out.edge: the step follows no edge
 NO_PARTNER = 0xFFFFFFFF  # s2k_graph_resolve_mask: d_partner of an edge that enters no resolved unitig
 
 
@@ -106,6 +109,12 @@ class NodeSeqs(C.Structure):
 class ThreadOut(C.Structure):
     _fields_ = [("capacity", C.c_uint64), ("path_off", C.c_void_p), ("unitig", C.c_void_p), ("pos", C.c_void_p), ("count", C.c_void_p),
                 ("item", C.c_void_p), ("flags", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p)]
+
+
+class WalkOut(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("walk_off", C.c_void_p), ("first_step", C.c_void_p), ("n_steps", C.c_void_p), ("items", C.c_void_p),
+                ("qstart", C.c_void_p), ("qend", C.c_void_p), ("path_len", C.c_void_p), ("path_start", C.c_void_p), ("path_end", C.c_void_p),
+                ("flags", C.c_void_p), ("edge", C.c_void_p)]
 
 
 # s2k_node_place: where the forward oriented node 2 i lies on the oriented unitigs
@@ -211,6 +220,11 @@ def load_library(path=None):
     L.s2k_unitig_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_uint64, C.POINTER(C.c_uint64)]
+    L.s2k_unitig_member_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(NodeSeqs), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.s2k_paths_walks.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ThreadOut), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(WalkOut),
+                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -735,6 +749,69 @@ class Engine:
         out.update(uni_off=res["uni_off"], circular=res["circular"][:nt], n_members=m)
         return out
 
+    def unitig_member_offsets(self, uni_off, members, circular, n_nodes, node_seqs):
+        """Where every member's piece starts in the stitched unitigs (s2k_unitig_member_offsets: the stitch without its copy) ->
+        (member_off, out_off, overlap, n_bases): int64 tensors of n_nodes and n_unitigs + 1 entries, the int32 overlap that leaves
+        each oriented unitig, and the bases of all unitigs; out_off and overlap equal those of unitig_sequences."""
+        import torch
+
+        uni_off, members, circular = uni_off.contiguous(), members.contiguous(), circular.contiguous()
+        t, n, dev = circular.numel(), int(n_nodes), uni_off.device
+        member_off = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        out_off = torch.zeros(t + 1, dtype=torch.int64, device=dev)
+        overlap = torch.zeros(max(2 * t, 1), dtype=torch.int32, device=dev)
+        ns, nb = node_seqs.struct(), C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_unitig_member_offsets(self.ctx, C.c_void_p(uni_off.data_ptr()), C.c_void_p(members.data_ptr() if n else 0),
+                                                       C.c_void_p(circular.data_ptr() if t else 0), t, n, C.byref(ns), C.c_void_p(member_off.data_ptr()),
+                                                       C.c_void_p(out_off.data_ptr()), C.c_void_p(overlap.data_ptr()), C.byref(nb)))
+        return member_off[:n], out_off, overlap[:2 * t], int(nb.value)
+
+    def paths_walks(self, unitig_graph, paths, offsets, seq_len, edge=True):
+        """The walks of one batch's ReadPaths over a UnitigGraph, with base coordinates (s2k_paths_walks; the definitions are in
+        include/s2k.h).  offsets: the (member_off, out_off, overlap, ...) that unitig_member_offsets returned for the graph; seq_len:
+        the seq_len of its NodeSequences.  Two calls: the sizes, then the arrays.  -> dict of GPU tensors walk_off (int64, n_reads + 1),
+        first_step, items, path_len, path_start, path_end (int64), n_steps, flags (int32), qstart, qend (int32, only when the paths
+        carry start and end), edge (int32 per step, -1 = NO_EDGE; only with edge=True), and the ints n_walks, n_followed, n_off_graph."""
+        import torch
+
+        ug, dev = unitig_graph, paths.path_off.device
+        t, ne, ns, nr, n = ug.n_unitigs, ug.dst.numel(), paths.n_steps, paths.path_off.numel() - 1, ug.members.numel()
+        row_off, dst, uni_off, members, circular = (x.contiguous() for x in (ug.row_off, ug.dst, ug.uni_off, ug.members, ug.circular))
+        member_off, out_off, overlap, seq_len = (x.contiguous() for x in (offsets[0], offsets[1], offsets[2], seq_len))
+        if (row_off.numel() != 2 * t + 1 or row_off.element_size() != 8 or dst.element_size() != 4 or uni_off.numel() != t + 1 or member_off.numel() != n
+                or member_off.element_size() != 8 or out_off.numel() != t + 1 or overlap.numel() != 2 * t or overlap.element_size() != 4
+                or seq_len.numel() != n or seq_len.element_size() != 4):
+            raise ValueError("paths_walks wants a UnitigGraph, the offsets Engine.unitig_member_offsets returned for it and one 32-bit seq_len per node")
+        o = ThreadOut()
+        o.capacity = ns
+        keep = {f: getattr(paths, f).contiguous() for f in ("path_off", "unitig", "pos", "count", "flags", "start", "end") if getattr(paths, f) is not None}
+        for f, x in keep.items():
+            setattr(o, f, x.data_ptr() if x.numel() else 0)
+        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
+        args = (self.ctx, nr, C.byref(o), ns, p(row_off), p(dst, ne), ne, p(uni_off), p(circular, t), t, p(member_off, n), p(out_off), p(overlap, t),
+                p(seq_len, n), p(members, n), n)
+        nw, nf, no = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_paths_walks(*args, None, C.byref(nw), C.byref(nf), C.byref(no)))
+        m = int(nw.value)
+        res = {"walk_off": torch.zeros(nr + 1, dtype=torch.int64, device=dev)}
+        for f in ("first_step", "items", "path_len", "path_start", "path_end"):
+            res[f] = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+        for f in ("n_steps", "flags") + (("qstart", "qend") if "start" in keep and "end" in keep else ()):
+            res[f] = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        if edge:
+            res["edge"] = torch.empty(max(ns, 1), dtype=torch.int32, device=dev)
+        w = WalkOut()
+        w.capacity = m
+        for f, x in res.items():
+            setattr(w, f, x.data_ptr())
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_paths_walks(*args, C.byref(w), C.byref(nw), C.byref(nf), C.byref(no)))
+        out = {f: (x if f == "walk_off" else x[:ns] if f == "edge" else x[:m]) for f, x in res.items()}
+        out.update(n_walks=m, n_followed=int(nf.value), n_off_graph=int(no.value))
+        return out
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -1251,6 +1328,21 @@ class UnitigGraph:
         contigs.n_nodes = x["n_members"]
         return contigs, x["node_origin"], {"copies": tc, "duplicated": u["n_duplicated"], "contigs": o["n_unitigs"]}
 
+    def member_offsets(self, engine, node_seqs):
+        """Where every member's piece starts in the unitigs' bases (Engine.unitig_member_offsets) -> (member_off, out_off, overlap,
+        n_bases), computed once per NodeSequences and kept"""
+        if getattr(self, "_member_offsets", None) is None or self._member_offsets[0] is not node_seqs:
+            n = getattr(self, "n_nodes", self.members.numel())
+            self._member_offsets = (node_seqs, engine.unitig_member_offsets(self.uni_off, self.members, self.circular, n, node_seqs))
+        return self._member_offsets[1]
+
+    def walks(self, engine, paths, node_seqs):
+        """One batch's ReadPaths joined into walks along this graph's edges, with base coordinates on the stitched path
+        (Engine.paths_walks) -> ReadWalks.  node_seqs: the NodeSequences of this graph's nodes -- of a simplified graph its subset, of
+        the contigs that untangle returned node_seqs.take(node_origin).  ReadWalks.write_gaf writes them as GAF."""
+        w = engine.paths_walks(self, paths, self.member_offsets(engine, node_seqs), node_seqs.seq_len)
+        return ReadWalks(paths, **w)
+
     def write_gfa(self, path, members=False, sequences=None):
         """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
         members=True an nd:Z: tag that lists node index and orientation in path order) and an L line per twin pair of edges, by the rule
@@ -1307,6 +1399,61 @@ def write_read_paths(path, path_off, unitig, pos, count, flags, first_read=0):
             steps = "".join("%s%s%d:%d+%d" % ("" if s == a or f[s] & STEP_LINKED else "*", "<" if u[s] & 1 else ">", u[s] >> 1, p[s], c[s])
                             for s in range(a, b))
             out.write("%d\t%d\t%s\n" % (first_read + r, b - a, steps))
+
+
+class ReadWalks:
+    """The walks of one batch of reads (UnitigGraph.walks; include/s2k.h: s2k_paths_walks): the walks of read r are walk_off[r] ..
+    walk_off[r + 1]; walk w holds the steps first_step[w] .. first_step[w] + n_steps[w] of `paths`, each after the first entered over
+    a graph edge; it covers items[w] k-min-mers, the read's bases qstart[w] .. qend[w] (None when the paths carry no start / end) and
+    the bases path_start[w] .. path_end[w] of its stitched path of path_len[w] bases; flags[w] & WALK_CIRCULAR tells a walk on a
+    circular unitig.  edge[s] = the edge step s follows, -1 for none.  GPU tensors: int64, and int32 holding the uint32 values."""
+
+    FIELDS = ("first_step", "n_steps", "items", "qstart", "qend", "path_len", "path_start", "path_end", "flags")
+
+    def __init__(self, paths, walk_off, first_step, n_steps, items, path_len, path_start, path_end, flags, qstart=None, qend=None, edge=None, n_walks=0,
+                 n_followed=0, n_off_graph=0):
+        self.paths, self.walk_off, self.first_step, self.n_steps, self.items = paths, walk_off, first_step, n_steps, items
+        self.path_len, self.path_start, self.path_end, self.flags, self.qstart, self.qend, self.edge = path_len, path_start, path_end, flags, qstart, qend, edge
+        self.n_walks, self.n_followed, self.n_off_graph = n_walks, n_followed, n_off_graph
+
+    def host(self):
+        """-> dict of numpy arrays: walk_off and the 64-bit records uint64, the 32-bit ones uint32 (qstart / qend / edge when present)"""
+        d = {"walk_off": self.walk_off.cpu().numpy().view(np.uint64)}
+        for f in self.FIELDS + ("edge",):
+            x = getattr(self, f)
+            if x is not None:
+                d[f] = x.cpu().numpy().view(np.uint64 if x.element_size() == 8 else np.uint32)
+        return d
+
+    def write_gaf(self, path, graph=None, names=None, read_lengths=None, first_read=0):
+        """One GAF line per walk (write_gaf_walks).  graph: the UnitigGraph the walks were taken on (only its naming is used: unitig t
+        is segment t, as in write_unitig_gfa; may be None); names: one name per read (the index first_read + r when None);
+        read_lengths: one length per read (* when None)."""
+        if self.qstart is None or self.qend is None:
+            raise ValueError("write_gaf wants paths that carry start and end (extract with start / end kept)")
+        h = self.host()
+        write_gaf_walks(path, h, self.paths.unitig.cpu().numpy().view(np.uint32), names=names, read_lengths=read_lengths, first_read=first_read)
+
+
+def write_gaf_walks(path, walks, step_unitig, names=None, read_lengths=None, first_read=0):
+    """ReadWalks.write_gaf on host arrays: walks = the dict ReadWalks.host() returns, step_unitig = the paths' oriented unitig per
+    step.  One line per walk, tab-separated: read name, read length (*: unknown), qstart, qend, +, the path as >t (oriented unitig 2
+    t) or <t (2 t + 1) per step with the unitig names of write_unitig_gfa, path_len, path_start, path_end, items (the matches column:
+    k-min-mers, not bases), max(qend - qstart, path_end - path_start) (the block length), 255, km:i:<items>, ns:i:<n_steps>.  On a
+    circular unitig path_end may pass path_len (include/s2k.h)."""
+    off = np.asarray(walks["walk_off"]).astype(np.int64).tolist()
+    w = {f: np.asarray(walks[f]).astype(np.int64).tolist() for f in ReadWalks.FIELDS}
+    u = np.asarray(step_unitig).astype(np.int64).tolist()
+    with open(path, "w") as out:
+        for r in range(len(off) - 1):
+            name = str(first_read + r) if names is None else names[r]
+            ln = "*" if read_lengths is None else "%d" % int(read_lengths[r])
+            for i in range(off[r], off[r + 1]):
+                a = w["first_step"][i]
+                steps = "".join("%s%d" % ("<" if x & 1 else ">", x >> 1) for x in u[a: a + w["n_steps"][i]])
+                qs, qe, ps, pe = w["qstart"][i], w["qend"][i], w["path_start"][i], w["path_end"][i]
+                out.write("%s\t%s\t%d\t%d\t+\t%s\t%d\t%d\t%d\t%d\t%d\t255\tkm:i:%d\tns:i:%d\n" % (
+                    name, ln, qs, qe, steps, w["path_len"][i], ps, pe, w["items"][i], max(qe - qs, pe - ps), w["items"][i], w["n_steps"][i]))
 
 
 class SpanTable:

@@ -38,13 +38,13 @@
 #include "s2k_call.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
+#include "s2k_stitch_dev.h"
 #include "s2k_table_dev.h"
 
 namespace s2k {
 namespace {
 
 constexpr uint32_t SQ_NONE = 0xFFFFFFFFu;
-constexpr int SQ_T = 256;
 constexpr uint64_t B01 = 0x0101010101010101ull;
 
 // ---- 16 bytes in two registers pairs --------------------------------------------------------------------------------------------
@@ -243,63 +243,6 @@ __global__ __launch_bounds__(SQ_T) void nodeseq_write_kernel(SeqIn in, const uin
 }
 
 // ---- the stitch ------------------------------------------------------------------------------------------------------------------
-struct NodeView {
-    const uint64_t *seq_off;
-    const uint32_t *seq_len, *shift_fwd, *shift_rev;
-    const uint8_t *rev, *pool;
-    uint64_t pool_capacity, n_nodes;
-};
-
-__global__ __launch_bounds__(SQ_T) void piece_len_kernel(const uint32_t *__restrict__ members, uint64_t n_members, NodeView nv, uint32_t *__restrict__ len,
-                                                         uint32_t *__restrict__ bad) {
-    const uint64_t p = (uint64_t)blockIdx.x * SQ_T + threadIdx.x;
-    if (p >= n_members) return;
-    const uint32_t u = members[p], i = u >> 1;
-    uint32_t l = 0;
-    bool ok = i < nv.n_nodes;
-    if (ok) {
-        const uint32_t sl = nv.seq_len[i], rv = nv.rev[i];
-        l = (u & 1u) == rv ? nv.shift_fwd[i] : nv.shift_rev[i];
-        const uint64_t so = nv.seq_off[i];
-        ok = rv <= 1 && nv.shift_fwd[i] <= sl && nv.shift_rev[i] <= sl && (sl == 0 || (so <= nv.pool_capacity && sl <= nv.pool_capacity - so));
-    }
-    if (!ok) {
-        atomicOr(bad, 1u);
-        l = 0;
-    }
-    len[p] = l;
-}
-
-__global__ __launch_bounds__(SQ_T) void unitig_last_kernel(const uint64_t *__restrict__ uni_off, const uint32_t *__restrict__ members,
-                                                           const uint8_t *__restrict__ circular, uint64_t n_unitigs, uint64_t n_members, NodeView nv,
-                                                           uint32_t *__restrict__ len, uint32_t *__restrict__ bad) {
-    const uint64_t t = (uint64_t)blockIdx.x * SQ_T + threadIdx.x;
-    if (t >= n_unitigs) return;
-    const uint64_t a = uni_off[t], b = uni_off[t + 1];
-    if ((t == 0 && a != 0) || a >= b || b > n_members || (t == n_unitigs - 1 && b != n_members)) { // every unitig holds a member
-        atomicOr(bad, 2u);
-        return;
-    }
-    if (circular[t]) return;
-    const uint32_t i = members[b - 1] >> 1;
-    if (i < nv.n_nodes) len[b - 1] = nv.seq_len[i]; // (else piece_len_kernel has set the flag)
-}
-
-__global__ __launch_bounds__(SQ_T) void unitig_off_kernel(const uint64_t *__restrict__ uni_off, const uint32_t *__restrict__ members, uint64_t n_unitigs,
-                                                          NodeView nv, const uint64_t *__restrict__ piece_off, uint64_t *__restrict__ out_off,
-                                                          uint32_t *__restrict__ overlap) {
-    const uint64_t t = (uint64_t)blockIdx.x * SQ_T + threadIdx.x;
-    if (t > n_unitigs) return;
-    const uint64_t a = uni_off[t];
-    if (out_off) out_off[t] = piece_off[a];
-    if (!overlap || t == n_unitigs) return;
-#pragma unroll
-    for (uint32_t s = 0; s < 2; s++) { // the last member of the oriented unitig 2 t + s
-        const uint32_t u = s ? members[a] ^ 1u : members[uni_off[t + 1] - 1], i = u >> 1;
-        overlap[2 * t + s] = nv.seq_len[i] - ((u & 1u) == nv.rev[i] ? nv.shift_fwd[i] : nv.shift_rev[i]);
-    }
-}
-
 // the largest p in [lo, hi] with piece_off[p] <= pos (piece_off[lo] <= pos holds): the piece that holds byte pos when pos < total
 __device__ inline uint64_t piece_of(const uint64_t *__restrict__ piece_off, uint64_t lo, uint64_t hi, uint64_t pos) {
     while (lo < hi) {
@@ -473,15 +416,9 @@ s2k_status s2k_unitig_sequences(s2k_ctx *ctx, const uint64_t *d_uni_off, const u
     uint32_t *bad = flag(w), *len = len_p(w);
     uint64_t *piece_off = off_p(w);
     const NodeView nv{nodes->seq_off, nodes->seq_len, nodes->shift_fwd, nodes->shift_rev, nodes->rev, nodes->pool, nodes->pool_capacity, n_nodes};
-    const unsigned gm = (unsigned)((n_members + SQ_T - 1) / SQ_T), gu = (unsigned)((n_unitigs + 1 + SQ_T - 1) / SQ_T);
+    const unsigned gu = (unsigned)((n_unitigs + 1 + SQ_T - 1) / SQ_T);
     uint64_t total = 0;
-    const uint32_t hbad = c.check(bad, 16, bad, [&] {
-        hipLaunchKernelGGL(piece_len_kernel, dim3(gm), dim3(SQ_T), 0, c.st, d_members, n_members, nv, len, bad);
-        hipLaunchKernelGGL(unitig_last_kernel, dim3(gu), dim3(SQ_T), 0, c.st, d_uni_off, d_members, d_circular, n_unitigs, n_members, nv, len, bad);
-        c.launched();
-        c.scan(len, n_members, piece_off, tmp_p(w));
-        c.fetch(&total, piece_off + n_members, 8);
-    });
+    const uint32_t hbad = stitch_offsets(c, d_uni_off, d_members, d_circular, n_unitigs, n_members, nv, bad, len, piece_off, tmp_p(w), &total);
     if (!c.ok()) return c.device_error();
     if (hbad)
         return c.invalid("uni_off is not the offsets of n_unitigs non-empty unitigs over n_nodes members, a member names a node >= n_nodes, or a "

@@ -7,7 +7,7 @@
 //  1. spans_check_kernel: path_off starts at 0, does not decrease and ends at n_steps; every step's unitig < 2 T; the CSR rules of
 //     simplify_check_kernel; uni_off strictly ascending.  One flag word, read by the host before anything is written; every read is
 //     clamped to the arrays whatever they hold.
-//  2. spans_count_kernel: per step its unitig, "ends at its unitig's last member" and "starts a read" to LDS, with one halo step on
+//  2. spans_count_kernel (follow_tile of s2k_span_dev.h, shared with the walks of s2k_walk.hip): per step its unitig, "ends at its unitig's last member" and "starts a read" to LDS, with one halo step on
 //     either side; the read starts in [t0, t0 + TB_TILE] are marked from the reads a binary search of path_off finds there.  The edge a
 //     step follows: a binary search of the row of the step before it, the row bounds of all TB_Q steps loaded before the first probe,
 //     the TB_Q searches side by side; the index (SP_NONE: none) goes to workspace and to LDS.  Step s spans iff it and step s + 1
@@ -37,49 +37,13 @@
 #include "s2k_dev.h"
 #include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
+#include "s2k_span_dev.h"
 #include "s2k_table_dev.h"
 
 namespace s2k {
 namespace {
 
-constexpr uint32_t SP_NONE = 0xFFFFFFFFu; // no edge (n_edges < 2^32: an index stays below it)
-
-struct Csr {
-    const uint64_t *row_off;
-    const uint32_t *dst;
-};
-
-// the index of B in the row of A (strictly ascending), SP_NONE if it is not there
-__device__ __forceinline__ uint32_t find_edge(const Csr &g, uint32_t A, uint32_t B) {
-    uint64_t lo = g.row_off[A], hi = g.row_off[A + 1];
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        const uint32_t v = g.dst[mid];
-        if (v < B) lo = mid + 1;
-        else if (v > B) hi = mid;
-        else return (uint32_t)mid;
-    }
-    return SP_NONE;
-}
-
-// the CSR rules of s2k_graph_simplify_mask for row u
-__device__ __forceinline__ bool csr_ids_ok(const uint64_t *__restrict__ row_off, const uint32_t *__restrict__ dst, uint64_t u, uint64_t n_ids,
-                                           uint64_t n_edges) {
-    uint64_t a, b;
-    if (!csr_row_ok(row_off, u, n_ids, n_edges, &a, &b)) return false;
-    bool ok = true;
-    for (uint64_t e = a; e < b; e++)
-        if (dst[e] >= n_ids) ok = false;
-    return ok;
-}
-
 // ---- spans -----------------------------------------------------------------------------------------------------------------------
-struct Paths {
-    const uint64_t *path_off;
-    const uint32_t *unitig, *pos, *count, *flags;
-    uint64_t n_reads, n_steps;
-};
-
 struct SpanWs {
     uint32_t *edge; // per step: the index of the edge it follows, SP_NONE when none
     CompactWs c;    // the span mask
@@ -103,108 +67,30 @@ __global__ __launch_bounds__(UT) void spans_check_kernel(Paths p, Csr g, const u
     if (!ok) atomicOr(bad, 1u);
 }
 
-constexpr uint8_t SF_ATEND = 1, SF_SELF = 2; // the step ends at its unitig's last member; it is linked and begins at position 0
-
 __global__ __launch_bounds__(TB_THREADS) void spans_count_kernel(Paths p, Csr g, const uint64_t *__restrict__ uni_off, SpanWs ws,
                                                                  unsigned long long *__restrict__ totals /* followed, off-graph */) {
-    // index x + 1 <-> step t0 + x: index 0 is the step before the tile, index TB_TILE + 1 the one after it
-    __shared__ uint32_t sU[TB_TILE + 2], sE[TB_TILE + 2];
-    __shared__ uint8_t sf[TB_TILE + 2], sstart[TB_TILE + 2];
+    __shared__ FollowLds s;
     __shared__ uint32_t wc[TB_WORDS];
-    __shared__ uint64_t sreads[2];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
-    uint32_t U[TB_Q], cnt[TB_Q], fl[TB_Q], ps[TB_Q];
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) {
-        const uint64_t j = std::min<uint64_t>(t0 + (uint64_t)r * TB_THREADS + tid, p.n_steps - 1);
-        U[r] = p.unitig[j], ps[r] = p.pos[j], cnt[r] = p.count[j], fl[r] = p.flags[j];
-    }
-    if (tid < 2) sreads[tid] = tid ? reads_upto(p.path_off, p.n_reads, t0 + TB_TILE) : t0 ? reads_upto(p.path_off, p.n_reads, t0 - 1) : 0;
+    uint32_t U[TB_Q], ps[TB_Q], cnt[TB_Q], fl[TB_Q], e[TB_Q];
     uint64_t len[TB_Q];
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) len[r] = uni_off[(U[r] >> 1) + 1] - uni_off[U[r] >> 1];
-    bool whole[TB_Q];
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) {
-        const int x = r * TB_THREADS + tid;
-        const bool valid = t0 + x < p.n_steps;
-        whole[r] = valid && cnt[r] == len[r];
-        sU[x + 1] = valid ? U[r] : SP_NONE;
-        sf[x + 1] = valid ? (uint8_t)(((uint64_t)ps[r] + cnt[r] == len[r] ? SF_ATEND : 0) | ((fl[r] & S2K_STEP_LINKED) && ps[r] == 0 ? SF_SELF : 0)) : 0;
-        sstart[x + 1] = 0;
-    }
-    if (tid == 0 || tid == 64) { // the two halo steps, one lane of two different waves
-        const uint64_t j = tid == 0 ? t0 + TB_TILE : t0 - 1; // t0 - 1 wraps to 2^64 - 1 for the first tile: no such step
-        uint32_t hU = SP_NONE;
-        uint8_t hf = 0;
-        if (j < p.n_steps) {
-            hU = p.unitig[j];
-            const uint64_t hl = uni_off[(hU >> 1) + 1] - uni_off[hU >> 1];
-            const uint32_t hp = p.pos[j];
-            hf = (uint8_t)(((uint64_t)hp + p.count[j] == hl ? SF_ATEND : 0) | ((p.flags[j] & S2K_STEP_LINKED) && hp == 0 ? SF_SELF : 0));
-        }
-        const int i = tid == 0 ? TB_TILE + 1 : 0;
-        sU[i] = hU;
-        sf[i] = hf;
-        sstart[i] = 0;
-        sE[i] = SP_NONE;
-    }
-    __syncthreads();
-    for (uint64_t r = sreads[0] + tid; r < sreads[1]; r += TB_THREADS) {
-        const uint64_t x = p.path_off[r] - t0; // in [0, TB_TILE] for a non-decreasing path_off
-        if (x <= TB_TILE) sstart[x + 1] = 1;
-    }
-    __syncthreads();
-    // index i may follow an edge out of index i - 1 (i >= 1): everything but the search
-    auto may_follow = [&](int i) { return (sf[i] & SF_SELF) && !sstart[i] && sU[i - 1] != SP_NONE && (sf[i - 1] & SF_ATEND); };
-    uint64_t lo[TB_Q], hi[TB_Q];
-    uint32_t e[TB_Q];
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) { // every row bound in flight before the first probe
-        const int i = r * TB_THREADS + tid + 1;
-        const bool m = t0 + (i - 1) < p.n_steps && may_follow(i);
-        const uint32_t A = m ? sU[i - 1] : 0u;
-        lo[r] = g.row_off[A];
-        hi[r] = m ? g.row_off[A + 1] : lo[r];
-        e[r] = SP_NONE;
-    }
-    for (;;) { // TB_Q searches side by side
-        bool more = false;
-#pragma unroll
-        for (int r = 0; r < TB_Q; r++) {
-            if (lo[r] < hi[r]) {
-                const uint64_t mid = (lo[r] + hi[r]) >> 1;
-                const uint32_t v = g.dst[mid], B = U[r];
-                if (v < B) lo[r] = mid + 1;
-                else if (v > B) hi[r] = mid;
-                else {
-                    e[r] = (uint32_t)mid;
-                    lo[r] = hi[r];
-                }
-                more |= lo[r] < hi[r];
-            }
-        }
-        if (!more) break;
-    }
+    follow_tile(p, g, uni_off, t0, s, U, ps, cnt, fl, len, e);
     uint32_t n[2] = {0, 0}; // followed, off-graph
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) {
-        const int x = r * TB_THREADS + tid;
-        const uint64_t j = t0 + x;
-        sE[x + 1] = e[r];
+        const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
         if (j < p.n_steps) {
             ws.edge[j] = e[r];
             n[0] += e[r] != SP_NONE;
             n[1] += (fl[r] & S2K_STEP_LINKED) && e[r] == SP_NONE;
         }
     }
-    if (tid == 0 && may_follow(TB_TILE + 1)) sE[TB_TILE + 1] = find_edge(g, sU[TB_TILE], sU[TB_TILE + 1]); // the step after the tile
-    __syncthreads();
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) {
         const int i = r * TB_THREADS + tid + 1;
-        const uint64_t m = __ballot(whole[r] && sE[i] != SP_NONE && sE[i + 1] != SP_NONE);
+        const bool whole = t0 + (i - 1) < p.n_steps && cnt[r] == len[r];
+        const uint64_t m = __ballot(whole && s.E[i] != SP_NONE && s.E[i + 1] != SP_NONE);
         const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
         if (lane == 0) {
             wc[r * 4 + wv] = (uint32_t)__popcll(m);

@@ -189,27 +189,6 @@ __global__ __launch_bounds__(256) void thread_offsets_kernel(const uint64_t *__r
     path_off[r] = kept_before(heads, n_items, n_tiles, km_off[r]);
 }
 
-// the item index of head number s, which lies in a tile before tile b (one lane)
-__device__ inline uint64_t head_item(const CompactWs &h, uint64_t b, uint64_t s) {
-    uint64_t lo = 0, hi = b - 1; // the last tile whose first head is at or before s
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (h.tile_off[mid] <= s) lo = mid;
-        else hi = mid - 1;
-    }
-    const uint32_t rel = (uint32_t)(s - h.tile_off[lo]);
-    const uint64_t w0 = lo * TB_WORDS; // a tile before another one holds all its words
-    uint32_t a = 0, z = TB_WORDS - 1;  // the last word whose prefix is at or below rel
-    while (a < z) {
-        const uint32_t mid = (a + z + 1) >> 1;
-        if (h.wpre[w0 + mid] <= rel) a = mid;
-        else z = mid - 1;
-    }
-    uint64_t m = h.wmask[w0 + a];
-    for (uint32_t k = rel - h.wpre[w0 + a]; k; k--) m &= m - 1; // drop the heads before it
-    return (w0 + a) * 64 + (uint64_t)__ffsll((unsigned long long)m) - 1;
-}
-
 struct ThreadIo {
     const uint64_t *km_off;
     uint64_t n_reads;
