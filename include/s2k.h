@@ -760,7 +760,11 @@ void s2k_fastx_close(s2k_fastx *rd);
  * at a record start and ending at a record end) becomes the (bases, read_off) pair s2k_extract_device consumes.
  * format: S2K_FASTA (multi-line allowed) or S2K_FASTQ (strict 4-line records).  *n_reads / *n_bases always receive
  * the sizes; S2K_ERR_CAPACITY when bases_capacity < *n_bases or off_capacity < *n_reads + 1 (call again),
- * S2K_ERR_INVALID_ARG for malformed text. */
+ * S2K_ERR_INVALID_ARG for malformed text.  FASTQ is rejected when a header line does not start with '@' or a third line
+ * not with '+', when the text ends inside a record (after a header, a sequence or a '+' line), and when a blank line
+ * stands before the first record, between two records or in place of a '+' line; blank lines behind the last record
+ * are accepted.  (s2k_fastx_open / s2k_fastx_next skip blank lines before and between records; s2k_run_file skips
+ * those before the first record and is as strict as this call about the rest.) */
 enum { S2K_FASTA = 0, S2K_FASTQ = 1 };
 s2k_status s2k_fastx_parse_device(s2k_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, int format, uint8_t *d_bases,
                                   uint64_t bases_capacity, uint64_t *d_read_off, uint64_t off_capacity,

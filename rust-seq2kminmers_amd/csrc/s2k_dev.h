@@ -316,9 +316,12 @@ hipError_t launch_hpc_count(const uint8_t *bases, const uint64_t *read_off, uint
 hipError_t launch_hpc_write(const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, const uint64_t *hpc_off,
                             uint8_t *o_hpc, uint32_t *o_pos, uint64_t capacity, hipStream_t st, bool rle = false);
 
-// FASTA/FASTQ record splitting in HBM (s2k_fastx_dev.hip).  count: totals = {records, sequence bytes, syntax errors};
+// FASTA/FASTQ record splitting in HBM (s2k_fastx_dev.hip).  count: totals (FX_N_TOTALS entries) = {records, sequence bytes,
+// syntax errors, and what fx_malformed needs for its verdict on a host copy of them: true = reject the text};
 // write: bases + read_off (n_records + 1 entries).  `ws` holds fx_ws_bytes(n) bytes and must survive both phases.
+enum { FX_TOT_RECORDS = 0, FX_TOT_BASES, FX_TOT_ERR, FX_TOT_BLANK, FX_TOT_LASTLINE, FX_TOT_NEWLINES, FX_N_TOTALS };
 size_t fx_ws_bytes(uint64_t n);
+bool fx_malformed(const uint64_t *h_totals, uint64_t n, int fastq);
 hipError_t fx_parse_count(const uint8_t *d_raw, uint64_t n, int fastq, void *ws, uint64_t *d_totals, hipStream_t st);
 hipError_t fx_parse_write(const uint8_t *d_raw, uint64_t n, int fastq, void *ws, uint64_t *d_totals, uint8_t *d_bases,
                           uint64_t bases_cap, uint64_t *d_read_off, uint64_t off_cap, hipStream_t st);

@@ -304,9 +304,9 @@ s2k_status s2k_fastx_parse_device(s2k_ctx *ctx, const uint8_t *d_text, uint64_t 
     if (hipSetDevice(s2k::ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
     hipStream_t st = s2k::ctx_stream(ctx);
     void *ws = nullptr;
-    uint64_t *d_tot = nullptr, h_tot[3] = {0, 0, 0};
+    uint64_t *d_tot = nullptr, h_tot[s2k::FX_N_TOTALS] = {0};
     s2k_status rc = S2K_OK;
-    if (hipMalloc(&ws, s2k::fx_ws_bytes(n_bytes)) != hipSuccess || hipMalloc((void **)&d_tot, 3 * sizeof(uint64_t)) != hipSuccess)
+    if (hipMalloc(&ws, s2k::fx_ws_bytes(n_bytes)) != hipSuccess || hipMalloc((void **)&d_tot, sizeof h_tot) != hipSuccess)
         rc = S2K_ERR_NOMEM;
     if (rc == S2K_OK && (s2k::fx_parse_count(d_text, n_bytes, format == S2K_FASTQ, ws, d_tot, st) != hipSuccess ||
                          hipMemcpyAsync(h_tot, d_tot, sizeof h_tot, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -315,7 +315,7 @@ s2k_status s2k_fastx_parse_device(s2k_ctx *ctx, const uint8_t *d_text, uint64_t 
     if (rc == S2K_OK) {
         *n_reads = h_tot[0];
         *n_bases = h_tot[1];
-        if (h_tot[2]) {
+        if (s2k::fx_malformed(h_tot, n_bytes, format == S2K_FASTQ)) {
             s2k::ctx_set_error(ctx, "malformed FASTA/FASTQ text (FASTQ must be strict 4-line records)");
             rc = S2K_ERR_INVALID_ARG;
         } else if (h_tot[1] > bases_capacity || h_tot[0] + 1 > off_capacity || !d_bases || !d_read_off) {
@@ -395,8 +395,8 @@ s2k_status run_file_impl(s2k_ctx *ctx, const char *path, const s2k_params *param
     uint64_t *d_tot = nullptr, *h_tot = nullptr;
     bool ok = hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&parsed, hipEventDisableTiming) == hipSuccess &&
-              hipMalloc((void **)&d_tot, 3 * sizeof(uint64_t)) == hipSuccess &&
-              hipHostMalloc((void **)&h_tot, 3 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
+              hipMalloc((void **)&d_tot, s2k::FX_N_TOTALS * sizeof(uint64_t)) == hipSuccess &&
+              hipHostMalloc((void **)&h_tot, s2k::FX_N_TOTALS * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
     s2k_status st = ok ? S2K_OK : S2K_ERR_DEVICE;
 
     auto launch = [&](Slot &d, uint64_t cap, bool wait) -> s2k_status { // k-min-mers of the batch held by slot d
@@ -486,13 +486,13 @@ s2k_status run_file_impl(s2k_ctx *ctx, const char *path, const s2k_params *param
             e = s2k::ctx_stager(ctx).h2d_fill(d.raw, n, copy_stream, from_file);
         }
         if (e == hipSuccess) e = s2k::fx_parse_count((const uint8_t *)d.raw, n, fastq == 1, d.ws, d_tot, copy_stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_tot, d_tot, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, copy_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_tot, d_tot, s2k::FX_N_TOTALS * sizeof(uint64_t), hipMemcpyDeviceToHost, copy_stream);
         if (e == hipSuccess) e = hipStreamSynchronize(copy_stream);
         if (e != hipSuccess) {
             st = S2K_ERR_DEVICE;
             break;
         }
-        if (h_tot[2]) {
+        if (s2k::fx_malformed(h_tot, n, fastq == 1)) {
             s2k::ctx_set_error(ctx, "malformed FASTA/FASTQ text (FASTQ must be strict 4-line records)");
             st = S2K_ERR_INVALID_ARG;
             break;

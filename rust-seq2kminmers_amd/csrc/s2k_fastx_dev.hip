@@ -12,6 +12,8 @@
 // work is three streaming passes over the text:
 //   pass 0  newline count + last line start of every block
 //   pass 1  with those carries: classify bytes, count sequence bytes / record starts per block, flag bad syntax
+//           (FASTQ: also the last line that holds anything and the blank lines where a header or a '+' line belongs,
+//           from which fx_malformed tells a truncated text or a blank line inside it from trailing blank lines)
 //   pass 2  with all three carries: write sequence bytes compacted and read_off[record] = bases before it
 // Each pass is bound by HBM; for a 256 MB chunk the three take well under a millisecond each.
 #include "s2k_dev.h"
@@ -81,33 +83,38 @@ __device__ __forceinline__ void newlines16(const Bytes16 &b, uint64_t pos, uint3
 
 struct Roles {
     uint32_t seq, rec, err; // bit j: byte j is a sequence byte / is the first byte of a record
+    uint32_t blank, last;   // FASTQ: blank lines at an even line index that end in these bytes; 1 + index of the last line that begins here
 };
 
 // nl_before = newlines before this thread's first byte; line_start = start of the line that byte belongs to
 __device__ __forceinline__ Roles classify16(const uint8_t *raw, const Bytes16 &b, uint64_t pos, uint32_t nl_before,
-                                            uint32_t line_start, int fastq) {
-    Roles r{0, 0, 0};
+                                            uint32_t line_start, int fastq, uint64_t n) {
+    Roles r{0, 0, 0, 0, 0};
     bool at_ls = line_start == pos;
     if (fastq) {
-        uint32_t line = nl_before & 3;
+        // the '\r' of a "\r\n" line may be the previous thread's last byte: the line has not begun yet
+        if (!at_ls && line_start + 1 == pos && raw[line_start] == '\r') at_ls = true;
+        uint32_t line = nl_before; // index of the line; & 3 = header / sequence / '+' / quality
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             const uint8_t c = b.c[j];
             if (c == '\n') {
-                line = (line + 1) & 3;
+                if (at_ls && !(line & 1) && pos + j < n) r.blank++; // (the padding behind the text does not count)
+                line++;
                 at_ls = true;
                 continue;
             }
             if (c == '\r') continue;
             if (at_ls) {
-                if (line == 0) {
+                if ((line & 3) == 0) {
                     if (c == '@') r.rec |= 1u << j;
                     else r.err++;
-                } else if (line == 2 && c != '+')
+                } else if ((line & 3) == 2 && c != '+')
                     r.err++;
+                r.last = line + 1;
                 at_ls = false;
             }
-            if (line == 1) r.seq |= 1u << j;
+            if ((line & 3) == 1) r.seq |= 1u << j;
         }
     } else {
         bool hdr = !at_ls && raw[line_start] == '>';
@@ -143,8 +150,10 @@ __global__ __launch_bounds__(FX_THREADS) void fx_pass0(const uint8_t *raw, uint6
     }
 }
 
-// exclusive scans over the per-block arrays, in place: sums for a (and c when given), max for m
-__global__ __launch_bounds__(1024) void fx_scan_blocks(uint32_t *a, uint32_t *m, uint32_t *c, uint32_t nb, uint64_t *totals) {
+// exclusive scans over the per-block arrays, in place: sums for a (and c when given), max for m; the totals go to
+// tot_a / tot_m / tot_c where given
+__global__ __launch_bounds__(1024) void fx_scan_blocks(uint32_t *a, uint32_t *m, uint32_t *c, uint32_t nb, uint64_t *tot_a,
+                                                       uint64_t *tot_m, uint64_t *tot_c) {
     __shared__ uint32_t sa[1024], sm[1024], sc[1024];
     const int t = threadIdx.x;
     uint32_t ca = 0, cm = 0, cc = 0;
@@ -184,16 +193,17 @@ __global__ __launch_bounds__(1024) void fx_scan_blocks(uint32_t *a, uint32_t *m,
         cm = tm > cm ? tm : cm;
         cc += tc;
     }
-    if (t == 0 && totals) {
-        totals[0] = cc; // records   (second sum)
-        totals[1] = ca; // sequence bytes (first sum)
+    if (t == 0) {
+        if (tot_a) *tot_a = ca;
+        if (tot_m) *tot_m = cm;
+        if (tot_c) *tot_c = cc;
     }
 }
 
 template <bool WRITE>
 __global__ __launch_bounds__(FX_THREADS) void fx_pass12(const uint8_t *raw, uint64_t n, int fastq, const uint32_t *bnl_ex,
                                                        const uint32_t *blast_ex, uint32_t *bseq, uint32_t *brec,
-                                                       uint64_t *totals, uint8_t *bases, uint64_t bases_cap,
+                                                       uint32_t *blastline, uint64_t *totals, uint8_t *bases, uint64_t bases_cap,
                                                        uint64_t *read_off, uint64_t off_cap) {
     __shared__ uint32_t ls[FX_THREADS], lm[FX_THREADS];
     const uint64_t pos = (uint64_t)blockIdx.x * FX_BLOCK + threadIdx.x * FX_PER;
@@ -204,21 +214,24 @@ __global__ __launch_bounds__(FX_THREADS) void fx_pass12(const uint8_t *raw, uint
     const uint32_t nl_before = bnl_ex[blockIdx.x] + es;
     const uint32_t carry = blast_ex[blockIdx.x];
     const uint32_t line_start = em > carry ? em : carry;
-    const Roles r = classify16(raw, b, pos, nl_before, line_start, fastq);
+    const Roles r = classify16(raw, b, pos, nl_before, line_start, fastq, n);
     const uint32_t nseq = __popc(r.seq), nrec = __popc(r.rec);
     uint32_t e_seq, e_rec, t_seq, t_rec;
-    block_scan(nseq, 0, &e_seq, &em, &t_seq, &tm, ls, lm);
+    uint32_t t_last;
+    block_scan(nseq, r.last, &e_seq, &em, &t_seq, &t_last, ls, lm); // (the max rides along in the scan of the sequence bytes)
     block_scan(nrec, 0, &e_rec, &em, &t_rec, &tm, ls, lm);
     if constexpr (!WRITE) {
         if (threadIdx.x == 0) {
             bseq[blockIdx.x] = t_seq;
             brec[blockIdx.x] = t_rec;
+            blastline[blockIdx.x] = t_last;
         }
-        if (r.err) atomicAdd((unsigned long long *)&totals[2], (unsigned long long)r.err);
+        if (r.err) atomicAdd((unsigned long long *)&totals[FX_TOT_ERR], (unsigned long long)r.err);
+        if (r.blank) atomicAdd((unsigned long long *)&totals[FX_TOT_BLANK], (unsigned long long)r.blank); // rare: behind the last record, or malformed
     } else {
         uint64_t so = (uint64_t)bseq[blockIdx.x] + e_seq; // sequence bytes before this thread's first byte
         uint64_t ro = (uint64_t)brec[blockIdx.x] + e_rec;
-        if (blockIdx.x == 0 && threadIdx.x == 0 && totals[0] < off_cap) read_off[totals[0]] = totals[1];
+        if (blockIdx.x == 0 && threadIdx.x == 0 && totals[FX_TOT_RECORDS] < off_cap) read_off[totals[FX_TOT_RECORDS]] = totals[FX_TOT_BASES];
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             if ((r.rec >> j) & 1) {
@@ -237,21 +250,41 @@ __global__ __launch_bounds__(FX_THREADS) void fx_pass12(const uint8_t *raw, uint
 
 size_t fx_ws_bytes(uint64_t n) {
     const uint64_t nb = (n + FX_BLOCK - 1) / FX_BLOCK + 1;
-    return (size_t)(4 * nb * sizeof(uint32_t) + 256);
+    return (size_t)(5 * nb * sizeof(uint32_t) + 256);
 }
 
-// Phase A (count): after it, d_totals = { n_records, n_sequence_bytes, n_syntax_errors }.
+// Phase A (count): after it, d_totals (FX_N_TOTALS entries) = { n_records, n_sequence_bytes, n_syntax_errors, ... }: fx_malformed
+// reads the rest.
 // Phase B (write): fills d_bases[0..n_seq) and d_read_off[0..n_records].  Both are stream-ordered.
 hipError_t fx_parse_count(const uint8_t *d_raw, uint64_t n, int fastq, void *ws, uint64_t *d_totals, hipStream_t st) {
     const uint32_t nb = (uint32_t)((n + FX_BLOCK - 1) / FX_BLOCK);
-    hipError_t e = hipMemsetAsync(d_totals, 0, 3 * sizeof(uint64_t), st);
+    hipError_t e = hipMemsetAsync(d_totals, 0, FX_N_TOTALS * sizeof(uint64_t), st);
     if (e != hipSuccess || nb == 0) return e;
-    uint32_t *bnl = (uint32_t *)ws, *blast = bnl + nb, *bseq = blast + nb, *brec = bseq + nb;
+    uint32_t *bnl = (uint32_t *)ws, *blast = bnl + nb, *bseq = blast + nb, *brec = bseq + nb, *blastline = brec + nb;
     fx_pass0<<<nb, FX_THREADS, 0, st>>>(d_raw, n, bnl, blast);
-    fx_scan_blocks<<<1, 1024, 0, st>>>(bnl, blast, nullptr, nb, nullptr);
-    fx_pass12<false><<<nb, FX_THREADS, 0, st>>>(d_raw, n, fastq, bnl, blast, bseq, brec, d_totals, nullptr, 0, nullptr, 0);
-    fx_scan_blocks<<<1, 1024, 0, st>>>(bseq, nullptr, brec, nb, d_totals);
+    fx_scan_blocks<<<1, 1024, 0, st>>>(bnl, blast, nullptr, nb, d_totals + FX_TOT_NEWLINES, nullptr, nullptr);
+    fx_pass12<false><<<nb, FX_THREADS, 0, st>>>(d_raw, n, fastq, bnl, blast, bseq, brec, blastline, d_totals, nullptr, 0, nullptr, 0);
+    fx_scan_blocks<<<1, 1024, 0, st>>>(bseq, blastline, brec, nb, d_totals + FX_TOT_BASES, d_totals + FX_TOT_LASTLINE,
+                                       d_totals + FX_TOT_RECORDS);
     return hipGetLastError();
+}
+
+// The verdict on the totals of phase A (host copy).  FASTA: the syntax errors.  FASTQ is strict 4-line records and nothing but
+// blank lines behind the last one.  A line that is not blank where a header or a '+' line belongs is a syntax error already; the
+// rest is counting.  Let `full` be the end of the last 4-line group that holds anything.  The text has to reach it (else it ends
+// inside a record), and the blank lines at even line indices -- the places of header and '+' lines -- must be exactly those
+// behind `full` (else one stands before the first record, between two records, or for a '+' line).
+bool fx_malformed(const uint64_t *t, uint64_t n, int fastq) {
+    if (t[FX_TOT_ERR]) return true;
+    if (!fastq) return false;
+    const uint64_t nb = (n + FX_BLOCK - 1) / FX_BLOCK;
+    const uint64_t newlines = t[FX_TOT_NEWLINES] - (nb * FX_BLOCK - n); // the last block is padded with '\n'
+    const uint64_t last = t[FX_TOT_LASTLINE];                           // 1 + index of the last line that is not blank
+    const uint64_t lines = newlines > last ? newlines : last;           // (a last line without '\n' is not blank)
+    const uint64_t full = (last + 3) & ~(uint64_t)3;
+    if (lines < full) return true;
+    const uint64_t want = newlines > full ? (newlines - full + 1) / 2 : 0;
+    return t[FX_TOT_BLANK] != want;
 }
 
 hipError_t fx_parse_write(const uint8_t *d_raw, uint64_t n, int fastq, void *ws, uint64_t *d_totals, uint8_t *d_bases,
@@ -259,7 +292,7 @@ hipError_t fx_parse_write(const uint8_t *d_raw, uint64_t n, int fastq, void *ws,
     const uint32_t nb = (uint32_t)((n + FX_BLOCK - 1) / FX_BLOCK);
     if (nb == 0) return hipMemsetAsync(d_read_off, 0, sizeof(uint64_t), st);
     uint32_t *bnl = (uint32_t *)ws, *blast = bnl + nb, *bseq = blast + nb, *brec = bseq + nb;
-    fx_pass12<true><<<nb, FX_THREADS, 0, st>>>(d_raw, n, fastq, bnl, blast, bseq, brec, d_totals, d_bases, bases_cap,
+    fx_pass12<true><<<nb, FX_THREADS, 0, st>>>(d_raw, n, fastq, bnl, blast, bseq, brec, nullptr, d_totals, d_bases, bases_cap,
                                                d_read_off, off_cap);
     return hipGetLastError();
 }
