@@ -47,6 +47,7 @@ extern "C" {
  * added entry points and one new struct, the version stays 2.)
  * (s2k_table_representatives, s2k_table_node_sequences, s2k_unitig_sequences and the struct s2k_node_seqs were added the same way.)
  * (s2k_paths_spans and s2k_graph_resolve_mask were added the same way: added entry points, the version stays 2.)
+ * (s2k_paths_bridge was added the same way: an added entry point, the version stays 2.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -714,6 +715,44 @@ s2k_status s2k_paths_walks(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out 
                            const uint64_t *d_member_off, const uint64_t *d_out_off, const uint32_t *d_overlap, const uint32_t *d_seq_len,
                            const uint32_t *d_members, uint64_t n_nodes, const s2k_walk_out *out, uint64_t *n_walks, uint64_t *n_followed,
                            uint64_t *n_off_graph);
+/* ---- bridged read paths: error gaps closed along the graph ---------------------------------------------------------
+ * Inputs: the path arrays s2k_table_thread wrote (path_off, unitig, pos, count, item and flags are required with n_steps > 0; start and
+ * end are optional, and out->start / out->end must be NULL when theirs is), the CSR over the oriented unitigs (d_row_off, d_dst,
+ * n_edges), d_uni_off, d_circular, n_unitigs, and the limits max_gap and max_slip, in items.  find(A, B) as for s2k_paths_spans.
+ * Join.  For step s that is not its read's first step let a = unitig[s - 1], b = unitig[s], endp = pos[s - 1] + count[s - 1], la = the
+ * members of a's unitig, gi = item[s] - (item[s - 1] + count[s - 1]): the read's items between the two steps.  join[s] is decided in
+ * this order: it is 0 if either unitig is circular; if a == b and pos[s] >= endp the kind is 1 (the same unitig) and gp = pos[s] -
+ * endp; otherwise, if find(a, b) exists, the kind is 2 (across one edge) and gp = (la - endp) + pos[s]; otherwise it is 0.  The kind
+ * stands iff gi <= max_gap, gp <= max_gap and |gi - gp| <= max_slip; otherwise join[s] = 0.  A read's first step has join 0.  A step
+ * that already follows an edge is kind 2 with gi = gp = 0 and comes out unchanged; a == b going backwards is kind 2 only over a loop
+ * edge.
+ * Output steps.  A run is a maximal sequence of steps s_a .. s_b of one read with join == 1 on all but the first; every run gives one
+ * output step, in step order: unitig = unitig[s_a]; pos = 0 if join[s_a] == 2, else pos[s_a]; count = endpos - pos, where endpos = the
+ * members of the unitig if step s_b + 1 is of the same read and join[s_b + 1] == 2, else pos[s_b] + count[s_b]; item = item[s_a]; flags
+ * = flags[s_a] | (join[s_a] == 2 ? S2K_STEP_LINKED : 0); start = start[s_a]; end = end[s_b]; matched = the sum of the run's input
+ * counts.  So in bridged paths count is "positions covered", the gaps included, and matched is "k-min-mers really found" (matched ==
+ * count on paths nothing was bridged in); item + count may pass the next step's item by up to max_slip per join.  Downstream the
+ * bridged paths are paths like any other: s2k_paths_spans and s2k_paths_walks take them as they are, and a walk's `items` over them
+ * counts positions, not found k-min-mers.
+ * Not done: a wholly missing unitig between two steps (two edges) is not bridged; a gap is judged in items only, with no base-space
+ * plausibility check (start / end are carried, not compared); steps on circular unitigs are never joined.
+ *
+ * s2k_paths_bridge: *n_out_steps, *n_merged (joins of kind 1) and *n_bridged (joins of kind 2 with gi + gp > 0) are always set.
+ * out->path_off (required, n_reads + 1) and d_join (may be NULL; one byte per input step) are written whenever the call returns
+ * S2K_OK.  The step arrays of `out` (each may be NULL) and d_matched (may be NULL; one uint32_t per output step) are written only when
+ * *n_out_steps <= out->capacity; otherwise S2K_ERR_CAPACITY and nothing at all is written; all of them NULL asks for the sizes only.
+ * Outputs must not overlap inputs.  Checked on the device before anything is written, one flag word read by the host,
+ * S2K_ERR_INVALID_ARG otherwise: the path and CSR rules of s2k_paths_walks (path_off from 0 to n_steps without decreasing; every unitig
+ * < 2 n_unitigs; count >= 1, pos < len and, unless the unitig is circular, pos + count <= len; the row_off rules, every id below 2
+ * n_unitigs; uni_off strictly ascending), no unitig of 2^32 members or more, and item[s] >= item[s - 1] + count[s - 1] inside a read,
+ * so that gi cannot wrap.  n_unitigs >= 2^31 and n_edges >= 2^32 are refused.  Twin symmetry and the order inside a row are trusted.
+ * Heads and tails of runs come from ballots and scans, matched from a prefix difference; there is no atomic on an output: every
+ * output is a function of the input, bit-identical from call to call.  Uses the context's grow-only count workspace: about 9.4 B per
+ * step.  Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_paths_bridge(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *paths, uint64_t n_steps, const uint64_t *d_row_off,
+                            const uint32_t *d_dst, uint64_t n_edges, const uint64_t *d_uni_off, const uint8_t *d_circular, uint64_t n_unitigs,
+                            uint32_t max_gap, uint32_t max_slip, const s2k_thread_out *out, uint32_t *d_matched, uint8_t *d_join,
+                            uint64_t *n_out_steps, uint64_t *n_merged, uint64_t *n_bridged);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

@@ -297,6 +297,21 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return t;
     }
+    // s2k_paths_bridge: one batch's paths with the error gaps bridged over the CSR (steps a few items apart on one unitig merged, steps a
+    // few items apart across one edge extended to it; max_gap, max_slip in items).  out.path_off is required; the step arrays of `out`
+    // and d_matched all nullptr: the sizes only.  d_join: one byte per input step.  Throws on S2K_ERR_CAPACITY too (nothing written).
+    struct BridgeTotals {
+        uint64_t steps, merged, bridged;
+    };
+    BridgeTotals paths_bridge(uint64_t n_reads, const s2k_thread_out &paths, uint64_t n_steps, const uint64_t *d_row_off, const uint32_t *d_dst,
+                              uint64_t n_edges, const uint64_t *d_uni_off, const uint8_t *d_circular, uint64_t n_unitigs, uint32_t max_gap,
+                              uint32_t max_slip, const s2k_thread_out &out, uint32_t *d_matched = nullptr, uint8_t *d_join = nullptr) {
+        BridgeTotals t{};
+        s2k_status st = s2k_paths_bridge(ctx_, n_reads, &paths, n_steps, d_row_off, d_dst, n_edges, d_uni_off, d_circular, n_unitigs, max_gap, max_slip,
+                                         &out, d_matched, d_join, &t.steps, &t.merged, &t.bridged);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

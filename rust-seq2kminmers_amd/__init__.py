@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "s2k_paths_spans", "s2k_graph_resolve_mask",
     "s2k_graph_untangle", "s2k_unitig_expand",
     "s2k_unitig_member_offsets", "s2k_paths_walks",
+    "s2k_paths_bridge",
 ]
 
 
@@ -225,6 +226,9 @@ def load_library(path=None):
     L.s2k_paths_walks.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ThreadOut), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(WalkOut),
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_paths_bridge.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ThreadOut), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                   C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ThreadOut), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -812,6 +816,49 @@ class Engine:
         out.update(n_walks=m, n_followed=int(nf.value), n_off_graph=int(no.value))
         return out
 
+    def paths_bridge(self, unitig_graph, paths, max_gap, max_slip, join=False):
+        """One batch's ReadPaths with the error gaps bridged over a UnitigGraph (s2k_paths_bridge; the definitions are in include/s2k.h):
+        steps at most max_gap items apart on one unitig are merged, steps at most max_gap items apart across one edge are extended to
+        the edge, where the gap in the read and the gap on the graph differ by at most max_slip.  Two calls: the sizes, then the arrays.
+        -> dict of GPU tensors path_off (int64, n_reads + 1), unitig, pos, count, item, flags, matched (int32; start, end only when the
+        paths carry them), join (uint8 per input step: 0 none, 1 the same unitig, 2 across an edge; only with join=True), and the ints
+        n_steps, n_merged, n_bridged."""
+        import torch
+
+        ug, dev = unitig_graph, paths.path_off.device
+        t, ne, ns, nr = ug.n_unitigs, ug.dst.numel(), paths.n_steps, paths.path_off.numel() - 1
+        row_off, dst, uni_off, circular = (x.contiguous() for x in (ug.row_off, ug.dst, ug.uni_off, ug.circular))
+        if (row_off.numel() != 2 * t + 1 or row_off.element_size() != 8 or dst.element_size() != 4 or uni_off.numel() != t + 1 or uni_off.element_size() != 8
+                or circular.element_size() != 1):
+            raise ValueError("paths_bridge wants a UnitigGraph: the CSR over its oriented unitigs, uni_off and circular")
+        i = ThreadOut()
+        i.capacity = ns
+        keep = {f: getattr(paths, f).contiguous() for f in ("path_off",) + ReadPaths.STEP_FIELDS if getattr(paths, f) is not None}
+        for f, x in keep.items():
+            setattr(i, f, x.data_ptr() if x.numel() else 0)
+        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
+        args = (self.ctx, nr, C.byref(i), ns, p(row_off), p(dst, ne), ne, p(uni_off), p(circular, t), t, int(max_gap), int(max_slip))
+        res = {"path_off": torch.zeros(nr + 1, dtype=torch.int64, device=dev)}
+        o = ThreadOut()
+        o.path_off = res["path_off"].data_ptr()
+        no, nm, nb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_paths_bridge(*args, C.byref(o), None, None, C.byref(no), C.byref(nm), C.byref(nb)))
+        m = int(no.value)
+        for f in [f for f in ReadPaths.STEP_FIELDS if f in keep] + ["matched"]:
+            res[f] = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+            if f != "matched":
+                setattr(o, f, res[f].data_ptr())
+        if join:
+            res["join"] = torch.empty(max(ns, 1), dtype=torch.uint8, device=dev)
+        o.capacity = m
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_paths_bridge(*args, C.byref(o), p(res["matched"]), p(res["join"]) if join else None, C.byref(no), C.byref(nm),
+                                              C.byref(nb)))
+        out = {f: (x if f == "path_off" else x[:ns] if f == "join" else x[:m]) for f, x in res.items()}
+        out.update(n_steps=m, n_merged=int(nm.value), n_bridged=int(nb.value))
+        return out
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -1328,6 +1375,21 @@ class UnitigGraph:
         contigs.n_nodes = x["n_members"]
         return contigs, x["node_origin"], {"copies": tc, "duplicated": u["n_duplicated"], "contigs": o["n_unitigs"]}
 
+    def bridge(self, engine, paths, max_gap=16, max_slip=2):
+        """One batch's ReadPaths with the gaps that read errors cut into them bridged along this graph (Engine.paths_bridge;
+        include/s2k.h: s2k_paths_bridge) -> (ReadPaths, stats).  Two consecutive steps of a read are joined when they lie on one unitig
+        (merged into one step), or on two unitigs that an edge joins (the first extended to its unitig's end, the second back to position
+        0 and marked STEP_LINKED), with at most max_gap items missing in the read and at most max_gap positions on the graph, the two
+        differing by at most max_slip.  In the returned paths count is the positions a step covers, the gaps included, and the new
+        attribute matched is the k-min-mers really found; they work in spans, span_table, walks, write_paths and write_gaf as they are
+        (a walk's items then counts positions).  stats = {"steps_in", "steps_out", "merged", "bridged"}.
+        The defaults 16 and 2 come from the repeat fixture of the tests at l = 12, k = 5 with 1 % substitutions (one substitution
+        removes up to k consecutive k-min-mers); they are not tuned on real data.  Not bridged: a wholly missing unitig between two
+        steps, and anything on a circular unitig; a gap is judged in items, not in bases."""
+        b = engine.paths_bridge(self, paths, max_gap, max_slip)
+        stats = {"steps_in": paths.n_steps, "steps_out": b["n_steps"], "merged": b["n_merged"], "bridged": b["n_bridged"]}
+        return ReadPaths(b["path_off"], **{f: b[f] for f in ReadPaths.STEP_FIELDS + ("matched",) if f in b}), stats
+
     def member_offsets(self, engine, node_seqs):
         """Where every member's piece starts in the unitigs' bases (Engine.unitig_member_offsets) -> (member_off, out_off, overlap,
         n_bases), computed once per NodeSequences and kept"""
@@ -1361,22 +1423,24 @@ class ReadPaths:
     """The paths of one batch of reads (UnitigGraph.thread; include/s2k.h: s2k_table_thread): the steps of read r are path_off[r] ..
     path_off[r + 1]; step s runs along the oriented unitig unitig[s] (2 t + strand) from position pos[s] over count[s] items, its first
     item is item[s] of the read, flags[s] & STEP_LINKED tells that the read entered it over a graph adjacency (not a gap), start[s] /
-    end[s] (None when the extraction kept none) are the read's bases it covers.  GPU tensors: path_off int64, the rest int32 holding
-    the uint32 values."""
+    end[s] (None when the extraction kept none) are the read's bases it covers.  matched[s] (None but on the paths
+    UnitigGraph.bridge returned) is the k-min-mers really found in a step whose count, after bridging, is the positions it covers.
+    GPU tensors: path_off int64, the rest int32 holding the uint32 values."""
 
     STEP_FIELDS = ("unitig", "pos", "count", "item", "flags", "start", "end")
 
-    def __init__(self, path_off, unitig, pos, count, item, flags, start=None, end=None):
+    def __init__(self, path_off, unitig, pos, count, item, flags, start=None, end=None, matched=None):
         self.path_off, self.unitig, self.pos, self.count, self.item, self.flags, self.start, self.end = path_off, unitig, pos, count, item, flags, start, end
+        self.matched = matched
 
     @property
     def n_steps(self):
         return self.unitig.numel()
 
     def host(self):
-        """-> dict of numpy arrays: path_off uint64, the step arrays uint32 (start / end only when present)"""
+        """-> dict of numpy arrays: path_off uint64, the step arrays uint32 (start / end / matched only when present)"""
         d = {"path_off": self.path_off.cpu().numpy().view(np.uint64)}
-        for f in self.STEP_FIELDS:
+        for f in self.STEP_FIELDS + ("matched",):
             if getattr(self, f) is not None:
                 d[f] = getattr(self, f).cpu().numpy().view(np.uint32)
         return d
