@@ -48,6 +48,7 @@ extern "C" {
  * (s2k_table_representatives, s2k_table_node_sequences, s2k_unitig_sequences and the struct s2k_node_seqs were added the same way.)
  * (s2k_paths_spans and s2k_graph_resolve_mask were added the same way: added entry points, the version stays 2.)
  * (s2k_paths_bridge was added the same way: an added entry point, the version stays 2.)
+ * (s2k_unitig_copy_places, s2k_paths_lift and S2K_NO_COPY were added the same way: added entry points, the version stays 2.)
  * A binding must refuse a library whose s2k_abi_version() differs from the header it was built against. */
 #define S2K_ABI_VERSION 2
 
@@ -753,6 +754,76 @@ s2k_status s2k_paths_bridge(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out
                             const uint32_t *d_dst, uint64_t n_edges, const uint64_t *d_uni_off, const uint8_t *d_circular, uint64_t n_unitigs,
                             uint32_t max_gap, uint32_t max_slip, const s2k_thread_out *out, uint32_t *d_matched, uint8_t *d_join,
                             uint64_t *n_out_steps, uint64_t *n_merged, uint64_t *n_bridged);
+/* ---- read paths lifted onto the untangled contigs -----------------------------------------------------------------------
+ * Where every copy lies.  Input: the outer decomposition that s2k_graph_unitigs wrote over the n_copies copies of s2k_graph_untangle
+ * (d_outer_off, d_outer_members, d_outer_circular, n_contigs), d_origin of s2k_graph_untangle, and d_uni_off, d_circular of the n_unitigs
+ * unitigs the copies were made of.  Let the outer member at slot p of contig t be C = 2 c + s, f = the members of all pieces before slot
+ * p in that contig, m = the members of unitig origin[c], Lc = the node instances of contig t as s2k_unitig_expand counts them.
+ * d_copy_place[c] (n_copies records of s2k_node_place, 16-byte aligned) says where the forward oriented copy 2 c lies: unitig = 2 t + s,
+ * the oriented contig; pos = s ? Lc - f - m : f; len = Lc; circular = what s2k_unitig_expand writes to circular_out[t].
+ * Checked on the device before anything is written, one flag word read by the host, S2K_ERR_INVALID_ARG otherwise: the rules of
+ * s2k_unitig_expand on the same arrays (the outer uni_off ascends strictly from 0 to n_copies, the inner one strictly from 0 -- its
+ * end cannot be checked without n_nodes; every outer member is below 2 n_copies; every origin it names is below n_unitigs), every copy
+ * is named by exactly one outer member (so every record has one writer), and no unitig or contig has 2^32 members or more.  n_copies
+ * >= 2^31 is refused; n_copies == 0 reads and writes nothing.  One lane per outer member for the piece lengths, a scan, one lane per
+ * outer member to write, its contig by a binary search of d_outer_off.  No atomic on an output.  Workspace: 16 B per copy of the
+ * context's grow-only count workspace.  Runs on the context's stream; returns when the records are written. */
+s2k_status s2k_unitig_copy_places(s2k_ctx *ctx, const uint64_t *d_outer_off, const uint32_t *d_outer_members, const uint8_t *d_outer_circular,
+                                  uint64_t n_contigs, uint64_t n_copies, const uint32_t *d_origin, const uint64_t *d_uni_off, const uint8_t *d_circular,
+                                  uint64_t n_unitigs, s2k_node_place *d_copy_place);
+/* The lift.  Inputs: the path arrays of an s2k_thread_out on the OLD unitig graph (path_off, unitig, pos, count, item and flags are
+ * required with n_steps > 0; start and end are optional, and out->start / out->end must be NULL when theirs is); d_matched_in (may be
+ * NULL), the matched of bridged paths; the old CSR (d_row_off, d_dst, n_edges) with d_uni_off, d_circular, n_unitigs; d_resolved and
+ * d_partner as s2k_graph_untangle took them and d_copy_off (n_unitigs + 1) as it wrote it; d_copy_place (n_copies records) from the
+ * call above; n_contigs.  "Step s follows edge e" and tw(e) are exactly as for s2k_paths_spans; len[t], base(t) = row_off[2 t + 1] and
+ * ncopies(t) = copy_off[t + 1] - copy_off[t] as for s2k_graph_untangle.
+ * Copy of a step.  Step s lies on U = unitig[s], t = U >> 1.  If t is not resolved, j = 0.  Otherwise, if s follows an edge e (it enters
+ * U): j = tw(e) - base(t) for U even, j = partner[e] - base(t) for U odd -- jB of s2k_graph_untangle.  Otherwise, if step s + 1 is of
+ * the same read and follows an edge e' (it leaves U): j = e' - base(t) for U odd, j = partner[tw(e')] - base(t) for U even -- jA.
+ * Otherwise the step is ambiguous: it lies on a duplicated unitig and the read shows neither the way in nor the way out; it is dropped
+ * and counted in *n_dropped.  Where both edges exist and give different j the entering edge wins and the step is counted in
+ * *n_conflicts: the read crossed the repeat by a pair the matching did not keep, and in the new graph its next step follows no edge.
+ * A j outside [0, ncopies(t)) is possible only where the trusted symmetry does not hold; it becomes 0, so that every access stays
+ * inside the arrays (the rule of s2k_graph_untangle).  c = copy_off[t] + j.
+ * Mapped position.  With rec = copy_place[c], m = len[t], su = U & 1: V = rec.unitig ^ su; q' = su ? rec.len - rec.pos - m + pos[s] :
+ * rec.pos + pos[s].
+ * Join.  join[s] = 1 iff steps s - 1 and s are of one read, both are kept, s follows an edge, V(s) == V(s - 1) and q'(s) == q'(s - 1) +
+ * count[s - 1] -- on a circular contig taken modulo rec.len, the wrap s2k_table_thread allows on a circular unitig; otherwise 0.  This
+ * holds exactly when the new edge between the two copies was compacted into a contig: there is one old edge per pair (A, B) and every
+ * old edge becomes exactly one new edge, between the copies this rule picks (jA, jB), so the step follows THAT new edge; the compaction
+ * joins two copies only along an edge, in path order, so two copies lie side by side on one contig strand, the second beginning where
+ * the first ends, iff the compaction went along that edge (a contig of one copy joined to itself end to end is circular, a cycle of
+ * copies closes modulo its length).
+ * Output steps.  One output step per maximal run s_a .. s_b of kept steps with join == 1 on all but the first, in step order: unitig =
+ * V(s_a); pos = q'(s_a); count = the sum of the run's counts (modulo 2^32; a run on a contig that is not circular stays inside it); item
+ * = item[s_a]; flags = flags[s_a]; start = start[s_a]; end = end[s_b]; matched = the sum of matched_in over the run, or of count when
+ * d_matched_in is NULL.  A dropped step is in no run; by its definition the step after it follows no edge, so heads and tails pair one
+ * to one.  The lifted paths are paths on the contig graph like any other: s2k_paths_spans, s2k_paths_walks and s2k_paths_bridge take
+ * them as they are.  The item order is not checked (bridged paths may overlap by max_slip).
+ *
+ * s2k_paths_lift: *n_out_steps, *n_merged (joins), *n_dropped and *n_conflicts are always set.  out->path_off (required, n_reads + 1),
+ * d_step_copy (may be NULL; one uint32_t per INPUT step: the copy c, S2K_NO_COPY when dropped) and d_join (may be NULL; one byte per
+ * input step) are written, and d_contig_items (may be NULL; n_contigs uint64_t: [V >> 1] += count for every output step; the caller
+ * zeroes it and it accumulates over batches, the rule of d_uni_items of s2k_table_thread, a sizes-only call included) gains, whenever
+ * the call returns S2K_OK.  The step arrays of `out` (each may be NULL) and d_matched (may be NULL; one uint32_t per output step) are
+ * written only when *n_out_steps <= out->capacity; otherwise S2K_ERR_CAPACITY and nothing at all is written; all of them NULL asks for
+ * the sizes only.  Outputs must not overlap inputs.  Checked on the device before anything is written, one flag word read by the
+ * host, S2K_ERR_INVALID_ARG otherwise: the path and CSR rules of s2k_paths_bridge but for the item order; d_resolved bytes 0 or 1;
+ * copy_off from 0, copy_off[n_unitigs] == n_copies, copy_off[t + 1] - copy_off[t] == out(2 t) >= 1 for a resolved t and 1 otherwise;
+ * every copy record has unitig < 2 n_contigs, pos + len[t] <= len and circular 0 or 1.  n_unitigs >= 2^31, n_copies >= 2^31 and
+ * n_edges >= 2^32 are refused.  Twin symmetry, the order inside a row and the partner rules that s2k_graph_untangle checks are
+ * trusted.  Kept steps, heads and tails of runs come from ballots and scans, the sums from prefix differences; the only atomic on an
+ * output is the integer sum into d_contig_items (one per kept input step: the steps of a run lie on one contig): every output is a
+ * function of the input, bit-identical from call to call.  Uses the context's grow-only count workspace: about 21.4 B per step (join
+ * 1, copy 4, the prefixes of count and matched_in 8 each, two masks).  Runs on the context's stream; returns when the outputs are
+ * written. */
+#define S2K_NO_COPY 0xFFFFFFFFu
+s2k_status s2k_paths_lift(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *paths, uint64_t n_steps, const uint32_t *d_matched_in,
+                          const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, const uint64_t *d_uni_off, const uint8_t *d_circular,
+                          uint64_t n_unitigs, const uint8_t *d_resolved, const uint32_t *d_partner, const uint64_t *d_copy_off,
+                          const s2k_node_place *d_copy_place, uint64_t n_copies, uint64_t n_contigs, const s2k_thread_out *out, uint32_t *d_matched,
+                          uint32_t *d_step_copy, uint8_t *d_join, uint64_t *d_contig_items, uint64_t *n_out_steps, uint64_t *n_merged,
+                          uint64_t *n_dropped, uint64_t *n_conflicts);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

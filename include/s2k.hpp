@@ -312,6 +312,45 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return t;
     }
+    // s2k_unitig_copy_places: where the forward strand of every copy of an untangled graph lies on the oriented contigs (`outer`: uni_off,
+    // members and circular of graph_unitigs over the n_copies copies; outer.capacity = their number), through d_origin and the uni_off and
+    // circular of the n_unitigs unitigs the copies were made of.  d_copy_place: n_copies records, 16-byte aligned.
+    void unitig_copy_places(const s2k_unitig_out &outer, uint64_t n_copies, const uint32_t *d_origin, const uint64_t *d_uni_off,
+                            const uint8_t *d_circular, uint64_t n_unitigs, s2k_node_place *d_copy_place) {
+        s2k_status st = s2k_unitig_copy_places(ctx_, outer.uni_off, outer.members, outer.circular, outer.capacity, n_copies, d_origin, d_uni_off,
+                                               d_circular, n_unitigs, d_copy_place);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+    }
+    // s2k_paths_lift: one batch's paths on the old unitig graph carried onto the contigs of its untangling (d_resolved, d_partner as
+    // graph_untangle took them, d_copy_off as it wrote it, d_copy_place of unitig_copy_places).  out.path_off is required; the step
+    // arrays of `out` and d_matched all nullptr: the sizes only.  d_step_copy and d_join: one entry per input step; d_contig_items:
+    // n_contigs sums that accumulate.  Throws on S2K_ERR_CAPACITY too (nothing written).
+    struct LiftGraph {
+        const uint64_t *row_off;
+        const uint32_t *dst;
+        uint64_t n_edges;
+        const uint64_t *uni_off;
+        const uint8_t *circular;
+        uint64_t n_unitigs;
+        const uint8_t *resolved;
+        const uint32_t *partner;
+        const uint64_t *copy_off;
+        const s2k_node_place *copy_place;
+        uint64_t n_copies, n_contigs;
+    };
+    struct LiftTotals {
+        uint64_t steps, merged, dropped, conflicts;
+    };
+    LiftTotals paths_lift(uint64_t n_reads, const s2k_thread_out &paths, uint64_t n_steps, const LiftGraph &g, const s2k_thread_out &out,
+                          const uint32_t *d_matched_in = nullptr, uint32_t *d_matched = nullptr, uint32_t *d_step_copy = nullptr,
+                          uint8_t *d_join = nullptr, uint64_t *d_contig_items = nullptr) {
+        LiftTotals t{};
+        s2k_status st = s2k_paths_lift(ctx_, n_reads, &paths, n_steps, d_matched_in, g.row_off, g.dst, g.n_edges, g.uni_off, g.circular, g.n_unitigs,
+                                       g.resolved, g.partner, g.copy_off, g.copy_place, g.n_copies, g.n_contigs, &out, d_matched, d_step_copy, d_join,
+                                       d_contig_items, &t.steps, &t.merged, &t.dropped, &t.conflicts);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "s2k_graph_untangle", "s2k_unitig_expand",
     "s2k_unitig_member_offsets", "s2k_paths_walks",
     "s2k_paths_bridge",
+    "s2k_unitig_copy_places", "s2k_paths_lift",
 ]
 
 
@@ -57,6 +58,7 @@ STEP_LINKED = 1  # s2k_thread_out.flags: the step's first item follows a solid i
 WALK_CIRCULAR = 1  # s2k_walk_out.flags: the walk lies on a circular unitig
 NO_EDGE = 0xFFFFFFFF  # s2k_walk_out.edge: the step follows no edge
 NO_PARTNER = 0xFFFFFFFF  # s2k_graph_resolve_mask: d_partner of an edge that enters no resolved unitig
+NO_COPY = 0xFFFFFFFF  # s2k_paths_lift: d_step_copy of a dropped step
 
 
 class S2kError(RuntimeError):
@@ -229,6 +231,12 @@ def load_library(path=None):
     L.s2k_paths_bridge.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ThreadOut), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ThreadOut), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_unitig_copy_places.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.c_void_p]
+    L.s2k_paths_lift.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ThreadOut), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ThreadOut),
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -859,6 +867,78 @@ class Engine:
         out.update(n_steps=m, n_merged=int(nm.value), n_bridged=int(nb.value))
         return out
 
+    def unitig_copy_places(self, outer, origin, uni_off, circular):
+        """Where every copy of an untangled graph lies on its contigs (s2k_unitig_copy_places; the definitions are in include/s2k.h):
+        outer = what graph_unitigs returned with the copies as its nodes, origin = graph_untangle's, uni_off / circular = the
+        decomposition the copies came from -> int32 GPU tensor of shape (n_copies, 4): row c is the NodePlace record (unitig, pos, len,
+        circular) of the forward oriented copy 2 c on the oriented contigs."""
+        import torch
+
+        oo, om, oc, origin = (x.contiguous() for x in (outer["uni_off"], outer["members"], outer["circular"], origin))
+        uni_off, circular = uni_off.contiguous(), circular.contiguous()
+        nt, ncp, t, dev = oc.numel(), origin.numel(), circular.numel(), uni_off.device
+        if (oo.numel() != nt + 1 or om.numel() != ncp or uni_off.numel() != t + 1 or oo.element_size() != 8 or uni_off.element_size() != 8
+                or om.element_size() != 4 or origin.element_size() != 4 or oc.element_size() != 1 or circular.element_size() != 1):
+            raise ValueError("unitig_copy_places wants the outer decomposition over the copies, one 32-bit origin per copy, and the inner uni_off and circular")
+        place = torch.empty((max(ncp, 1), 4), dtype=torch.int32, device=dev)
+        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_unitig_copy_places(self.ctx, p(oo), p(om, ncp), p(oc, nt), nt, ncp, p(origin, ncp), p(uni_off), p(circular, t), t, p(place)))
+        return place[:ncp]
+
+    def paths_lift(self, unitig_graph, paths, resolved, partner, copy_off, copy_place, n_contigs, contig_items=None, step_copy=False, join=False):
+        """One batch's ReadPaths on a UnitigGraph lifted onto the contigs of its untangling (s2k_paths_lift; the definitions are in
+        include/s2k.h).  resolved, partner: what graph_untangle took; copy_off: what it returned; copy_place: unitig_copy_places' tensor;
+        contig_items: an int64 GPU tensor of n_contigs entries (zeroed by the caller) that gains the items every contig carries.  Two
+        calls: the sizes, then the arrays.  -> dict of GPU tensors path_off (int64, n_reads + 1), unitig, pos, count, item, flags,
+        matched (int32; start, end only when the paths carry them), step_copy (int32 per input step, -1 = NO_COPY: dropped; only with
+        step_copy=True), join (uint8 per input step; only with join=True), and the ints n_steps, n_merged, n_dropped, n_conflicts."""
+        import torch
+
+        ug, dev = unitig_graph, paths.path_off.device
+        t, ne, ns, nr, ncp = ug.n_unitigs, ug.dst.numel(), paths.n_steps, paths.path_off.numel() - 1, copy_place.shape[0]
+        row_off, dst, uni_off, circular = (x.contiguous() for x in (ug.row_off, ug.dst, ug.uni_off, ug.circular))
+        resolved, partner, copy_off, copy_place = (x.contiguous() for x in (resolved, partner, copy_off, copy_place))
+        if (row_off.numel() != 2 * t + 1 or row_off.element_size() != 8 or dst.element_size() != 4 or uni_off.numel() != t + 1 or uni_off.element_size() != 8
+                or circular.element_size() != 1 or resolved.numel() != t or resolved.element_size() != 1 or partner.numel() != ne
+                or partner.element_size() != 4 or copy_off.numel() != t + 1 or copy_off.element_size() != 8 or copy_place.element_size() != 4
+                or copy_place.numel() != 4 * ncp):
+            raise ValueError("paths_lift wants a UnitigGraph, one resolved byte per unitig, one 32-bit partner per edge, copy_off (n_unitigs + 1, 64-bit) "
+                             "and the (n_copies, 4) records of unitig_copy_places")
+        if contig_items is not None and (contig_items.numel() != n_contigs or contig_items.element_size() != 8 or not contig_items.is_contiguous()):
+            raise ValueError("contig_items holds one 64-bit entry per contig")
+        i = ThreadOut()
+        i.capacity = ns
+        keep = {f: getattr(paths, f).contiguous() for f in ("path_off",) + ReadPaths.STEP_FIELDS if getattr(paths, f) is not None}
+        for f, x in keep.items():
+            setattr(i, f, x.data_ptr() if x.numel() else 0)
+        matched_in = paths.matched.contiguous() if paths.matched is not None else None
+        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k and x is not None else 0)  # noqa: E731
+        args = (self.ctx, nr, C.byref(i), ns, p(matched_in, ns), p(row_off), p(dst, ne), ne, p(uni_off), p(circular, t), t, p(resolved, t), p(partner, ne),
+                p(copy_off), p(copy_place, ncp), ncp, int(n_contigs))
+        res = {"path_off": torch.zeros(nr + 1, dtype=torch.int64, device=dev)}
+        o = ThreadOut()
+        o.path_off = res["path_off"].data_ptr()
+        tot = [C.c_uint64(0) for _ in range(4)]
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_paths_lift(*args, C.byref(o), None, None, None, None, *(C.byref(x) for x in tot)))
+        m = int(tot[0].value)
+        for f in [f for f in ReadPaths.STEP_FIELDS if f in keep] + ["matched"]:
+            res[f] = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+            if f != "matched":
+                setattr(o, f, res[f].data_ptr())
+        if step_copy:
+            res["step_copy"] = torch.empty(max(ns, 1), dtype=torch.int32, device=dev)
+        if join:
+            res["join"] = torch.empty(max(ns, 1), dtype=torch.uint8, device=dev)
+        o.capacity = m
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_paths_lift(*args, C.byref(o), p(res["matched"]), p(res.get("step_copy")), p(res.get("join")),
+                                            p(contig_items, n_contigs), *(C.byref(x) for x in tot)))
+        out = {f: (x if f == "path_off" else x[:ns] if f in ("join", "step_copy") else x[:m]) for f, x in res.items()}
+        out.update(n_steps=m, n_merged=int(tot[1].value), n_dropped=int(tot[2].value), n_conflicts=int(tot[3].value))
+        return out
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -1354,8 +1434,15 @@ class UnitigGraph:
         duplicated unitig has one instance per copy), counts = the summed copy counts, edge counts gathered from self's; node_origin, an
         int32 GPU tensor with the old node of every instance -- contigs.sequences(engine, node_seqs.take(node_origin)), write_gfa and
         write_fasta then work as they are; stats = {"copies", "duplicated", "contigs"}.  self is untouched.
-        One round only: the contigs' own repeats would need the reads threaded through them, and a count table keyed by hash cannot
-        hold two instances of one k-min-mer."""
+        One round; untangle_map returns the same three and the ContigLift that carries read paths onto the contigs, so that a second
+        round can be made by hand on the lifted paths (contigs.span_table, resolve, untangle_map, lift).  There is no driver that loops."""
+        return self.untangle_map(engine, resolved, partner)[:3]
+
+    def untangle_map(self, engine, resolved, partner):
+        """untangle, and the map of the old graph onto the contigs -> (contigs, node_origin, stats, lift): the first three are exactly
+        what untangle returns; lift is a ContigLift: lift.lift(engine, paths) carries the ReadPaths threaded through self (plain or
+        bridged) onto the contigs (Engine.unitig_copy_places, Engine.paths_lift), which a count table keyed by hash cannot do: a
+        duplicated k-min-mer has two instances, and only the edges a read used tell them apart."""
         import torch
 
         u = engine.graph_untangle(self, resolved, partner)
@@ -1373,7 +1460,9 @@ class UnitigGraph:
         counts = csum[o["uni_off"][1:]] - csum[o["uni_off"][:-1]]
         contigs = UnitigGraph(x["uni_off"], x["members"], x["node_unitig"], x["node_pos"], x["circular"], counts, ek, ec, c_row_off, c_dst, o["n_links"])
         contigs.n_nodes = x["n_members"]
-        return contigs, x["node_origin"], {"copies": tc, "duplicated": u["n_duplicated"], "contigs": o["n_unitigs"]}
+        place = engine.unitig_copy_places(o, u["origin"], self.uni_off, self.circular)
+        lift = ContigLift(self, resolved, partner, u["copy_off"], place, tc, o["n_unitigs"])
+        return contigs, x["node_origin"], {"copies": tc, "duplicated": u["n_duplicated"], "contigs": o["n_unitigs"]}, lift
 
     def bridge(self, engine, paths, max_gap=16, max_slip=2):
         """One batch's ReadPaths with the gaps that read errors cut into them bridged along this graph (Engine.paths_bridge;
@@ -1419,12 +1508,35 @@ class UnitigGraph:
                          self.edge_keys.cpu().numpy().view(np.uint64), self.edge_counts.cpu().numpy().view(np.uint32), members=members, sequences=seq)
 
 
+class ContigLift:
+    """The map of a UnitigGraph onto the contigs of one round of untangling (UnitigGraph.untangle_map): graph, the old graph; resolved
+    and partner, what was untangled; copy_off (int64, n_unitigs + 1), the copies of every unitig; copy_place (int32, (n_copies, 4)), the
+    NodePlace record of every copy on the oriented contigs; n_copies, n_contigs."""
+
+    def __init__(self, graph, resolved, partner, copy_off, copy_place, n_copies, n_contigs):
+        self.graph, self.resolved, self.partner, self.copy_off, self.copy_place = graph, resolved, partner, copy_off, copy_place
+        self.n_copies, self.n_contigs = n_copies, n_contigs
+
+    def lift(self, engine, paths, contig_items=None):
+        """One batch's ReadPaths on the old graph carried onto the contigs (Engine.paths_lift; include/s2k.h: s2k_paths_lift) ->
+        (ReadPaths, stats).  A step on a duplicated unitig goes to the copy whose matched pair of edges the read used; steps that the
+        compaction put side by side on one contig become one step; a step on a duplicated unitig that the read neither enters nor
+        leaves over an edge cannot be placed and is dropped.  The returned paths carry matched (the k-min-mers really found: the
+        paths' own matched summed, or their counts) and go into contigs.spans, contigs.walks(engine, lifted,
+        node_seqs.take(node_origin)), write_gaf and write_paths as they are.  contig_items: an int64 GPU tensor of n_contigs zeros that
+        gains the items every contig carries, batch after batch.  stats = {"steps_in", "steps_out", "merged", "dropped", "conflicts"};
+        conflicts counts the steps whose read left a duplicated unitig by another edge than the one matched to the edge it came by."""
+        b = engine.paths_lift(self.graph, paths, self.resolved, self.partner, self.copy_off, self.copy_place, self.n_contigs, contig_items=contig_items)
+        stats = {"steps_in": paths.n_steps, "steps_out": b["n_steps"], "merged": b["n_merged"], "dropped": b["n_dropped"], "conflicts": b["n_conflicts"]}
+        return ReadPaths(b["path_off"], **{f: b[f] for f in ReadPaths.STEP_FIELDS + ("matched",) if f in b}), stats
+
+
 class ReadPaths:
     """The paths of one batch of reads (UnitigGraph.thread; include/s2k.h: s2k_table_thread): the steps of read r are path_off[r] ..
     path_off[r + 1]; step s runs along the oriented unitig unitig[s] (2 t + strand) from position pos[s] over count[s] items, its first
     item is item[s] of the read, flags[s] & STEP_LINKED tells that the read entered it over a graph adjacency (not a gap), start[s] /
     end[s] (None when the extraction kept none) are the read's bases it covers.  matched[s] (None but on the paths
-    UnitigGraph.bridge returned) is the k-min-mers really found in a step whose count, after bridging, is the positions it covers.
+    UnitigGraph.bridge and ContigLift.lift returned) is the k-min-mers really found in a step whose count, after bridging, is the positions it covers.
     GPU tensors: path_off int64, the rest int32 holding the uint32 values."""
 
     STEP_FIELDS = ("unitig", "pos", "count", "item", "flags", "start", "end")
