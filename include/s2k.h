@@ -824,6 +824,53 @@ s2k_status s2k_paths_lift(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *
                           const s2k_node_place *d_copy_place, uint64_t n_copies, uint64_t n_contigs, const s2k_thread_out *out, uint32_t *d_matched,
                           uint32_t *d_step_copy, uint8_t *d_join, uint64_t *d_contig_items, uint64_t *n_out_steps, uint64_t *n_merged,
                           uint64_t *n_dropped, uint64_t *n_conflicts);
+/* ---- majority-vote representatives: every node takes its best-supported occurrence ---------------------------------
+ * The sequence calls above take the bytes of a node's earliest occurrence.  These calls choose another ordinal for d_rep: the
+ * occurrence that reads like most of the others.  No alignment, no new record format: s2k_table_node_sequences, the stitch and
+ * everything after them take the voted d_rep as they take the earliest one.  Inputs per batch as for s2k_table_node_sequences.
+ * Readings.  An occurrence x of node i (an item whose hash is key i, whatever its count) with bytes B, rev, shift_fwd and shift_rev
+ * as defined above has three readings, each with a tag:
+ *   whole:        B if rev == 0, else revcomp(B)                                             tag 4 i
+ *   forward end:  B[:shift_fwd], what the stitch takes from the oriented node 2 i + rev      tag 4 i + 2 + rev
+ *   reverse end:  revcomp(B[len - shift_rev:]), what it takes from 2 i + (1 - rev)           tag 4 i + 2 + (1 - rev)
+ * Fingerprint of a byte string s of length n: F(s) = sum over j of (s_j + 1) * M^(n - 1 - j) mod 2^64, M = 0x9E3779B97F4A7C15 (the
+ * Horner loop F = F * M + s_j + 1 from F = 0; the empty string has F = 0).  F(a || b) = F(a) * M^|b| + F(b).
+ * Vote key of a reading s with tag g: mix64(F(s) ^ mix64(g)), mix64 the splitmix64 finaliser: z = (z ^ (z >> 30)) *
+ * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31).  (Mixed so that a count's radix partition sees
+ * uniform top bits even for a graph of a few hundred nodes.)
+ * votes(key) = the number of occurrences, over all batches, that gave that key, those of nodes that are not solid included.  The
+ * score of x is the pair (votes(whole), votes(forward end) + votes(reverse end)), compared lexicographically; the voted representative
+ * of node i is its occurrence with the largest score, the smallest global ordinal among equals.  In the packed word below the first
+ * number saturates at 2047 and the second at 4095.  A fingerprint collision only adds a vote to another reading.  With error-free
+ * reads all occurrences of a node read the same unless two k-min-mers share its hash, so the voted representative is the earliest.
+ * Protocol: s2k_table_vote_keys per batch into a counter (s2k_counter_add); s2k_counter_finish with min_count 1 and s2k_table_create
+ * give the vote table; s2k_table_vote_representatives per batch with the same ordinal_base rule as s2k_table_representatives;
+ * s2k_vote_ordinals once.
+ *
+ * s2k_table_vote_keys: d_keys = the three vote keys (whole, forward end, reverse end) of every item of the batch whose hash is in the
+ * table, in item order.  *n_keys is always set; d_keys NULL asks for the size only (d_bases may then be NULL); *n_keys > capacity is
+ * S2K_ERR_CAPACITY and nothing is written.  Checked on the device before anything is written, S2K_ERR_INVALID_ARG otherwise: what
+ * s2k_table_node_sequences checks, but for every item of the table, not only the representatives: km_off[0] == mn_off[0] == 0,
+ * km_off / mn_off / read_off do not decrease, mn_capacity covers mn_off[n_reads], every read with n > 0 items has n + k - 1 triples,
+ * every position an item uses lies inside its read and in order.  k < 2 is refused.  Every base of the batch is read twice (once
+ * per pass of the two-pass fingerprint scan, both orientations from the same registers) whatever k is, and an item reads at most 15
+ * more bytes at each of its five positions; no lane walks a node's bytes.  Workspace (the context's grow-only count workspace): 4.2 B
+ * per item and 1 B per base.  Keys come from ballots and scans: bit-identical from call to call.  Runs on the context's stream;
+ * returns when the outputs are written. */
+s2k_status s2k_table_vote_keys(s2k_table *t, uint64_t n_reads, const s2k_device_out *in, uint32_t k, const uint8_t *d_bases,
+                               const uint64_t *d_read_off, uint64_t *d_keys, uint64_t capacity, uint64_t *n_keys);
+/* d_best[i] = max(d_best[i], w << 52 | e << 40 | (2^40 - 1 - (ordinal_base + x))) over the items x of the batch whose hash is key i of
+ * `t`, w = min(votes(whole), 2047), e = min(votes(forward end) + votes(reverse end), 4095), the votes looked up in vote_table (its
+ * counts; a table without counts gives 1).  d_best (one uint64_t per key of t) is the caller's: zeroed before the first batch,
+ * carried from batch to batch; a 0 left at the end means no occurrence (every occurrence has w >= 1).  One 64-bit atomicMax per
+ * item, the only atomic on an output; max does not depend on the order, so d_best is a function of the input.  The checks of
+ * s2k_table_vote_keys apply; ordinal_base + the batch's items > 2^40 is refused on the host; a key that vote_table lacks (it is not
+ * the table counted from these batches) is S2K_ERR_INVALID_ARG, found on the device before anything is written.  Workspace: 12.2 B
+ * per item and 1 B per base.  Runs on t's context's stream; returns when d_best is written. */
+s2k_status s2k_table_vote_representatives(s2k_table *t, s2k_table *vote_table, uint64_t n_reads, const s2k_device_out *in, uint32_t k,
+                                          const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t ordinal_base, uint64_t *d_best);
+/* d_rep[i] = 2^40 - 1 - (d_best[i] & (2^40 - 1)), or all ones where d_best[i] == 0: the d_rep that s2k_table_node_sequences takes. */
+s2k_status s2k_vote_ordinals(s2k_ctx *ctx, const uint64_t *d_best, uint64_t n, uint64_t *d_rep);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

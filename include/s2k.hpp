@@ -351,6 +351,11 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return t;
     }
+    // s2k_vote_ordinals: d_rep[i] = the ordinal packed into d_best[i] (Table::vote_representatives), all ones where d_best[i] == 0
+    void vote_ordinals(const uint64_t *d_best, uint64_t n, uint64_t *d_rep) {
+        s2k_status st = s2k_vote_ordinals(ctx_, d_best, n, d_rep);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:
@@ -424,6 +429,21 @@ class Table {
         uint64_t n_bytes = 0;
         check(s2k_table_node_sequences(t_, n_reads, &in, k, d_bases, d_read_off, ordinal_base, d_rep, nodes, pool_used, &n_bytes));
         return n_bytes;
+    }
+    // s2k_table_vote_keys: the three vote keys (whole, forward end, reverse end) of every item of the batch whose hash is in the table,
+    // in item order, for a Counter; d_keys nullptr: the size only.  Returns the number of keys (throws on S2K_ERR_CAPACITY too).
+    uint64_t vote_keys(uint64_t n_reads, const s2k_device_out &in, uint32_t k, const uint8_t *d_bases, const uint64_t *d_read_off,
+                       uint64_t *d_keys = nullptr, uint64_t capacity = 0) {
+        uint64_t n_keys = 0;
+        check(s2k_table_vote_keys(t_, n_reads, &in, k, d_bases, d_read_off, d_keys, capacity, &n_keys));
+        return n_keys;
+    }
+    // s2k_table_vote_representatives: d_best[i] = max(d_best[i], votes and ordinal of item x) over the batch's items x whose hash is
+    // key i, the votes from `votes`, the table over the counted vote keys of every batch (d_best: one uint64_t per key, zeroed before
+    // the first batch; Engine::vote_ordinals turns it into the d_rep of node_sequences)
+    void vote_representatives(Table &votes, uint64_t n_reads, const s2k_device_out &in, uint32_t k, const uint8_t *d_bases,
+                              const uint64_t *d_read_off, uint64_t ordinal_base, uint64_t *d_best) {
+        check(s2k_table_vote_representatives(t_, votes.t_, n_reads, &in, k, d_bases, d_read_off, ordinal_base, d_best));
     }
     // s2k_table_thread: each read's path through the unitigs whose node places are d_place (Engine::unitig_node_places; n_nodes = the
     // table's keys): out.path_off always, the step arrays of `out` when they fit (all nullptr: the sizes only); d_uni_items (may be

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "s2k_unitig_member_offsets", "s2k_paths_walks",
     "s2k_paths_bridge",
     "s2k_unitig_copy_places", "s2k_paths_lift",
+    "s2k_table_vote_keys", "s2k_table_vote_representatives", "s2k_vote_ordinals",
 ]
 
 
@@ -237,6 +238,11 @@ def load_library(path=None):
                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ThreadOut),
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64)]
+    L.s2k_table_vote_keys.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.POINTER(C.c_uint64)]
+    L.s2k_table_vote_representatives.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_void_p,
+                                                 C.c_uint64, C.c_void_p]
+    L.s2k_vote_ordinals.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -627,6 +633,53 @@ class Engine:
             torch.cuda.synchronize(dev)
             self._check(self.lib.s2k_unitig_sequences(*args, C.c_void_p(out.data_ptr()), C.c_void_p(overlap.data_ptr()), total, C.byref(nb)))
         return out_off, out[:total], overlap[:2 * t]
+
+    def table_vote_keys(self, table, o, k):
+        """The vote keys of one batch (s2k_table_vote_keys; the rule is in include/s2k.h): o = the GPU tensors extract_device wrote with
+        FLAG_WANT_MINIMIZERS plus the batch's `bases` and `read_off`; table: the CountTable of the nodes.  Two calls: the size, then the
+        keys.  -> int64 GPU tensor, three keys (whole, forward end, reverse end) per item of the table, in item order."""
+        import torch
+
+        nr = o["km_off"].numel() - 1
+        i, nk = _seq_in(o, nr), C.c_uint64(0)
+        b, ro = o["bases"], o["read_off"]
+        args = (table.handle, nr, C.byref(i), int(k), C.c_void_p(b.data_ptr() if b.numel() else 0), C.c_void_p(ro.data_ptr()))
+        torch.cuda.synchronize(ro.device)
+        self._check(self.lib.s2k_table_vote_keys(*args, None, 0, C.byref(nk)))
+        n = int(nk.value)
+        keys = torch.empty(max(n, 1), dtype=torch.int64, device=ro.device)
+        if n:
+            torch.cuda.synchronize(ro.device)
+            self._check(self.lib.s2k_table_vote_keys(*args, C.c_void_p(keys.data_ptr()), n, C.byref(nk)))
+        return keys[:n]
+
+    def table_vote_representatives(self, table, vote_table, o, k, ordinal_base, best):
+        """best[i] = max(best[i], votes and ordinal of x) over the batch's items x whose hash is key i of `table`
+        (s2k_table_vote_representatives); vote_table: the CountTable over the counted vote keys of every batch; best: int64 GPU tensor,
+        one entry per key, zeroed before the first batch.  -> the batch's items, to add to ordinal_base."""
+        import torch
+
+        nr = o["km_off"].numel() - 1
+        i = _seq_in(o, nr)
+        b, ro = o["bases"], o["read_off"]
+        if best.numel() < table.n or best.element_size() != 8 or not best.is_contiguous():
+            raise ValueError("best holds one 64-bit entry per key of the table")
+        torch.cuda.synchronize(ro.device)
+        self._check(self.lib.s2k_table_vote_representatives(table.handle, vote_table.handle, nr, C.byref(i), int(k),
+                                                            C.c_void_p(b.data_ptr() if b.numel() else 0), C.c_void_p(ro.data_ptr()), int(ordinal_base),
+                                                            C.c_void_p(best.data_ptr() if table.n else 0)))
+        return i.km_capacity
+
+    def vote_ordinals(self, best):
+        """-> int64 GPU tensor rep: the ordinal packed into every best[i], all ones where best[i] == 0 (s2k_vote_ordinals): the rep that
+        s2k_table_node_sequences takes"""
+        import torch
+
+        best = best.contiguous()
+        rep = torch.empty(max(best.numel(), 1), dtype=torch.int64, device=best.device)
+        torch.cuda.synchronize(best.device)
+        self._check(self.lib.s2k_vote_ordinals(self.ctx, C.c_void_p(best.data_ptr() if best.numel() else 0), best.numel(), C.c_void_p(rep.data_ptr())))
+        return rep[:best.numel()]
 
     def unitig_node_places(self, uni_off, members, node_unitig, node_pos, circular):
         """Where every node lies on the oriented unitigs (s2k_unitig_node_places), from the arrays graph_unitigs returned -> int32 GPU
@@ -1186,12 +1239,38 @@ class NodeSequences:
         old = node_origin.long()
         return type(self)(*(getattr(self, f)[old] for f in ("rep",) + self.FIELDS), self.pool, self.n_bytes, self.k)
 
+    @staticmethod
+    def _voted(engine, table, outs, k, dev):
+        """the voted ordinals of every key of `table` over the batches `outs`: keys -> counter -> vote table -> best -> ordinals"""
+        import torch
+
+        counter = KminmerCounter(engine)
+        try:
+            for o in outs:
+                counter.add_tensor(engine.table_vote_keys(table, o, k))
+            vkeys, vcounts = counter.finish(1)
+        finally:
+            counter.close()
+        votes = CountTable(engine, vkeys, vcounts)
+        try:
+            best = torch.zeros(max(table.n, 1), dtype=torch.int64, device=dev)
+            base = 0
+            for o in outs:
+                base += engine.table_vote_representatives(table, votes, o, k, base, best)
+        finally:
+            votes.close()
+        rep = engine.vote_ordinals(best)
+        return rep if table.n else torch.full((1,), -1, dtype=torch.int64, device=dev)
+
     @classmethod
-    def build(cls, engine, table_or_graph, outs, k=None):
+    def build(cls, engine, table_or_graph, outs, k=None, vote=False):
         """outs: per batch the GPU tensors extract_device wrote with FLAG_WANT_MINIMIZERS (km_off, hash, rev, mn_off, mn_j, mn_jend) plus
         the batch's `bases` and `read_off`, in the order the graph was built from; table_or_graph: the CountTable of the nodes, or a
         KminmerGraph (a table over its keys lives for this call).  k (the k-min-mer order) is taken from the first read with items
-        when not given; the device checks it against every read.  Three rounds over the batches: representatives, sizes, records."""
+        when not given; the device checks it against every read.  Three rounds over the batches: representatives, sizes, records.
+        vote=True chooses every node's best-supported occurrence instead of its earliest: the batches' vote keys are
+        counted (a KminmerCounter and the table over its result live for this call), every batch's items are scored against them, and
+        rep holds the voted ordinals; the two record rounds are the same."""
         import torch
 
         own = isinstance(table_or_graph, KminmerGraph)
@@ -1212,12 +1291,15 @@ class NodeSequences:
                 ins.append((i, nr))
                 bases.append((o["bases"], o["read_off"]))
             k = 2 if k is None else int(k)
-            rep = torch.full((max(n_keys, 1),), -1, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize(dev)
-            base = 0
-            for i, nr in ins:
-                engine._check(engine.lib.s2k_table_representatives(table.handle, nr, C.byref(i), base, C.c_void_p(rep.data_ptr())))
-                base += i.km_capacity
+            if vote:
+                rep = cls._voted(engine, table, outs, k, dev)
+            else:
+                rep = torch.full((max(n_keys, 1),), -1, dtype=torch.int64, device=dev)
+                torch.cuda.synchronize(dev)
+                base = 0
+                for i, nr in ins:
+                    engine._check(engine.lib.s2k_table_representatives(table.handle, nr, C.byref(i), base, C.c_void_p(rep.data_ptr())))
+                    base += i.km_capacity
 
             def round_(ns):
                 base, used = 0, 0
