@@ -674,7 +674,8 @@ s2k_status s2k_unitig_expand(s2k_ctx *ctx, const uint64_t *d_outer_off, const ui
  * len) * L + the unraised hi of (U, last % len), i.e. path_start + the stitched length of its items; it may exceed path_len = L.
  * Elsewhere path_start <= path_end <= path_len.  The stitched path of a walk is the unitig sequences on the walk's strands, each after
  * the first without the overlap[U] bases of the one before it; on error-free reads read[qstart, qend) equals its bases [path_start,
- * path_end).  This is exact arithmetic on records, not an alignment: there is no CIGAR. */
+ * path_end).  This is exact arithmetic on records, not an alignment: there is no CIGAR (s2k_walks_targets and s2k_align_pairs, below,
+ * align a walk to its path). */
 s2k_status s2k_unitig_member_offsets(s2k_ctx *ctx, const uint64_t *d_uni_off, const uint32_t *d_members, const uint8_t *d_circular,
                                      uint64_t n_unitigs, uint64_t n_nodes, const s2k_node_seqs *nodes, uint64_t *d_member_off,
                                      uint64_t *d_out_off, uint32_t *d_overlap, uint64_t *n_bases);
@@ -871,6 +872,80 @@ s2k_status s2k_table_vote_representatives(s2k_table *t, s2k_table *vote_table, u
                                           const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t ordinal_base, uint64_t *d_best);
 /* d_rep[i] = 2^40 - 1 - (d_best[i] & (2^40 - 1)), or all ones where d_best[i] == 0: the d_rep that s2k_table_node_sequences takes. */
 s2k_status s2k_vote_ordinals(s2k_ctx *ctx, const uint64_t *d_best, uint64_t n, uint64_t *d_rep);
+/* ---- read walks aligned to their paths: targets, edit distance and CIGAR ----------------------------------------------
+ * Targets.  Inputs: the walk records first_step, n_steps, path_start, path_end and flags that s2k_paths_walks wrote (n_walks of each),
+ * the oriented unitig of every step of the paths (d_step_unitig, n_steps entries), and d_out_off, d_out (n_bases bytes) and d_overlap of
+ * s2k_unitig_sequences over n_unitigs unitigs.  Step j of a walk runs on U_j = step_unitig[first_step + j]; its string s_j is the
+ * unitig's bases for an even U_j and revcomp of them (above) for an odd one, L_j its length.  The stitched path is s_0 followed by
+ * s_j[overlap[U_(j-1)]:] for j = 1 .. n_steps - 1; target w is its bytes [path_start, path_end).  For a walk with S2K_WALK_CIRCULAR
+ * (one step) byte x of the target is s_0[x mod L_0]: path_end may pass L_0, more than once.
+ * A walk is bad, which is no error of the call, when a junction has overlap[U_(j-1)] > min(L_(j-1), L_j) (representatives of
+ * erroneous reads can give one), when it is circular with L_0 == 0 or without a step, when path_start > path_end, or when it is not
+ * circular and path_end passes the stitched length.  A bad walk has d_bad[w] = 1 and an empty target; every other walk d_bad[w] = 0.
+ * d_tgt_off (n_walks + 1 entries, may be NULL): tgt_off[w + 1] - tgt_off[w] = path_end - path_start, 0 for a bad walk; d_bad (n_walks
+ * bytes, may be NULL); d_tgt (may be NULL: the sizes only; 16-byte aligned, stores are 16 bytes wide) the bytes; *n_bytes is always
+ * set.  *n_bytes > capacity with d_tgt given is S2K_ERR_CAPACITY and nothing at all is written.  Checked on the device before
+ * anything is written, one flag word read by the host, S2K_ERR_INVALID_ARG otherwise: every walk's steps lie inside the n_steps steps;
+ * every step's unitig < 2 n_unitigs; out_off does not decrease and ends inside n_bases; no unitig of 2^32 bases or more; no target of
+ * 2^32 bytes or more.  n_unitigs >= 2^31 is refused.  d_out is read in aligned 8-byte words (it must be 8-byte aligned and its
+ * allocation whole words, as the node pool); the contents of d_overlap are only compared.  Lengths by one lane per walk from two
+ * scans over the steps, a scan over the lengths, then an output-ordered copy: consecutive lanes take consecutive 16 bytes, the step
+ * of a byte is found by a search of the walk's per-step prefix, a twin strand is complemented in registers.  No atomic on an output:
+ * every output is a function of the input.  Workspace (the context's grow-only count workspace): 24 B per step and 13 B per walk.
+ * Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_walks_targets(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_first_step, const uint32_t *d_n_steps, const uint64_t *d_path_start,
+                             const uint64_t *d_path_end, const uint32_t *d_flags, const uint32_t *d_step_unitig, uint64_t n_steps,
+                             const uint64_t *d_out_off, const uint8_t *d_out, uint64_t n_bases, const uint32_t *d_overlap, uint64_t n_unitigs,
+                             uint64_t *d_tgt_off, uint8_t *d_tgt, uint8_t *d_bad, uint64_t capacity, uint64_t *n_bytes);
+/* Pairs.  Pair i aligns q = d_query[q_begin[i], q_end[i]) with t = d_target[t_begin[i], t_end[i]) (absolute in their pools of
+ * n_query_bytes and n_target_bytes), globally, at unit costs: a mismatch 1, an inserted or deleted base 1.  Bytes are compared as they
+ * are: no case folding, N == N.  No load touches a byte outside a pool.
+ * The rule, on furthest-reaching points.  m = |q|, n = |t|; diagonal k = j - i for i bases of q and j of t consumed; ext(i, k) = i
+ * advanced while i < m, i + k < n and q[i] == t[i + k].  H[0][0] = ext(0, 0).  For s >= 1 and -s <= k <= s the candidates are H[s-1][k]
+ * + 1 (X), H[s-1][k+1] + 1 (I: a query base without a target base) and H[s-1][k-1] (D: a target base without a query base), each only
+ * where its source exists, and kept only if i <= m and 0 <= i + k <= n; without a candidate H[s][k] does not exist, otherwise v = the
+ * largest candidate and H[s][k] = ext(v, k).  edits = the smallest s with H[s][n - m] == m.
+ * Traceback from (s = edits, k = n - m, i = m): v = v of (s, k) (0 at s == 0); emit i - v bases of '='; i = v; stop at s == 0;
+ * otherwise take the first predecessor that gives v -- X if H[s-1][k] + 1 == v: i -= 1; I if H[s-1][k+1] + 1 == v: i -= 1, k += 1; D
+ * (H[s-1][k-1] == v): k -= 1 -- and s -= 1.  The result reversed, equal neighbours merged into runs: at most 2 edits + 1 runs.
+ * Outputs per pair: edits; flags, bit 0 S2K_ALIGN_OVER = the distance exceeds max_edits (|n - m| > max_edits decides at once), then
+ * edits = max_edits + 1 and n_ops = matches = 0; ops_off (n_pairs + 1 entries) = the exclusive scan of 2 edits + 1 over the pairs
+ * that are not over and of 0 over those that are; n_ops; matches = the bases under '='; ops, one uint32_t per run, len << 4 | op with
+ * the BAM codes below: the CIGAR of pair i is ops[ops_off[i] .. ops_off[i] + n_ops[i]), the slots behind it are left untouched.
+ * A call with out NULL or without ops, n_ops and matches is the sizes call: it writes edits, flags and ops_off (those given) and
+ * *n_ops_bound = ops_off[n_pairs], which is always set.  A call with one of ops, n_ops, matches needs edits, flags and ops_off too (the
+ * second pass reads edits and ops_off back), and out->capacity, in runs: *n_ops_bound > capacity is S2K_ERR_CAPACITY and nothing at all is written.
+ * S2K_ERR_INVALID_ARG, nothing written (found on the device, one flag word read by the host): a begin above its end, an interval
+ * outside its pool, an interval of 2^31 bytes or more; on the host: max_edits > S2K_ALIGN_MAX_EDITS, n_pairs >= 2^32.  n_pairs == 0
+ * reads nothing.  S2K_ALIGN_BAD_PATH is never set here: it marks, in the flags a caller keeps per walk, a walk whose target
+ * s2k_walks_targets called bad.
+ * One wave per pair, lanes across the diagonals of a wavefront; a bounded grid of at most S2K_ALIGN_WAVES waves in which a wave takes
+ * the next pair off a counter in the workspace.  Two passes: the distances with two wavefronts in registers and no storage, then,
+ * ops_off known, the wavefronts again with every H kept, and the traceback, which recomputes v.  No atomic touches an output and which
+ * wave took a pair reaches none: two calls are bit-identical.  Workspace (the context's grow-only count workspace): 20 B per pair,
+ * then 4 (emax + 1)^2 B per wave in flight, emax = the largest distance of a pair that is not over (<= max_edits), over min(n_pairs,
+ * S2K_ALIGN_WAVES) waves, fewer (never below 4) where that would pass 256 MiB.  Runs on the context's stream; returns when the outputs
+ * are written. */
+#define S2K_ALIGN_OVER 1u
+#define S2K_ALIGN_BAD_PATH 2u
+#define S2K_ALIGN_MAX_EDITS 255u
+#define S2K_ALIGN_WAVES 2048u
+#define S2K_CIGAR_I 1u
+#define S2K_CIGAR_D 2u
+#define S2K_CIGAR_EQ 7u
+#define S2K_CIGAR_X 8u
+typedef struct s2k_align_out { /* device pointers, each may be NULL; capacity in runs */
+    uint64_t capacity;
+    uint32_t *edits;
+    uint32_t *flags;
+    uint64_t *ops_off; /* n_pairs + 1 */
+    uint32_t *n_ops;
+    uint32_t *matches;
+    uint32_t *ops;
+} s2k_align_out;
+s2k_status s2k_align_pairs(s2k_ctx *ctx, const uint8_t *d_query, uint64_t n_query_bytes, const uint8_t *d_target, uint64_t n_target_bytes,
+                           const uint64_t *d_q_begin, const uint64_t *d_q_end, const uint64_t *d_t_begin, const uint64_t *d_t_end, uint64_t n_pairs,
+                           uint32_t max_edits, const s2k_align_out *out, uint64_t *n_ops_bound);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

@@ -356,6 +356,32 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         s2k_status st = s2k_vote_ordinals(ctx_, d_best, n, d_rep);
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
     }
+    // s2k_walks_targets: the bases of every walk's path interval (`walks`: the record arrays s2k_paths_walks wrote, walks.capacity =
+    // n_walks; d_step_unitig: the paths' unitig per step).  d_tgt nullptr: the sizes only.  Returns the bytes of all targets; throws on
+    // S2K_ERR_CAPACITY too (nothing written).
+    uint64_t walks_targets(const s2k_walk_out &walks, const uint32_t *d_step_unitig, uint64_t n_steps, const uint64_t *d_out_off, const uint8_t *d_out,
+                           uint64_t n_bases, const uint32_t *d_overlap, uint64_t n_unitigs, uint64_t *d_tgt_off = nullptr, uint8_t *d_tgt = nullptr,
+                           uint8_t *d_bad = nullptr, uint64_t capacity = 0) {
+        uint64_t n_bytes = 0;
+        s2k_status st = s2k_walks_targets(ctx_, walks.capacity, walks.first_step, walks.n_steps, walks.path_start, walks.path_end, walks.flags, d_step_unitig,
+                                          n_steps, d_out_off, d_out, n_bases, d_overlap, n_unitigs, d_tgt_off, d_tgt, d_bad, capacity, &n_bytes);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_bytes;
+    }
+    // s2k_align_pairs: pair i aligns d_query[q_begin[i], q_end[i]) with d_target[t_begin[i], t_end[i]) at unit costs.  out nullptr or
+    // without ops, n_ops and matches: the sizes only.  Returns the run slots of all pairs; throws on S2K_ERR_CAPACITY too (nothing written).
+    struct Pool {
+        const uint8_t *bytes;
+        uint64_t n_bytes;
+        const uint64_t *begin, *end; // one interval per pair
+    };
+    uint64_t align_pairs(const Pool &query, const Pool &target, uint64_t n_pairs, uint32_t max_edits = S2K_ALIGN_MAX_EDITS, const s2k_align_out *out = nullptr) {
+        uint64_t n_ops_bound = 0;
+        s2k_status st = s2k_align_pairs(ctx_, query.bytes, query.n_bytes, target.bytes, target.n_bytes, query.begin, query.end, target.begin, target.end,
+                                        n_pairs, max_edits, out, &n_ops_bound);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_ops_bound;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

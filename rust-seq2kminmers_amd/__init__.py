@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "s2k_paths_bridge",
     "s2k_unitig_copy_places", "s2k_paths_lift",
     "s2k_table_vote_keys", "s2k_table_vote_representatives", "s2k_vote_ordinals",
+    "s2k_walks_targets", "s2k_align_pairs",
 ]
 
 
@@ -60,6 +61,12 @@ WALK_CIRCULAR = 1  # s2k_walk_out.flags: the walk lies on a circular unitig
 NO_EDGE = 0xFFFFFFFF  # s2k_walk_out.edge: the step follows no edge
 NO_PARTNER = 0xFFFFFFFF  # s2k_graph_resolve_mask: d_partner of an edge that enters no resolved unitig
 NO_COPY = 0xFFFFFFFF  # s2k_paths_lift: d_step_copy of a dropped step
+ALIGN_OVER = 1  # s2k_align_out.flags: the distance exceeds max_edits
+ALIGN_BAD_PATH = 2  # WalkAlignments.flags: s2k_walks_targets called the walk's path bad; it was not aligned
+ALIGN_MAX_EDITS = 255  # s2k_align_pairs: the largest max_edits
+ALIGN_WAVES = 2048  # s2k_align_pairs: the waves of its persistent grid
+CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # s2k_align_out.ops: len << 4 | op, the BAM codes
+CIGAR_CHARS = {CIGAR_I: "I", CIGAR_D: "D", CIGAR_EQ: "=", CIGAR_X: "X"}
 
 
 class S2kError(RuntimeError):
@@ -119,6 +126,11 @@ class WalkOut(C.Structure):
     _fields_ = [("capacity", C.c_uint64), ("walk_off", C.c_void_p), ("first_step", C.c_void_p), ("n_steps", C.c_void_p), ("items", C.c_void_p),
                 ("qstart", C.c_void_p), ("qend", C.c_void_p), ("path_len", C.c_void_p), ("path_start", C.c_void_p), ("path_end", C.c_void_p),
                 ("flags", C.c_void_p), ("edge", C.c_void_p)]
+
+
+class AlignOut(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("edits", C.c_void_p), ("flags", C.c_void_p), ("ops_off", C.c_void_p), ("n_ops", C.c_void_p),
+                ("matches", C.c_void_p), ("ops", C.c_void_p)]
 
 
 # s2k_node_place: where the forward oriented node 2 i lies on the oriented unitigs
@@ -243,6 +255,10 @@ def load_library(path=None):
     L.s2k_table_vote_representatives.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DeviceOut), C.c_uint32, C.c_void_p, C.c_void_p,
                                                  C.c_uint64, C.c_void_p]
     L.s2k_vote_ordinals.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.s2k_walks_targets.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                    C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.s2k_align_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.c_uint32, C.POINTER(AlignOut), C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -992,6 +1008,66 @@ class Engine:
         out.update(n_steps=m, n_merged=int(tot[1].value), n_dropped=int(tot[2].value), n_conflicts=int(tot[3].value))
         return out
 
+    def walks_targets(self, walks, step_unitig, out_off, out, overlap):
+        """The bases of every walk's path interval (s2k_walks_targets; the definitions are in include/s2k.h).  walks: a ReadWalks (or
+        anything with first_step, n_steps, path_start, path_end, flags); step_unitig: the oriented unitig of every step of its paths;
+        out_off, out: the pair UnitigGraph.sequences returned; overlap: the graph's.  Two calls: the sizes, then the bytes.  -> dict of
+        GPU tensors tgt_off (int64, n_walks + 1), tgt (uint8), bad (uint8 per walk), and the int n_bytes."""
+        import torch
+
+        rec = [getattr(walks, f).contiguous() for f in ("first_step", "n_steps", "path_start", "path_end", "flags")]
+        step_unitig, out_off, out, overlap = (x.contiguous() for x in (step_unitig, out_off, out, overlap))
+        nw, ns, t, dev = rec[0].numel(), step_unitig.numel(), out_off.numel() - 1, out_off.device
+        if (any(x.numel() != nw for x in rec) or [x.element_size() for x in rec] != [8, 4, 8, 8, 4] or step_unitig.element_size() != 4
+                or out_off.element_size() != 8 or out.element_size() != 1 or overlap.numel() != 2 * t or overlap.element_size() != 4):
+            raise ValueError("walks_targets wants the walk records, one 32-bit unitig per step, and the out_off, out and overlap of the unitig sequences")
+        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
+        args = (self.ctx, nw, *(p(x, nw) for x in rec), p(step_unitig, ns), ns, p(out_off), p(out, out.numel()), out.numel(), p(overlap, t), t)
+        tgt_off = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
+        bad = torch.zeros(max(nw, 1), dtype=torch.uint8, device=dev)
+        nb = C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_walks_targets(*args, None, None, None, 0, C.byref(nb)))
+        n = int(nb.value)
+        tgt = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_walks_targets(*args, p(tgt_off), p(tgt), p(bad), n, C.byref(nb)))
+        return {"tgt_off": tgt_off, "tgt": tgt[:n], "bad": bad[:nw], "n_bytes": n}
+
+    def align_pairs(self, query, target, q_begin, q_end, t_begin, t_end, max_edits=ALIGN_MAX_EDITS):
+        """Global unit-cost alignment of many pairs of byte intervals (s2k_align_pairs; the rule is in include/s2k.h): pair i aligns
+        query[q_begin[i] : q_end[i]] with target[t_begin[i] : t_end[i]] (uint8 GPU tensors; int64 GPU tensors of one length).  Two
+        calls: the sizes, then the runs.  -> dict of GPU tensors edits, flags, n_ops, matches (int32 per pair), ops_off (int64, n_pairs
+        + 1), ops (int32 per run: len << 4 | op; the CIGAR of pair i is ops[ops_off[i] : ops_off[i] + n_ops[i]]), and the int
+        n_ops_bound.  A pair whose distance exceeds max_edits has flags & ALIGN_OVER, edits = max_edits + 1 and no run."""
+        import torch
+
+        query, target = query.contiguous(), target.contiguous()
+        iv = [x.contiguous() for x in (q_begin, q_end, t_begin, t_end)]
+        n, dev = iv[0].numel(), query.device
+        if any(x.numel() != n or x.element_size() != 8 for x in iv) or query.element_size() != 1 or target.element_size() != 1:
+            raise ValueError("align_pairs wants two byte pools and four 64-bit interval arrays of one length")
+        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
+        args = (self.ctx, p(query, query.numel()), query.numel(), p(target, target.numel()), target.numel(), *(p(x, n) for x in iv), n, int(max_edits))
+        res = {f: torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for f in ("edits", "flags", "n_ops", "matches")}
+        res["ops_off"] = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        o = AlignOut()
+        for f in ("edits", "flags", "ops_off"):
+            setattr(o, f, res[f].data_ptr())
+        nb = C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_align_pairs(*args, C.byref(o), C.byref(nb)))
+        m = int(nb.value)
+        res["ops"] = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)
+        o.capacity = m
+        for f in ("n_ops", "matches", "ops"):
+            setattr(o, f, res[f].data_ptr())
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_align_pairs(*args, C.byref(o), C.byref(nb)))
+        out = {f: (x if f == "ops_off" else x[:m] if f == "ops" else x[:n]) for f, x in res.items()}
+        out["n_ops_bound"] = m
+        return out
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -1576,6 +1652,29 @@ class UnitigGraph:
         w = engine.paths_walks(self, paths, self.member_offsets(engine, node_seqs), node_seqs.seq_len)
         return ReadWalks(paths, **w)
 
+    def align(self, engine, walks, bases, read_off, sequences, max_edits=ALIGN_MAX_EDITS):
+        """Every walk's read bases aligned to its path interval on the device (Engine.walks_targets, Engine.align_pairs;
+        include/s2k.h) -> WalkAlignments.  walks: the ReadWalks self.walks returned (its paths must carry start and end); bases,
+        read_off: the batch's bases (uint8) and read offsets (int64) on the GPU; sequences: the pair self.sequences returned.  The
+        alignment is global between read[qstart, qend) and the path's bases [path_start, path_end): it finds no better walk and moves
+        no endpoint.  A walk whose path walks_targets called bad gets ALIGN_BAD_PATH and is not aligned; one whose distance exceeds
+        max_edits gets ALIGN_OVER.  It works as it is on simplified graphs and on the contigs of untangle_map with lifted paths."""
+        import torch
+
+        if walks.qstart is None or walks.qend is None:
+            raise ValueError("align wants walks whose paths carry start and end (extract with start / end kept)")
+        if getattr(self, "overlap", None) is None:
+            raise ValueError("align wants the pair that self.sequences(engine, node_seqs) returned")
+        t = engine.walks_targets(walks, walks.paths.unitig, sequences[0], sequences[1], self.overlap)
+        nw = walks.first_step.numel()
+        qb, qe = walk_query_intervals(walks, read_off)
+        bad = t["bad"].bool()
+        qe = torch.where(bad, qb, qe)  # a bad walk is an empty pair: nothing is read for it
+        a = engine.align_pairs(bases, t["tgt"], qb, qe, t["tgt_off"][:-1].contiguous(), t["tgt_off"][1:].contiguous(), max_edits)
+        flags = torch.where(bad, torch.full_like(a["flags"], ALIGN_BAD_PATH), a["flags"]) if nw else a["flags"]
+        zero = lambda x: torch.where(bad, torch.zeros_like(x), x) if nw else x  # noqa: E731
+        return WalkAlignments(a["edits"], zero(a["matches"]), zero(a["n_ops"]), a["ops_off"], a["ops"], flags)
+
     def write_gfa(self, path, members=False, sequences=None):
         """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
         members=True an nd:Z: tag that lists node index and orientation in path order) and an L line per twin pair of edges, by the rule
@@ -1683,25 +1782,33 @@ class ReadWalks:
                 d[f] = x.cpu().numpy().view(np.uint64 if x.element_size() == 8 else np.uint32)
         return d
 
-    def write_gaf(self, path, graph=None, names=None, read_lengths=None, first_read=0):
+    def write_gaf(self, path, graph=None, names=None, read_lengths=None, first_read=0, alignments=None):
         """One GAF line per walk (write_gaf_walks).  graph: the UnitigGraph the walks were taken on (only its naming is used: unitig t
         is segment t, as in write_unitig_gfa; may be None); names: one name per read (the index first_read + r when None);
-        read_lengths: one length per read (* when None)."""
+        read_lengths: one length per read (* when None); alignments: the WalkAlignments UnitigGraph.align returned for these walks
+        (residue matches, block length, NM:i: and cg:Z: on every walk it aligned)."""
         if self.qstart is None or self.qend is None:
             raise ValueError("write_gaf wants paths that carry start and end (extract with start / end kept)")
         h = self.host()
-        write_gaf_walks(path, h, self.paths.unitig.cpu().numpy().view(np.uint32), names=names, read_lengths=read_lengths, first_read=first_read)
+        write_gaf_walks(path, h, self.paths.unitig.cpu().numpy().view(np.uint32), names=names, read_lengths=read_lengths, first_read=first_read,
+                        alignments=None if alignments is None else alignments.host())
 
 
-def write_gaf_walks(path, walks, step_unitig, names=None, read_lengths=None, first_read=0):
+def write_gaf_walks(path, walks, step_unitig, names=None, read_lengths=None, first_read=0, alignments=None):
     """ReadWalks.write_gaf on host arrays: walks = the dict ReadWalks.host() returns, step_unitig = the paths' oriented unitig per
     step.  One line per walk, tab-separated: read name, read length (*: unknown), qstart, qend, +, the path as >t (oriented unitig 2
     t) or <t (2 t + 1) per step with the unitig names of write_unitig_gfa, path_len, path_start, path_end, items (the matches column:
     k-min-mers, not bases), max(qend - qstart, path_end - path_start) (the block length), 255, km:i:<items>, ns:i:<n_steps>.  On a
-    circular unitig path_end may pass path_len (include/s2k.h)."""
+    circular unitig path_end may pass path_len (include/s2k.h).  alignments: the dict WalkAlignments.host() returns (edits, matches,
+    n_ops, ops_off, ops, flags per walk); a walk whose flags are 0 then has the residue matches in the matches column, the sum of its
+    run lengths as the block length, and NM:i:<edits> and cg:Z:<runs with = X I D> after the two tags; a flagged walk keeps the line
+    it has without alignments."""
     off = np.asarray(walks["walk_off"]).astype(np.int64).tolist()
     w = {f: np.asarray(walks[f]).astype(np.int64).tolist() for f in ReadWalks.FIELDS}
     u = np.asarray(step_unitig).astype(np.int64).tolist()
+    al = alignments
+    if al is not None:
+        block = al["block_len"] if "block_len" in al else alignment_block_len(al["ops_off"], al["n_ops"], al["ops"])
     with open(path, "w") as out:
         for r in range(len(off) - 1):
             name = str(first_read + r) if names is None else names[r]
@@ -1710,8 +1817,75 @@ def write_gaf_walks(path, walks, step_unitig, names=None, read_lengths=None, fir
                 a = w["first_step"][i]
                 steps = "".join("%s%d" % ("<" if x & 1 else ">", x >> 1) for x in u[a: a + w["n_steps"][i]])
                 qs, qe, ps, pe = w["qstart"][i], w["qend"][i], w["path_start"][i], w["path_end"][i]
-                out.write("%s\t%s\t%d\t%d\t+\t%s\t%d\t%d\t%d\t%d\t%d\t255\tkm:i:%d\tns:i:%d\n" % (
-                    name, ln, qs, qe, steps, w["path_len"][i], ps, pe, w["items"][i], max(qe - qs, pe - ps), w["items"][i], w["n_steps"][i]))
+                matches, blen, tags = w["items"][i], max(qe - qs, pe - ps), ""
+                if al is not None and int(al["flags"][i]) == 0:
+                    o = int(al["ops_off"][i])
+                    matches, blen = int(al["matches"][i]), int(block[i])
+                    tags = "\tNM:i:%d\tcg:Z:%s" % (int(al["edits"][i]), cigar_string(al["ops"][o: o + int(al["n_ops"][i])]))
+                out.write("%s\t%s\t%d\t%d\t+\t%s\t%d\t%d\t%d\t%d\t%d\t255\tkm:i:%d\tns:i:%d%s\n" % (
+                    name, ln, qs, qe, steps, w["path_len"][i], ps, pe, matches, blen, w["items"][i], w["n_steps"][i], tags))
+
+
+def walk_query_intervals(walks, read_off):
+    """-> (begin, end): int64 GPU tensors with every walk's read interval [read_off[r] + qstart, read_off[r] + qend) in the batch's
+    bases, the read r of a walk from walk_off"""
+    import torch
+
+    wo, dev = walks.walk_off.to(torch.int64), read_off.device
+    read = torch.repeat_interleave(torch.arange(wo.numel() - 1, device=dev), wo[1:] - wo[:-1])
+    base = read_off.to(torch.int64)[read]
+    return base + (walks.qstart.to(torch.int64) & 0xFFFFFFFF), base + (walks.qend.to(torch.int64) & 0xFFFFFFFF)
+
+
+class WalkAlignments:
+    """The alignments of one batch's walks (UnitigGraph.align; include/s2k.h: s2k_align_pairs), one entry per walk: edits, matches (the
+    bases under =), n_ops, flags (ALIGN_OVER: the distance exceeds max_edits; ALIGN_BAD_PATH: the walk's path could not be stitched),
+    ops_off (n_walks + 1) and ops: the CIGAR of walk w is ops[ops_off[w] : ops_off[w] + n_ops[w]], each len << 4 | op with the BAM
+    codes CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X.  A flagged walk has no run.  GPU tensors: ops_off int64, the rest int32 holding the
+    uint32 values."""
+
+    FIELDS = ("edits", "matches", "n_ops", "ops_off", "ops", "flags")
+
+    def __init__(self, edits, matches, n_ops, ops_off, ops, flags):
+        self.edits, self.matches, self.n_ops, self.ops_off, self.ops, self.flags = edits, matches, n_ops, ops_off, ops, flags
+        self._host = None
+
+    @property
+    def n_over(self):
+        return int((self.flags & ALIGN_OVER).ne(0).sum())
+
+    @property
+    def n_bad(self):
+        return int((self.flags & ALIGN_BAD_PATH).ne(0).sum())
+
+    def host(self):
+        """-> dict of numpy arrays: ops_off uint64, the rest uint32; block_len (uint64 per walk) = the sum of the run lengths"""
+        if self._host is None:
+            d = {f: getattr(self, f).cpu().numpy().view(np.uint64 if f == "ops_off" else np.uint32) for f in self.FIELDS}
+            d["block_len"] = alignment_block_len(d["ops_off"], d["n_ops"], d["ops"])
+            self._host = d
+        return self._host
+
+    @property
+    def block_len(self):
+        return self.host()["block_len"]
+
+    def cigar(self, w):
+        """the CIGAR of walk w with = X I D, "" for a flagged walk"""
+        h = self.host()
+        return cigar_string(h["ops"][int(h["ops_off"][w]): int(h["ops_off"][w]) + int(h["n_ops"][w])])
+
+
+def cigar_string(ops):
+    """runs len << 4 | op -> text with = X I D"""
+    return "".join("%d%s" % (int(x) >> 4, CIGAR_CHARS[int(x) & 15]) for x in ops)
+
+
+def alignment_block_len(ops_off, n_ops, ops):
+    """per alignment the sum of its run lengths (uint64)"""
+    ln = np.concatenate([[0], np.cumsum(np.asarray(ops).astype(np.uint64) >> np.uint64(4))]).astype(np.uint64)
+    a = np.asarray(ops_off).astype(np.int64)[:-1]
+    return ln[a + np.asarray(n_ops).astype(np.int64)] - ln[a]
 
 
 class SpanTable:
