@@ -303,6 +303,42 @@ def pack_reads(reads):
     return np.ascontiguousarray(bases, dtype=np.uint8), off
 
 
+def _p(x, k=1):
+    """the device pointer of tensor x as a C argument, NULL when k is 0 (an empty array) or x is None"""
+    return C.c_void_p(x.data_ptr() if k and x is not None else 0)
+
+
+def _paths_struct(paths, fields, capacity):
+    """-> (ThreadOut, tensors): the struct that names path_off and those of `fields` a ReadPaths carries, and the contiguous
+    tensors behind it by field, which the caller keeps alive over its calls"""
+    o = ThreadOut()
+    o.capacity = capacity
+    keep = {f: getattr(paths, f).contiguous() for f in ("path_off",) + tuple(fields) if getattr(paths, f) is not None}
+    for f, x in keep.items():
+        setattr(o, f, x.data_ptr() if x.numel() else 0)
+    return o, keep
+
+
+def _paths_out(o, res, keep, m, per_step, n_steps):
+    """before the second call of paths_bridge / paths_lift: room for m output steps of the step fields the input carries (named in o) and
+    of matched, and for the per_step arrays ({name: dtype}, one entry per input step), all into res"""
+    import torch
+
+    dev = res["path_off"].device
+    for f in [f for f in ReadPaths.STEP_FIELDS if f in keep] + ["matched"]:
+        res[f] = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        if f != "matched":
+            setattr(o, f, res[f].data_ptr())
+    for f, dt in per_step.items():
+        res[f] = torch.empty(max(n_steps, 1), dtype=dt, device=dev)
+    o.capacity = m
+
+
+def _paths_result(res, per_step, m, n_steps, **totals):
+    """what paths_bridge / paths_lift return: path_off whole, the per_step arrays cut to n_steps, the rest to m, and the totals"""
+    return {**{f: (x if f == "path_off" else x[:n_steps] if f in per_step else x[:m]) for f, x in res.items()}, "n_steps": m, **totals}
+
+
 class Engine:
     """One s2k_ctx (one per thread and device, like one KminmersIterator per thread in src/main.rs:65-79)."""
 
@@ -621,10 +657,9 @@ class Engine:
         ok, oc = torch.empty(max(n, 1), dtype=torch.int64, device=dev), torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         oek, oec = torch.empty(max(ne, 1), dtype=torch.int64, device=dev), torch.empty(max(ne, 1), dtype=torch.int32, device=dev)
         nn, nne = C.c_uint64(0), C.c_uint64(0)
-        p = lambda t, m=1: C.c_void_p(t.data_ptr() if m else 0)  # noqa: E731
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_graph_induced(self.ctx, p(keys, n), p(counts, n), n, p(ek, ne), p(ec, ne), ne, *mask_args,
-                                               p(new_id), p(ok), p(oc), n, p(oek), p(oec), ne, C.byref(nn), C.byref(nne)))
+        self._check(self.lib.s2k_graph_induced(self.ctx, _p(keys, n), _p(counts, n), n, _p(ek, ne), _p(ec, ne), ne, *mask_args,
+                                               _p(new_id), _p(ok), _p(oc), n, _p(oek), _p(oec), ne, C.byref(nn), C.byref(nne)))
         a, b = int(nn.value), int(nne.value)
         return {"keys": ok[:a], "counts": oc[:a], "edge_keys": oek[:b], "edge_counts": oec[:b], "new_id": new_id[:n]}
 
@@ -729,21 +764,15 @@ class Engine:
             raise ValueError("paths_spans wants a UnitigGraph: the CSR over its oriented unitigs and uni_off")
         if edge_support is not None and (edge_support.numel() != ne or edge_support.element_size() != 8 or not edge_support.is_contiguous()):
             raise ValueError("edge_support holds one 64-bit entry per edge")
-        o = ThreadOut()
-        o.capacity = ns
-        keep = {f: getattr(paths, f).contiguous() for f in ("path_off", "unitig", "pos", "count", "flags")}
-        for f, x in keep.items():
-            setattr(o, f, x.data_ptr() if x.numel() else 0)
+        o, keep = _paths_struct(paths, ("unitig", "pos", "count", "flags"), ns)
         nk, nf, no = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        args = (self.ctx, nr, C.byref(o), ns, C.c_void_p(row_off.data_ptr()), C.c_void_p(dst.data_ptr() if ne else 0), ne,
-                C.c_void_p(uni_off.data_ptr()), t)
+        args = (self.ctx, nr, C.byref(o), ns, _p(row_off), _p(dst, ne), ne, _p(uni_off), t)
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_paths_spans(*args, None, 0, None, C.byref(nk), C.byref(nf), C.byref(no)))
         n = int(nk.value)
         keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_paths_spans(*args, C.c_void_p(keys.data_ptr()), n, C.c_void_p(edge_support.data_ptr() if edge_support is not None and ne else 0),
-                                             C.byref(nk), C.byref(nf), C.byref(no)))
+        self._check(self.lib.s2k_paths_spans(*args, _p(keys), n, _p(edge_support, ne), C.byref(nk), C.byref(nf), C.byref(no)))
         return keys[:n], int(nf.value), int(no.value)
 
     def graph_resolve_mask(self, unitig_graph, span_keys, span_counts, min_support=2):
@@ -785,8 +814,7 @@ class Engine:
                 or partner.numel() != ne or partner.element_size() != 4 or counts.numel() != t or counts.element_size() != 8 or ec.numel() != ne
                 or ec.element_size() != 4):
             raise ValueError("graph_untangle wants a UnitigGraph, one resolved byte per unitig and one 32-bit partner per edge")
-        p = lambda x, n=1: C.c_void_p(x.data_ptr() if n else 0)  # noqa: E731
-        args = (self.ctx, p(row_off), p(dst, ne), ne, t, p(resolved, t), p(partner, ne), p(counts, t), p(ec, ne))
+        args = (self.ctx, _p(row_off), _p(dst, ne), ne, t, _p(resolved, t), _p(partner, ne), _p(counts, t), _p(ec, ne))
         nc, nd = C.c_uint64(0), C.c_uint64(0)
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_graph_untangle(*args, None, None, None, None, None, 0, C.byref(nc), C.byref(nd)))
@@ -796,7 +824,7 @@ class Engine:
         copy_count = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         keys, src = torch.empty(max(ne, 1), dtype=torch.int64, device=dev), torch.empty(max(ne, 1), dtype=torch.int64, device=dev)
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_graph_untangle(*args, p(copy_off), p(origin), p(copy_count), p(keys), p(src), n, C.byref(nc), C.byref(nd)))
+        self._check(self.lib.s2k_graph_untangle(*args, _p(copy_off), _p(origin), _p(copy_count), _p(keys), _p(src), n, C.byref(nc), C.byref(nd)))
         return {"copy_off": copy_off, "origin": origin[:n], "copy_count": copy_count[:n], "keys": keys[:ne], "src_edge": src[:ne], "n_copies": n,
                 "n_duplicated": int(nd.value)}
 
@@ -814,8 +842,7 @@ class Engine:
         if (oo.numel() != nt + 1 or om.numel() != ncp or uni_off.numel() != t + 1 or oo.element_size() != 8 or uni_off.element_size() != 8
                 or om.element_size() != 4 or origin.element_size() != 4 or members.element_size() != 4):
             raise ValueError("unitig_expand wants the outer decomposition over the copies, one 32-bit origin per copy, and the inner decomposition")
-        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
-        args = (self.ctx, p(oo), p(om, ncp), p(oc, nt), nt, ncp, p(origin, ncp), p(uni_off), p(members, n), p(circular, t), t, n)
+        args = (self.ctx, _p(oo), _p(om, ncp), _p(oc, nt), nt, ncp, _p(origin, ncp), _p(uni_off), _p(members, n), _p(circular, t), t, n)
         nm = C.c_uint64(0)
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_unitig_expand(*args, None, None, None, None, None, None, 0, C.byref(nm)))
@@ -824,7 +851,7 @@ class Engine:
                "node_unitig": torch.empty(max(m, 1), dtype=torch.int32, device=dev), "node_pos": torch.empty(max(m, 1), dtype=torch.int32, device=dev),
                "circular": torch.empty(max(nt, 1), dtype=torch.uint8, device=dev), "node_origin": torch.empty(max(m, 1), dtype=torch.int32, device=dev)}
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_unitig_expand(*args, *(p(res[f]) for f in ("uni_off", "members", "node_unitig", "node_pos", "circular", "node_origin")),
+        self._check(self.lib.s2k_unitig_expand(*args, *(_p(res[f]) for f in ("uni_off", "members", "node_unitig", "node_pos", "circular", "node_origin")),
                                                m, C.byref(nm)))
         out = {f: res[f][:m] for f in ("members", "node_unitig", "node_pos", "node_origin")}
         out.update(uni_off=res["uni_off"], circular=res["circular"][:nt], n_members=m)
@@ -864,14 +891,9 @@ class Engine:
                 or member_off.element_size() != 8 or out_off.numel() != t + 1 or overlap.numel() != 2 * t or overlap.element_size() != 4
                 or seq_len.numel() != n or seq_len.element_size() != 4):
             raise ValueError("paths_walks wants a UnitigGraph, the offsets Engine.unitig_member_offsets returned for it and one 32-bit seq_len per node")
-        o = ThreadOut()
-        o.capacity = ns
-        keep = {f: getattr(paths, f).contiguous() for f in ("path_off", "unitig", "pos", "count", "flags", "start", "end") if getattr(paths, f) is not None}
-        for f, x in keep.items():
-            setattr(o, f, x.data_ptr() if x.numel() else 0)
-        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
-        args = (self.ctx, nr, C.byref(o), ns, p(row_off), p(dst, ne), ne, p(uni_off), p(circular, t), t, p(member_off, n), p(out_off), p(overlap, t),
-                p(seq_len, n), p(members, n), n)
+        o, keep = _paths_struct(paths, ("unitig", "pos", "count", "flags", "start", "end"), ns)
+        args = (self.ctx, nr, C.byref(o), ns, _p(row_off), _p(dst, ne), ne, _p(uni_off), _p(circular, t), t, _p(member_off, n), _p(out_off), _p(overlap, t),
+                _p(seq_len, n), _p(members, n), n)
         nw, nf, no = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_paths_walks(*args, None, C.byref(nw), C.byref(nf), C.byref(no)))
@@ -908,13 +930,8 @@ class Engine:
         if (row_off.numel() != 2 * t + 1 or row_off.element_size() != 8 or dst.element_size() != 4 or uni_off.numel() != t + 1 or uni_off.element_size() != 8
                 or circular.element_size() != 1):
             raise ValueError("paths_bridge wants a UnitigGraph: the CSR over its oriented unitigs, uni_off and circular")
-        i = ThreadOut()
-        i.capacity = ns
-        keep = {f: getattr(paths, f).contiguous() for f in ("path_off",) + ReadPaths.STEP_FIELDS if getattr(paths, f) is not None}
-        for f, x in keep.items():
-            setattr(i, f, x.data_ptr() if x.numel() else 0)
-        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
-        args = (self.ctx, nr, C.byref(i), ns, p(row_off), p(dst, ne), ne, p(uni_off), p(circular, t), t, int(max_gap), int(max_slip))
+        i, keep = _paths_struct(paths, ReadPaths.STEP_FIELDS, ns)
+        args = (self.ctx, nr, C.byref(i), ns, _p(row_off), _p(dst, ne), ne, _p(uni_off), _p(circular, t), t, int(max_gap), int(max_slip))
         res = {"path_off": torch.zeros(nr + 1, dtype=torch.int64, device=dev)}
         o = ThreadOut()
         o.path_off = res["path_off"].data_ptr()
@@ -922,19 +939,11 @@ class Engine:
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_paths_bridge(*args, C.byref(o), None, None, C.byref(no), C.byref(nm), C.byref(nb)))
         m = int(no.value)
-        for f in [f for f in ReadPaths.STEP_FIELDS if f in keep] + ["matched"]:
-            res[f] = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
-            if f != "matched":
-                setattr(o, f, res[f].data_ptr())
-        if join:
-            res["join"] = torch.empty(max(ns, 1), dtype=torch.uint8, device=dev)
-        o.capacity = m
+        per_step = {"join": torch.uint8} if join else {}
+        _paths_out(o, res, keep, m, per_step, ns)
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_paths_bridge(*args, C.byref(o), p(res["matched"]), p(res["join"]) if join else None, C.byref(no), C.byref(nm),
-                                              C.byref(nb)))
-        out = {f: (x if f == "path_off" else x[:ns] if f == "join" else x[:m]) for f, x in res.items()}
-        out.update(n_steps=m, n_merged=int(nm.value), n_bridged=int(nb.value))
-        return out
+        self._check(self.lib.s2k_paths_bridge(*args, C.byref(o), _p(res["matched"]), _p(res.get("join")), C.byref(no), C.byref(nm), C.byref(nb)))
+        return _paths_result(res, per_step, m, ns, n_merged=int(nm.value), n_bridged=int(nb.value))
 
     def unitig_copy_places(self, outer, origin, uni_off, circular):
         """Where every copy of an untangled graph lies on its contigs (s2k_unitig_copy_places; the definitions are in include/s2k.h):
@@ -950,9 +959,8 @@ class Engine:
                 or om.element_size() != 4 or origin.element_size() != 4 or oc.element_size() != 1 or circular.element_size() != 1):
             raise ValueError("unitig_copy_places wants the outer decomposition over the copies, one 32-bit origin per copy, and the inner uni_off and circular")
         place = torch.empty((max(ncp, 1), 4), dtype=torch.int32, device=dev)
-        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_unitig_copy_places(self.ctx, p(oo), p(om, ncp), p(oc, nt), nt, ncp, p(origin, ncp), p(uni_off), p(circular, t), t, p(place)))
+        self._check(self.lib.s2k_unitig_copy_places(self.ctx, _p(oo), _p(om, ncp), _p(oc, nt), nt, ncp, _p(origin, ncp), _p(uni_off), _p(circular, t), t, _p(place)))
         return place[:ncp]
 
     def paths_lift(self, unitig_graph, paths, resolved, partner, copy_off, copy_place, n_contigs, contig_items=None, step_copy=False, join=False):
@@ -976,15 +984,10 @@ class Engine:
                              "and the (n_copies, 4) records of unitig_copy_places")
         if contig_items is not None and (contig_items.numel() != n_contigs or contig_items.element_size() != 8 or not contig_items.is_contiguous()):
             raise ValueError("contig_items holds one 64-bit entry per contig")
-        i = ThreadOut()
-        i.capacity = ns
-        keep = {f: getattr(paths, f).contiguous() for f in ("path_off",) + ReadPaths.STEP_FIELDS if getattr(paths, f) is not None}
-        for f, x in keep.items():
-            setattr(i, f, x.data_ptr() if x.numel() else 0)
+        i, keep = _paths_struct(paths, ReadPaths.STEP_FIELDS, ns)
         matched_in = paths.matched.contiguous() if paths.matched is not None else None
-        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k and x is not None else 0)  # noqa: E731
-        args = (self.ctx, nr, C.byref(i), ns, p(matched_in, ns), p(row_off), p(dst, ne), ne, p(uni_off), p(circular, t), t, p(resolved, t), p(partner, ne),
-                p(copy_off), p(copy_place, ncp), ncp, int(n_contigs))
+        args = (self.ctx, nr, C.byref(i), ns, _p(matched_in, ns), _p(row_off), _p(dst, ne), ne, _p(uni_off), _p(circular, t), t, _p(resolved, t), _p(partner, ne),
+                _p(copy_off), _p(copy_place, ncp), ncp, int(n_contigs))
         res = {"path_off": torch.zeros(nr + 1, dtype=torch.int64, device=dev)}
         o = ThreadOut()
         o.path_off = res["path_off"].data_ptr()
@@ -992,21 +995,12 @@ class Engine:
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_paths_lift(*args, C.byref(o), None, None, None, None, *(C.byref(x) for x in tot)))
         m = int(tot[0].value)
-        for f in [f for f in ReadPaths.STEP_FIELDS if f in keep] + ["matched"]:
-            res[f] = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
-            if f != "matched":
-                setattr(o, f, res[f].data_ptr())
-        if step_copy:
-            res["step_copy"] = torch.empty(max(ns, 1), dtype=torch.int32, device=dev)
-        if join:
-            res["join"] = torch.empty(max(ns, 1), dtype=torch.uint8, device=dev)
-        o.capacity = m
+        per_step = {**({"step_copy": torch.int32} if step_copy else {}), **({"join": torch.uint8} if join else {})}
+        _paths_out(o, res, keep, m, per_step, ns)
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_paths_lift(*args, C.byref(o), p(res["matched"]), p(res.get("step_copy")), p(res.get("join")),
-                                            p(contig_items, n_contigs), *(C.byref(x) for x in tot)))
-        out = {f: (x if f == "path_off" else x[:ns] if f in ("join", "step_copy") else x[:m]) for f, x in res.items()}
-        out.update(n_steps=m, n_merged=int(tot[1].value), n_dropped=int(tot[2].value), n_conflicts=int(tot[3].value))
-        return out
+        self._check(self.lib.s2k_paths_lift(*args, C.byref(o), _p(res["matched"]), _p(res.get("step_copy")), _p(res.get("join")),
+                                            _p(contig_items, n_contigs), *(C.byref(x) for x in tot)))
+        return _paths_result(res, per_step, m, ns, n_merged=int(tot[1].value), n_dropped=int(tot[2].value), n_conflicts=int(tot[3].value))
 
     def walks_targets(self, walks, step_unitig, out_off, out, overlap):
         """The bases of every walk's path interval (s2k_walks_targets; the definitions are in include/s2k.h).  walks: a ReadWalks (or
@@ -1021,8 +1015,7 @@ class Engine:
         if (any(x.numel() != nw for x in rec) or [x.element_size() for x in rec] != [8, 4, 8, 8, 4] or step_unitig.element_size() != 4
                 or out_off.element_size() != 8 or out.element_size() != 1 or overlap.numel() != 2 * t or overlap.element_size() != 4):
             raise ValueError("walks_targets wants the walk records, one 32-bit unitig per step, and the out_off, out and overlap of the unitig sequences")
-        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
-        args = (self.ctx, nw, *(p(x, nw) for x in rec), p(step_unitig, ns), ns, p(out_off), p(out, out.numel()), out.numel(), p(overlap, t), t)
+        args = (self.ctx, nw, *(_p(x, nw) for x in rec), _p(step_unitig, ns), ns, _p(out_off), _p(out, out.numel()), out.numel(), _p(overlap, t), t)
         tgt_off = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
         bad = torch.zeros(max(nw, 1), dtype=torch.uint8, device=dev)
         nb = C.c_uint64(0)
@@ -1031,7 +1024,7 @@ class Engine:
         n = int(nb.value)
         tgt = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_walks_targets(*args, p(tgt_off), p(tgt), p(bad), n, C.byref(nb)))
+        self._check(self.lib.s2k_walks_targets(*args, _p(tgt_off), _p(tgt), _p(bad), n, C.byref(nb)))
         return {"tgt_off": tgt_off, "tgt": tgt[:n], "bad": bad[:nw], "n_bytes": n}
 
     def align_pairs(self, query, target, q_begin, q_end, t_begin, t_end, max_edits=ALIGN_MAX_EDITS):
@@ -1047,8 +1040,7 @@ class Engine:
         n, dev = iv[0].numel(), query.device
         if any(x.numel() != n or x.element_size() != 8 for x in iv) or query.element_size() != 1 or target.element_size() != 1:
             raise ValueError("align_pairs wants two byte pools and four 64-bit interval arrays of one length")
-        p = lambda x, k=1: C.c_void_p(x.data_ptr() if k else 0)  # noqa: E731
-        args = (self.ctx, p(query, query.numel()), query.numel(), p(target, target.numel()), target.numel(), *(p(x, n) for x in iv), n, int(max_edits))
+        args = (self.ctx, _p(query, query.numel()), query.numel(), _p(target, target.numel()), target.numel(), *(_p(x, n) for x in iv), n, int(max_edits))
         res = {f: torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for f in ("edits", "flags", "n_ops", "matches")}
         res["ops_off"] = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         o = AlignOut()

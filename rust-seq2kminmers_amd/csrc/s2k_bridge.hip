@@ -2,25 +2,20 @@
 // and two that lie a few items apart across one edge are extended to the edge, so that the spans, walks and GAF lines downstream see
 // the crossing (include/s2k.h: s2k_paths_bridge).
 //
-// The stable stream compaction of s2k_compact_dev.h with two masks, as s2k_table_thread and s2k_paths_walks, over tiles of TB_TILE
-// steps (lane tid holds steps r * 256 + tid):
-//  1. bridge_check_kernel: the path and CSR rules of walks_check_kernel (s2k_walk.hip) without the base-space arrays, and no unitig
-//     of 2^32 members or more.  One flag word, read by the host before anything is written; every read is clamped to the arrays.
+// Runs of steps (s2k_runs_dev.h), tiles of TB_TILE steps (lane tid holds steps r * 256 + tid):
+//  1. bridge_check_kernel: the shared rules of s2k_span_dev.h (path_off_ok, steps_ok, unitig_row_ok).  One flag word, read by the
+//     host before anything is written; every read is clamped to the arrays.
 //  2. bridge_count_kernel: per step its unitig, where it ends (pos + count), the members left behind it (len - pos - count; BR_NONE
 //     on a circular unitig) and the item it ends at go to LDS with the step before the tile; the read starts in [t0, t0 + TB_TILE] are
 //     marked from the reads a binary search of path_off finds there.  One lane per step decides join from its neighbour in LDS; the
-//     row search of kind 2 runs only where the limits already stand, the row bounds of all TB_Q steps loaded before the first probe,
-//     the TB_Q searches side by side.  join goes to workspace and to LDS; one lane decides the step after the tile.  Heads (join !=
-//     1) and tails (the step after it is not joined by 1): two ballots per 64 steps, tile_prefixes twice, and whether a run is open at
-//     the tile's first step.  Merged and bridged joins: a block sum.  An item order that would wrap gi sets the flag word, which the
-//     host reads again with the totals, before anything is written.
-//  3. launch_scan_u32 over the heads per tile (tails before a tile = heads before it - open) and over count: matched is a difference
-//     of two prefix entries.
-//  4. bridge_offsets_kernel: out path_off[r] = heads before path_off[r].
-//  5. bridge_write_kernel: output step s is the s-th head and the s-th tail, paired as in thread_write_kernel and walks_write_kernel
-//     (heads' indices in LDS by slot; the one tail per tile whose head lies in an earlier tile finds it by head_item).  The tail's
-//     lane gathers the head's fields and the join of the step after it; each array is staged in LDS and leaves with leave_run.  No
-//     lane walks a run, and there is no atomic on an output.
+//     row search of kind 2 (search_rows) runs only where the limits already stand.  join goes to workspace and to LDS; one lane
+//     decides the step after the tile.  Heads: join != 1; tails: the step after it is not joined by 1.  Merged and bridged joins: a
+//     block sum.  An item order that would wrap gi sets the flag word, which the host reads again with the totals, before anything
+//     is written.
+//  3. launch_scan_u32 over count: matched is a difference of two prefix entries.
+//  4. run_offsets_kernel: out path_off[r] = heads before path_off[r].
+//  5. bridge_write_kernel: output step s is the s-th head and the s-th tail.  The tail's lane gathers the head's fields and the join
+//     of the step after it.  There is no atomic on an output.
 //
 // Workspace (the context's grow-only count workspace): 9 B per step (join 1, the prefix of count 8), and per mask 8 B + 4 B per 64
 // steps and 4 B + 8 B per tile.
@@ -28,10 +23,10 @@
 
 #include "../../include/s2k.h"
 #include "s2k_call.h"
-#include "s2k_compact_dev.h"
 #include "s2k_dev.h"
 #include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
+#include "s2k_runs_dev.h"
 #include "s2k_span_dev.h"
 #include "s2k_table_dev.h"
 
@@ -50,36 +45,18 @@ struct BridgeIn {
 };
 
 struct BridgeWs {
-    uint8_t *join;       // per step
-    uint64_t *C;         // n_steps + 1: the exclusive prefix of count
-    uint32_t *tile_open; // per tile: 1 when its first step is joined to the step before it on the same unitig
-    CompactWs h, t;      // heads; tails (of the tails only wmask, wpre and tile_kept are used)
+    uint8_t *join; // per step
+    uint64_t *C;   // n_steps + 1: the exclusive prefix of count
+    RunWs run;     // open: the tile's first step is joined to the step before it on the same unitig
 };
 
 __global__ __launch_bounds__(UT) void bridge_check_kernel(BridgeIn p, Csr g, uint64_t n_edges, uint32_t *__restrict__ bad) {
-    bool ok = true;
     const uint64_t n_ids = 2 * p.n_unitigs;
     const uint64_t i0 = (uint64_t)blockIdx.x * UT + threadIdx.x, stride = (uint64_t)gridDim.x * UT;
-    for (uint64_t r = i0; r <= p.n_reads; r += stride) {
-        const uint64_t a = p.path_off[r];
-        if (r == 0 && a != 0) ok = false;
-        if (r == p.n_reads ? a != p.n_steps : a > p.path_off[r + 1]) ok = false;
-    }
-    for (uint64_t s = i0; s < p.n_steps; s += stride) {
-        const uint64_t U = p.unitig[s];
-        if (U >= n_ids) {
-            ok = false;
-            continue;
-        }
-        const uint64_t a = p.uni_off[U >> 1], b = p.uni_off[(U >> 1) + 1], c = p.count[s], q = p.pos[s];
-        if (a >= b || c == 0 || q >= b - a || (!p.circular[U >> 1] && q + c > b - a)) ok = false;
-    }
-    for (uint64_t u = i0; u < n_ids; u += stride) {
-        if (!csr_ids_ok(g.row_off, g.dst, u, n_ids, n_edges)) ok = false;
-        if (u & 1) continue;
-        const uint64_t a = p.uni_off[u >> 1], b = p.uni_off[(u >> 1) + 1];
-        if (a >= b || b - a >= (1ull << 32)) ok = false;
-    }
+    bool ok = path_off_ok(p.path_off, p.n_reads, p.n_steps, i0, stride);
+    if (!steps_ok(p.unitig, p.pos, p.count, p.n_steps, p.uni_off, p.circular, n_ids, i0, stride)) ok = false;
+    for (uint64_t u = i0; u < n_ids; u += stride)
+        if (!unitig_row_ok(g, p.uni_off, u, n_ids, n_edges)) ok = false;
     if (!ok) atomicOr(bad, 1u);
 }
 
@@ -114,8 +91,7 @@ __device__ __forceinline__ uint32_t join_before_search(const BridgeIn &p, uint32
 __global__ __launch_bounds__(TB_THREADS) void bridge_count_kernel(BridgeIn p, Csr g, BridgeWs ws, unsigned long long *__restrict__ totals /* merged, bridged */,
                                                                   uint32_t *__restrict__ bad) {
     __shared__ BridgeLds s;
-    __shared__ uint32_t wch[TB_WORDS], wct[TB_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     uint32_t U[TB_Q], ps[TB_Q], it[TB_Q];
     bool circ[TB_Q], wrong = false;
@@ -176,24 +152,7 @@ __global__ __launch_bounds__(TB_THREADS) void bridge_count_kernel(BridgeIn p, Cs
         hi[r] = kind[r] == 2 ? g.row_off[A + 1] : lo[r];
         if (kind[r] == 2) kind[r] = 0; // until the edge is found
     }
-    for (;;) { // TB_Q searches side by side
-        bool more = false;
-#pragma unroll
-        for (int r = 0; r < TB_Q; r++) {
-            if (lo[r] < hi[r]) {
-                const uint64_t mid = (lo[r] + hi[r]) >> 1;
-                const uint32_t v = g.dst[mid], B = U[r];
-                if (v < B) lo[r] = mid + 1;
-                else if (v > B) hi[r] = mid;
-                else {
-                    kind[r] = 2;
-                    lo[r] = hi[r];
-                }
-                more |= lo[r] < hi[r];
-            }
-        }
-        if (!more) break;
-    }
+    search_rows(g, lo, hi, U, [&](int r, uint64_t) { kind[r] = 2; });
     uint32_t n[2] = {0, 0}; // merged, bridged
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) {
@@ -215,34 +174,12 @@ __global__ __launch_bounds__(TB_THREADS) void bridge_count_kernel(BridgeIn p, Cs
         s.join[TB_TILE + 1] = (uint8_t)(k == 1);
     }
     __syncthreads();
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) {
-        const int i = r * TB_THREADS + tid + 1;
-        const bool valid = t0 + (i - 1) < p.n_steps;
-        const uint64_t mh = __ballot(valid && s.join[i] != 1), mt = __ballot(valid && s.join[i + 1] != 1);
-        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wch[r * 4 + wv] = (uint32_t)__popcll(mh);
-            wct[r * 4 + wv] = (uint32_t)__popcll(mt);
-            if (w0 < p.n_steps) {
-                ws.h.wmask[w0 >> 6] = mh;
-                ws.t.wmask[w0 >> 6] = mt;
-            }
-        }
-    }
-    if (tid == 0) ws.tile_open[blockIdx.x] = s.join[1] == 1;
-    __syncthreads();
-    tile_prefixes(wch, t0, p.n_steps, ws.h);
-    tile_prefixes(wct, t0, p.n_steps, ws.t);
+    auto valid = [&](int i) { return t0 + (i - 1) < p.n_steps; };
+    run_count_end(
+        ws.run, t0, p.n_steps, [&](int, int i) { return valid(i) && s.join[i] != 1; }, [&](int, int i) { return valid(i) && s.join[i + 1] != 1; },
+        [&] { return s.join[1] == 1; });
     block_add(n, totals);
     if (wrong) atomicOr(bad, 1u);
-}
-
-__global__ __launch_bounds__(256) void bridge_offsets_kernel(const uint64_t *__restrict__ path_off, uint64_t n_reads, uint64_t n_steps, uint64_t n_tiles,
-                                                             CompactWs heads, uint64_t *__restrict__ out_off) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > n_reads) return;
-    out_off[r] = kept_before(heads, n_steps, n_tiles, path_off[r]);
 }
 
 struct BridgeOut {
@@ -251,31 +188,18 @@ struct BridgeOut {
 
 __global__ __launch_bounds__(TB_THREADS) void bridge_write_kernel(BridgeIn p, BridgeOut io, BridgeWs ws) {
     __shared__ uint4 stage4[(TB_TILE + 2 * STAGE_PAD) / 4]; // TB_TILE 32-bit elements, and a run's shift
-    __shared__ uint32_t shead[TB_TILE];                     // by head slot: the head's step, relative to the tile
-    __shared__ uint64_t sopen;
-    uint32_t *stage = (uint32_t *)stage4;
     const int tid = threadIdx.x;
-    const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
-    const uint64_t hbase = ws.h.tile_off[blockIdx.x];
-    const uint32_t ttot = ws.t.tile_kept[blockIdx.x];
-    if (ttot == 0) return;
-    const uint32_t open = ws.tile_open[blockIdx.x];
-    const uint64_t tbase = hbase - open; // tails before the tile: every head before it has its tail but the open one
-    uint32_t hslot[TB_Q], tslot[TB_Q];
-    const uint32_t hkeep = tile_slots(ws.h, t0, p.n_steps, hslot), tkeep = tile_slots(ws.t, t0, p.n_steps, tslot);
-    if (tid == 64 && open) sopen = head_item(ws.h, blockIdx.x, tbase);
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++)
-        if ((hkeep >> r) & 1u) shead[hslot[r]] = (uint32_t)(r * TB_THREADS + tid);
-    __syncthreads();
+    RunTile rt;
+    if (!run_tile(ws.run, p.n_steps, rt)) return;
+    const uint64_t t0 = rt.t0;
     uint64_t hd[TB_Q];
     uint32_t opos[TB_Q], ocnt[TB_Q], edge = 0; // edge: the run's head was entered across an edge
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) {
         hd[r] = 0, opos[r] = ocnt[r] = 0;
-        if ((tkeep >> r) & 1u) {
+        if ((rt.tkeep >> r) & 1u) {
             const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
-            const uint64_t h = tslot[r] >= open ? t0 + shead[tslot[r] - open] : sopen;
+            const uint64_t h = rt.head_of(r);
             const bool in2 = ws.join[h] == 2, out2 = j + 1 < p.n_steps && ws.join[j + 1] == 2; // a read's first step has join 0
             const uint32_t Uj = p.unitig[j];
             const uint32_t endpos = out2 ? (uint32_t)(p.uni_off[(Uj >> 1) + 1] - p.uni_off[Uj >> 1]) : p.pos[j] + p.count[j];
@@ -285,28 +209,14 @@ __global__ __launch_bounds__(TB_THREADS) void bridge_write_kernel(BridgeIn p, Br
             edge |= (in2 ? 1u : 0u) << r;
         }
     }
-#define BR_LEAVE(OUT, VAL)                                                                  \
-    do {                                                                                    \
-        if (OUT) {                                                                          \
-            const uint32_t sh = shift_of(OUT + tbase);                                      \
-            _Pragma("unroll") for (int r = 0; r < TB_Q; r++) if ((tkeep >> r) & 1u) {       \
-                const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;                     \
-                (void)j;                                                                    \
-                stage[sh + tslot[r]] = (VAL);                                               \
-            }                                                                               \
-            __syncthreads();                                                                \
-            leave_run(OUT + tbase, stage, sh, ttot);                                        \
-        }                                                                                   \
-    } while (0)
-    BR_LEAVE(io.unitig, p.unitig[hd[r]]);
-    BR_LEAVE(io.pos, opos[r]);
-    BR_LEAVE(io.count, ocnt[r]);
-    BR_LEAVE(io.item, p.item[hd[r]]);
-    BR_LEAVE(io.flags, p.flags[hd[r]] | (((edge >> r) & 1u) ? S2K_STEP_LINKED : 0u));
-    BR_LEAVE(io.start, p.start[hd[r]]);
-    BR_LEAVE(io.end, p.end[j]);
-    BR_LEAVE(io.matched, (uint32_t)(ws.C[j + 1] - ws.C[hd[r]]));
-#undef BR_LEAVE
+    rt.leave_tails(io.unitig, stage4, [&](int r, uint64_t) { return p.unitig[hd[r]]; });
+    rt.leave_tails(io.pos, stage4, [&](int r, uint64_t) { return opos[r]; });
+    rt.leave_tails(io.count, stage4, [&](int r, uint64_t) { return ocnt[r]; });
+    rt.leave_tails(io.item, stage4, [&](int r, uint64_t) { return p.item[hd[r]]; });
+    rt.leave_tails(io.flags, stage4, [&](int r, uint64_t) { return p.flags[hd[r]] | (((edge >> r) & 1u) ? S2K_STEP_LINKED : 0u); });
+    rt.leave_tails(io.start, stage4, [&](int r, uint64_t) { return p.start[hd[r]]; });
+    rt.leave_tails(io.end, stage4, [&](int, uint64_t j) { return p.end[j]; });
+    rt.leave_tails(io.matched, stage4, [&](int r, uint64_t j) { return ws.C[j + 1] - ws.C[hd[r]]; });
 }
 
 } // namespace
@@ -322,8 +232,7 @@ s2k_status s2k_paths_bridge(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out
     if (n_out_steps) *n_out_steps = 0;
     if (n_merged) *n_merged = 0;
     if (n_bridged) *n_bridged = 0;
-    if (!ctx || !paths || !out || !n_out_steps || !n_merged || !n_bridged || !paths->path_off || !out->path_off) return S2K_ERR_INVALID_ARG;
-    if (n_steps && (!paths->unitig || !paths->pos || !paths->count || !paths->item || !paths->flags)) return S2K_ERR_INVALID_ARG;
+    if (!ctx || !out || !n_out_steps || !n_merged || !n_bridged || !paths_given(paths, n_steps, true) || !out->path_off) return S2K_ERR_INVALID_ARG;
     if (n_steps && ((out->start && !paths->start) || (out->end && !paths->end))) return S2K_ERR_INVALID_ARG;
     Call c(ctx, "s2k_paths_bridge");
     if (n_unitigs >= (1ull << 31) || n_edges >= (1ull << 32))
@@ -338,13 +247,12 @@ s2k_status s2k_paths_bridge(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out
     const auto join = L.take<uint8_t>(n_steps);
     const auto C = L.take<uint64_t>(n_steps + 1);
     const auto stmp = L.bytes<uint64_t>(scan_tmp_bytes(n_steps));
-    const auto topen = L.take<uint32_t>(nt);
-    const auto hw = carve(L, n_steps, nt), tw = carve(L, n_steps, nt);
+    const auto runs = carve_runs(L, n_steps, nt);
     char *w = L.alloc(ctx);
     if (!w) return c.nomem();
     unsigned long long *totals = words(w);
     uint32_t *bad = (uint32_t *)(totals + 2);
-    const BridgeWs ws{join(w), C(w), topen(w), hw(w), tw(w)};
+    const BridgeWs ws{join(w), C(w), runs(w)};
     const BridgeIn p{paths->path_off, paths->unitig, paths->pos, paths->count, paths->item, paths->flags, paths->start, paths->end,
                      d_uni_off,       d_circular,    n_reads,    n_steps,      n_unitigs,   max_gap,      max_slip};
     const Csr g{d_row_off, d_dst};
@@ -363,13 +271,9 @@ s2k_status s2k_paths_bridge(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out
     }
     uint64_t total = 0;
     unsigned long long h[2] = {0, 0};
-    hipLaunchKernelGGL(bridge_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, p, g, ws, totals, bad);
-    c.launched();
-    c.scan(ws.h.tile_kept, nt, ws.h.tile_off, hw.scan_tmp(w));
-    c.fetch(&total, ws.h.tile_off + nt, 8);
-    c.fetch(h, totals, sizeof(h));
-    c.fetch(&hbad, bad, 4);
-    if (!c.sync()) return c.device_error();
+    if (!count_runs(c, ws.run, nt, runs.h.scan_tmp(w), [&] { hipLaunchKernelGGL(bridge_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, p, g, ws, totals, bad); },
+                    &total, totals, h, 2, bad, &hbad))
+        return c.device_error();
     if (hbad) return c.invalid(refusal);
     *n_out_steps = total;
     *n_merged = h[0];
@@ -377,9 +281,7 @@ s2k_status s2k_paths_bridge(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out
     const bool records = out->unitig || out->pos || out->count || out->item || out->flags || out->start || out->end || d_matched;
     if (records && total > out->capacity) return S2K_ERR_CAPACITY;
     if (d_join) c.copy(d_join, ws.join, n_steps, hipMemcpyDeviceToDevice);
-    hipLaunchKernelGGL(bridge_offsets_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, c.st, paths->path_off, n_reads, n_steps, nt, ws.h,
-                       out->path_off);
-    c.launched();
+    launch_run_offsets(c, paths->path_off, n_reads, n_steps, nt, ws.run, out->path_off);
     if (records) {
         if (d_matched) c.scan(paths->count, n_steps, ws.C, stmp(w));
         const BridgeOut io{out->unitig, out->pos, out->count, out->item, out->flags, out->start, out->end, d_matched};

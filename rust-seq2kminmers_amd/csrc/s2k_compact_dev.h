@@ -85,7 +85,7 @@ __device__ inline uint64_t kept_before(const CompactWs &ws, uint64_t n_items, ui
 }
 
 // the input index of kept item number s, which lies in a tile before tile b (one lane): the head of a run whose tail lies in tile b
-// (s2k_thread.hip, s2k_walk.hip)
+// (s2k_runs_dev.h)
 __device__ inline uint64_t head_item(const CompactWs &h, uint64_t b, uint64_t s) {
     uint64_t lo = 0, hi = b - 1; // the last tile whose first head is at or before s
     while (lo < hi) {

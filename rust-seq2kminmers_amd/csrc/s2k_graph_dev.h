@@ -1,5 +1,5 @@
 // s2k_graph_dev.h -- what the kernel families that walk oriented ids grid-stride share (s2k_unitig.hip, DESIGN.md §3.10;
-// s2k_simplify.hip, §3.12): the launch shape, the block sum behind their counters and the rule of a CSR row.
+// s2k_simplify.hip, §3.12): the launch shape, the block sum behind their counters, the rules of a CSR row and the search of one (also s2k_span_dev.h, s2k_untangle.hip).
 #pragma once
 #include <algorithm>
 
@@ -44,6 +44,35 @@ __device__ __forceinline__ bool csr_row_ok(const uint64_t *__restrict__ row_off,
                                            uint64_t *b) {
     *a = row_off[u], *b = row_off[u + 1];
     return !((u == 0 && *a != 0) || (u == n_ids - 1 && *b != n_edges) || *a > *b || *b > n_edges);
+}
+
+struct Csr {
+    const uint64_t *row_off;
+    const uint32_t *dst;
+};
+
+// the index of B in the row of A (strictly ascending), NONE if it is not there; both bounds are loaded before the first probe
+__device__ __forceinline__ uint32_t find_edge(const Csr &g, uint32_t A, uint32_t B) {
+    uint64_t lo = g.row_off[A], hi = g.row_off[A + 1];
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        const uint32_t v = g.dst[mid];
+        if (v < B) lo = mid + 1;
+        else if (v > B) hi = mid;
+        else return (uint32_t)mid;
+    }
+    return NONE;
+}
+
+// the CSR rules of s2k_graph_simplify_mask for row u
+__device__ __forceinline__ bool csr_ids_ok(const uint64_t *__restrict__ row_off, const uint32_t *__restrict__ dst, uint64_t u, uint64_t n_ids,
+                                           uint64_t n_edges) {
+    uint64_t a, b;
+    if (!csr_row_ok(row_off, u, n_ids, n_edges, &a, &b)) return false;
+    bool ok = true;
+    for (uint64_t e = a; e < b; e++)
+        if (dst[e] >= n_ids) ok = false;
+    return ok;
 }
 
 } // namespace

@@ -10,23 +10,19 @@
 //     flag word for all of it, read by the host before anything is written.
 //  3. places_write_kernel, one lane per outer member: its contig by a binary search of the outer uni_off, its record.
 //
-// s2k_paths_lift, the stable stream compaction of s2k_compact_dev.h with two masks over tiles of TB_TILE steps, as s2k_paths_bridge:
-//  1. lift_check_kernel: the path and CSR rules of bridge_check_kernel, the resolved bytes, copy_off against the rows, every copy
-//     record against its unitig.  One flag word, read by the host before anything is written.
+// s2k_paths_lift, runs of steps (s2k_runs_dev.h), tiles of TB_TILE steps:
+//  1. lift_check_kernel: the shared rules of s2k_span_dev.h (path_off_ok, steps_ok, unitig_row_ok), the resolved bytes, copy_off against
+//     the rows, every copy record against its unitig.  One flag word, read by the host before anything is written.
 //  2. lift_count_kernel: follow_tile (s2k_span_dev.h) gives the edge every step of the tile follows and that of the step behind the
 //     tile, which is the leaving edge of the tile's last step.  One lane per step picks the copy (one search of one row for tw(e), only
 //     on an even strand of a resolved unitig) and maps the position; V, q' and count go to LDS.  One lane does the same for the step
 //     before the tile, whose entering edge takes the one search that follow_tile has not made, and one lane for the step behind it,
-//     whose entering edge alone matters.  join from the neighbour in LDS; kept steps, heads (kept, join == 0) and tails (kept, the
-//     step behind it not joined): ballots per 64 steps, tile_prefixes twice, and whether a run is open at the tile's first step.
-//     Merged, dropped and conflicts: a block sum.
-//  3. launch_scan_u32 over the heads per tile (tails before a tile = heads before it - open), over count and over matched_in: a run's
-//     sums are differences of two prefix entries.
-//  4. lift_offsets_kernel: out path_off[r] = heads before path_off[r].
-//  5. lift_write_kernel: output step s is the s-th head and the s-th tail, paired as in bridge_write_kernel (the heads' indices in LDS
-//     by slot; the one tail per tile whose head lies in an earlier tile finds it by head_item).  The tail's lane maps the head again
-//     from its copy; each array is staged in LDS and leaves with leave_run.  No lane walks a run.  lift_items_kernel, one lane per kept
-//     input step, adds its count to its contig: the only atomic on an output, an integer sum.
+//     whose entering edge alone matters.  join from the neighbour in LDS.  Heads: kept, join == 0; tails: kept, the step behind it not
+//     joined.  Merged, dropped and conflicts: a block sum.
+//  3. launch_scan_u32 over count and over matched_in: a run's sums are differences of two prefix entries.
+//  4. run_offsets_kernel: out path_off[r] = heads before path_off[r].
+//  5. lift_write_kernel: output step s is the s-th head and the s-th tail.  The tail's lane maps the head again from its copy.
+//     lift_items_kernel, one lane per kept input step, adds its count to its contig: the only atomic on an output, an integer sum.
 //
 // Workspace (the context's grow-only count workspace).  Copy places: 16 B per copy (piece length, piece offset, slot_of).  Lift: 21 B
 // per step (join 1, copy 4, the prefixes of count and of matched_in 8 each), and per mask 8 B + 4 B per 64 steps and 4 B + 8 B per tile.
@@ -34,10 +30,10 @@
 
 #include "../../include/s2k.h"
 #include "s2k_call.h"
-#include "s2k_compact_dev.h"
 #include "s2k_dev.h"
 #include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
+#include "s2k_runs_dev.h"
 #include "s2k_span_dev.h"
 #include "s2k_table_dev.h"
 
@@ -149,37 +145,22 @@ struct LiftIn {
 };
 
 struct LiftWs {
-    uint8_t *join;       // per step
-    uint32_t *copy;      // per step: its copy, S2K_NO_COPY when it is dropped
-    uint64_t *C, *M;     // n_steps + 1 each: the exclusive prefixes of count and of matched_in
-    uint32_t *tile_open; // per tile: 1 when its first step is joined to the step before it
-    CompactWs h, t;      // heads; tails (of the tails only wmask, wpre and tile_kept are used)
+    uint8_t *join;   // per step
+    uint32_t *copy;  // per step: its copy, S2K_NO_COPY when it is dropped
+    uint64_t *C, *M; // n_steps + 1 each: the exclusive prefixes of count and of matched_in
+    RunWs run;       // open: the tile's first step is joined to the step before it
 };
 
 __global__ __launch_bounds__(UT) void lift_check_kernel(LiftIn k, Csr g, uint64_t n_edges, uint32_t *__restrict__ bad) {
-    bool ok = true;
     const Paths &p = k.p;
     const uint64_t n_ids = 2 * k.n_unitigs;
     const uint64_t i0 = (uint64_t)blockIdx.x * UT + threadIdx.x, stride = (uint64_t)gridDim.x * UT;
-    for (uint64_t r = i0; r <= p.n_reads; r += stride) {
-        const uint64_t a = p.path_off[r];
-        if (r == 0 && a != 0) ok = false;
-        if (r == p.n_reads ? a != p.n_steps : a > p.path_off[r + 1]) ok = false;
-    }
-    for (uint64_t s = i0; s < p.n_steps; s += stride) {
-        const uint64_t U = p.unitig[s];
-        if (U >= n_ids) {
-            ok = false;
-            continue;
-        }
-        const uint64_t a = k.uni_off[U >> 1], b = k.uni_off[(U >> 1) + 1], c = p.count[s], q = p.pos[s];
-        if (a >= b || c == 0 || q >= b - a || (!k.circular[U >> 1] && q + c > b - a)) ok = false;
-    }
+    bool ok = path_off_ok(p.path_off, p.n_reads, p.n_steps, i0, stride);
+    if (!steps_ok(p.unitig, p.pos, p.count, p.n_steps, k.uni_off, k.circular, n_ids, i0, stride)) ok = false;
     for (uint64_t u = i0; u < n_ids; u += stride) {
-        if (!csr_ids_ok(g.row_off, g.dst, u, n_ids, n_edges)) ok = false;
+        if (!unitig_row_ok(g, k.uni_off, u, n_ids, n_edges)) ok = false;
         if (u & 1) continue;
         const uint64_t t = u >> 1, a = k.uni_off[t], b = k.uni_off[t + 1];
-        if (a >= b || b - a >= (1ull << 32)) ok = false;
         const uint8_t r = k.resolved[t];
         if (r > 1) ok = false;
         const uint64_t ca = k.copy_off[t], cb = k.copy_off[t + 1];
@@ -253,9 +234,8 @@ struct LiftLds {
 __global__ __launch_bounds__(TB_THREADS) void lift_count_kernel(LiftIn k, Csr g, LiftWs ws, unsigned long long *__restrict__ totals /* merged, dropped, conflicts */) {
     __shared__ FollowLds s;
     __shared__ LiftLds l;
-    __shared__ uint32_t wch[TB_WORDS], wct[TB_WORDS];
     const Paths &p = k.p;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     uint32_t U[TB_Q], ps[TB_Q], cnt[TB_Q], fl[TB_Q], e[TB_Q];
     uint64_t len[TB_Q];
@@ -320,33 +300,11 @@ __global__ __launch_bounds__(TB_THREADS) void lift_count_kernel(LiftIn k, Csr g,
         l.join[TB_TILE + 1] = goes_on(l.V[TB_TILE], l.Q[TB_TILE], l.cnt[TB_TILE], hV, hQ, rec.z, rec.w != 0);
     }
     __syncthreads();
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) {
-        const int i = r * TB_THREADS + tid + 1;
-        const bool kept = V[r] != LIFT_NONE; // never on a step past n_steps
-        const uint64_t mh = __ballot(kept && l.join[i] != 1), mt = __ballot(kept && l.join[i + 1] != 1);
-        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wch[r * 4 + wv] = (uint32_t)__popcll(mh);
-            wct[r * 4 + wv] = (uint32_t)__popcll(mt);
-            if (w0 < p.n_steps) {
-                ws.h.wmask[w0 >> 6] = mh;
-                ws.t.wmask[w0 >> 6] = mt;
-            }
-        }
-    }
-    if (tid == 0) ws.tile_open[blockIdx.x] = l.join[1] == 1;
-    __syncthreads();
-    tile_prefixes(wch, t0, p.n_steps, ws.h);
-    tile_prefixes(wct, t0, p.n_steps, ws.t);
+    auto kept = [&](int r) { return V[r] != LIFT_NONE; }; // never on a step past n_steps
+    run_count_end(
+        ws.run, t0, p.n_steps, [&](int r, int i) { return kept(r) && l.join[i] != 1; }, [&](int r, int i) { return kept(r) && l.join[i + 1] != 1; },
+        [&] { return l.join[1] == 1; });
     block_add(n, totals);
-}
-
-__global__ __launch_bounds__(256) void lift_offsets_kernel(const uint64_t *__restrict__ path_off, uint64_t n_reads, uint64_t n_steps, uint64_t n_tiles,
-                                                           CompactWs heads, uint64_t *__restrict__ out_off) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > n_reads) return;
-    out_off[r] = kept_before(heads, n_steps, n_tiles, path_off[r]);
 }
 
 struct LiftOut {
@@ -355,32 +313,19 @@ struct LiftOut {
 
 __global__ __launch_bounds__(TB_THREADS) void lift_write_kernel(LiftIn k, LiftOut io, LiftWs ws) {
     __shared__ uint4 stage4[(TB_TILE + 2 * STAGE_PAD) / 4]; // TB_TILE 32-bit elements, and a run's shift
-    __shared__ uint32_t shead[TB_TILE];                     // by head slot: the head's step, relative to the tile
-    __shared__ uint64_t sopen;
-    uint32_t *stage = (uint32_t *)stage4;
     const Paths &p = k.p;
     const int tid = threadIdx.x;
-    const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
-    const uint64_t hbase = ws.h.tile_off[blockIdx.x];
-    const uint32_t ttot = ws.t.tile_kept[blockIdx.x];
-    if (ttot == 0) return;
-    const uint32_t open = ws.tile_open[blockIdx.x];
-    const uint64_t tbase = hbase - open; // tails before the tile: every head before it has its tail but the open one
-    uint32_t hslot[TB_Q], tslot[TB_Q];
-    const uint32_t hkeep = tile_slots(ws.h, t0, p.n_steps, hslot), tkeep = tile_slots(ws.t, t0, p.n_steps, tslot);
-    if (tid == 64 && open) sopen = head_item(ws.h, blockIdx.x, tbase);
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++)
-        if ((hkeep >> r) & 1u) shead[hslot[r]] = (uint32_t)(r * TB_THREADS + tid);
-    __syncthreads();
+    RunTile rt;
+    if (!run_tile(ws.run, p.n_steps, rt)) return;
+    const uint64_t t0 = rt.t0;
     uint64_t hd[TB_Q];
     uint32_t oV[TB_Q], opos[TB_Q], ocnt[TB_Q], omat[TB_Q];
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) {
         hd[r] = 0, oV[r] = opos[r] = ocnt[r] = omat[r] = 0;
-        if ((tkeep >> r) & 1u) {
+        if ((rt.tkeep >> r) & 1u) {
             const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
-            const uint64_t h = tslot[r] >= open ? t0 + shead[tslot[r] - open] : sopen;
+            const uint64_t h = rt.head_of(r);
             const uint32_t Uh = p.unitig[h];
             hd[r] = h;
             map_step(k.place[ws.copy[h]], Uh, p.pos[h], (uint32_t)(k.uni_off[(Uh >> 1) + 1] - k.uni_off[Uh >> 1]), &oV[r], &opos[r]);
@@ -388,28 +333,14 @@ __global__ __launch_bounds__(TB_THREADS) void lift_write_kernel(LiftIn k, LiftOu
             omat[r] = io.matched && k.matched_in ? (uint32_t)(ws.M[j + 1] - ws.M[h]) : ocnt[r]; // M is scanned only when both are given
         }
     }
-#define LF_LEAVE(OUT, VAL)                                                                  \
-    do {                                                                                    \
-        if (OUT) {                                                                          \
-            const uint32_t sh = shift_of(OUT + tbase);                                      \
-            _Pragma("unroll") for (int r = 0; r < TB_Q; r++) if ((tkeep >> r) & 1u) {       \
-                const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;                     \
-                (void)j;                                                                    \
-                stage[sh + tslot[r]] = (VAL);                                               \
-            }                                                                               \
-            __syncthreads();                                                                \
-            leave_run(OUT + tbase, stage, sh, ttot);                                        \
-        }                                                                                   \
-    } while (0)
-    LF_LEAVE(io.unitig, oV[r]);
-    LF_LEAVE(io.pos, opos[r]);
-    LF_LEAVE(io.count, ocnt[r]);
-    LF_LEAVE(io.item, k.item[hd[r]]);
-    LF_LEAVE(io.flags, p.flags[hd[r]]);
-    LF_LEAVE(io.start, k.start[hd[r]]);
-    LF_LEAVE(io.end, k.end[j]);
-    LF_LEAVE(io.matched, omat[r]);
-#undef LF_LEAVE
+    rt.leave_tails(io.unitig, stage4, [&](int r, uint64_t) { return oV[r]; });
+    rt.leave_tails(io.pos, stage4, [&](int r, uint64_t) { return opos[r]; });
+    rt.leave_tails(io.count, stage4, [&](int r, uint64_t) { return ocnt[r]; });
+    rt.leave_tails(io.item, stage4, [&](int r, uint64_t) { return k.item[hd[r]]; });
+    rt.leave_tails(io.flags, stage4, [&](int r, uint64_t) { return p.flags[hd[r]]; });
+    rt.leave_tails(io.start, stage4, [&](int r, uint64_t) { return k.start[hd[r]]; });
+    rt.leave_tails(io.end, stage4, [&](int, uint64_t j) { return k.end[j]; });
+    rt.leave_tails(io.matched, stage4, [&](int r, uint64_t) { return omat[r]; });
 }
 
 // contig_items[V >> 1] += count of every kept step: the steps of a run lie on one contig, so the sums are those over the output steps
@@ -479,8 +410,8 @@ s2k_status s2k_paths_lift(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *
     if (n_merged) *n_merged = 0;
     if (n_dropped) *n_dropped = 0;
     if (n_conflicts) *n_conflicts = 0;
-    if (!ctx || !paths || !out || !n_out_steps || !n_merged || !n_dropped || !n_conflicts || !paths->path_off || !out->path_off) return S2K_ERR_INVALID_ARG;
-    if (n_steps && (!paths->unitig || !paths->pos || !paths->count || !paths->item || !paths->flags)) return S2K_ERR_INVALID_ARG;
+    if (!ctx || !out || !n_out_steps || !n_merged || !n_dropped || !n_conflicts || !paths_given(paths, n_steps, true) || !out->path_off)
+        return S2K_ERR_INVALID_ARG;
     if (n_steps && ((out->start && !paths->start) || (out->end && !paths->end))) return S2K_ERR_INVALID_ARG;
     Call c(ctx, "s2k_paths_lift");
     if (n_unitigs >= (1ull << 31) || n_edges >= (1ull << 32) || n_copies >= (1ull << 31))
@@ -500,14 +431,13 @@ s2k_status s2k_paths_lift(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *
     const auto C = L.take<uint64_t>(n_steps + 1);
     const auto M = L.take<uint64_t>(n_steps + 1);
     const auto stmp = L.bytes<uint64_t>(scan_tmp_bytes(n_steps));
-    const auto topen = L.take<uint32_t>(nt);
-    const auto hw = carve(L, n_steps, nt), tw = carve(L, n_steps, nt);
+    const auto runs = carve_runs(L, n_steps, nt);
     char *w = L.alloc(ctx);
     if (!w) return c.nomem();
     unsigned long long *totals = words(w);
     uint32_t *bad = (uint32_t *)(totals + 3);
-    const LiftWs ws{join(w), copy(w), C(w), M(w), topen(w), hw(w), tw(w)};
-    const LiftIn k{Paths{paths->path_off, paths->unitig, paths->pos, paths->count, paths->flags, n_reads, n_steps},
+    const LiftWs ws{join(w), copy(w), C(w), M(w), runs(w)};
+    const LiftIn k{paths_of(paths, n_reads, n_steps),
                    paths->item,
                    paths->start,
                    paths->end,
@@ -538,12 +468,9 @@ s2k_status s2k_paths_lift(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *
     }
     uint64_t total = 0;
     unsigned long long h[3] = {0, 0, 0};
-    hipLaunchKernelGGL(lift_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, k, g, ws, totals);
-    c.launched();
-    c.scan(ws.h.tile_kept, nt, ws.h.tile_off, hw.scan_tmp(w));
-    c.fetch(&total, ws.h.tile_off + nt, 8);
-    c.fetch(h, totals, sizeof(h));
-    if (!c.sync()) return c.device_error();
+    if (!count_runs(c, ws.run, nt, runs.h.scan_tmp(w), [&] { hipLaunchKernelGGL(lift_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, k, g, ws, totals); },
+                    &total, totals, h, 3))
+        return c.device_error();
     *n_out_steps = total;
     *n_merged = h[0];
     *n_dropped = h[1];
@@ -552,11 +479,7 @@ s2k_status s2k_paths_lift(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out *
     if (records && total > out->capacity) return S2K_ERR_CAPACITY;
     if (d_join) c.copy(d_join, ws.join, n_steps, hipMemcpyDeviceToDevice);
     if (d_step_copy) c.copy(d_step_copy, ws.copy, n_steps * 4, hipMemcpyDeviceToDevice);
-    if (c.ok()) {
-        hipLaunchKernelGGL(lift_offsets_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, c.st, paths->path_off, n_reads, n_steps, nt, ws.h,
-                           out->path_off);
-        c.launched();
-    }
+    if (c.ok()) launch_run_offsets(c, paths->path_off, n_reads, n_steps, nt, ws.run, out->path_off);
     if (records && total) {
         c.scan(paths->count, n_steps, ws.C, stmp(w));
         if (d_matched && d_matched_in) c.scan(d_matched_in, n_steps, ws.M, stmp(w));

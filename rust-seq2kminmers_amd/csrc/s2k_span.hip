@@ -4,8 +4,8 @@
 //
 // s2k_paths_spans, the stable stream compaction of s2k_compact_dev.h over the steps, tiles of TB_TILE steps (lane tid holds steps
 // r * 256 + tid):
-//  1. spans_check_kernel: path_off starts at 0, does not decrease and ends at n_steps; every step's unitig < 2 T; the CSR rules of
-//     simplify_check_kernel; uni_off strictly ascending.  One flag word, read by the host before anything is written; every read is
+//  1. spans_check_kernel: path_off_ok (s2k_span_dev.h); every step's unitig < 2 T; the CSR rules of simplify_check_kernel; uni_off
+//     strictly ascending.  One flag word, read by the host before anything is written; every read is
 //     clamped to the arrays whatever they hold.
 //  2. spans_count_kernel (follow_tile of s2k_span_dev.h, shared with the walks of s2k_walk.hip): per step its unitig, "ends at its unitig's last member" and "starts a read" to LDS, with one halo step on
 //     either side; the read starts in [t0, t0 + TB_TILE] are marked from the reads a binary search of path_off finds there.  The edge a
@@ -51,14 +51,9 @@ struct SpanWs {
 
 __global__ __launch_bounds__(UT) void spans_check_kernel(Paths p, Csr g, const uint64_t *__restrict__ uni_off, uint64_t n_ids, uint64_t n_edges,
                                                          uint32_t *__restrict__ bad) {
-    bool ok = true;
     const uint64_t i0 = (uint64_t)blockIdx.x * UT + threadIdx.x, stride = (uint64_t)gridDim.x * UT;
-    for (uint64_t r = i0; r <= p.n_reads; r += stride) {
-        const uint64_t a = p.path_off[r];
-        if (r == 0 && a != 0) ok = false;
-        if (r == p.n_reads ? a != p.n_steps : a > p.path_off[r + 1]) ok = false;
-    }
-    for (uint64_t s = i0; s < p.n_steps; s += stride)
+    bool ok = path_off_ok(p.path_off, p.n_reads, p.n_steps, i0, stride);
+    for (uint64_t s = i0; s < p.n_steps; s += stride) // of a step only its unitig: less than steps_ok asks
         if (p.unitig[s] >= n_ids) ok = false;
     for (uint64_t u = i0; u < n_ids; u += stride) {
         if (!(u & 1) && uni_off[u >> 1] >= uni_off[(u >> 1) + 1]) ok = false;
@@ -239,8 +234,7 @@ s2k_status s2k_paths_spans(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out 
     if (n_keys) *n_keys = 0;
     if (n_followed) *n_followed = 0;
     if (n_off_graph) *n_off_graph = 0;
-    if (!ctx || !paths || !n_keys || !n_followed || !n_off_graph || !paths->path_off) return S2K_ERR_INVALID_ARG;
-    if (n_steps && (!paths->unitig || !paths->pos || !paths->count || !paths->flags)) return S2K_ERR_INVALID_ARG;
+    if (!ctx || !n_keys || !n_followed || !n_off_graph || !paths_given(paths, n_steps, false)) return S2K_ERR_INVALID_ARG;
     Call c(ctx, "s2k_paths_spans");
     if (n_unitigs >= (1ull << 31) || n_edges >= (1ull << 32))
         return c.invalid("2^31 unitigs or more (oriented ids are 32-bit), or 2^32 edges or more (a span key holds two edge indices)");
@@ -258,7 +252,7 @@ s2k_status s2k_paths_spans(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out 
     unsigned long long *totals = words(w);
     uint32_t *bad = (uint32_t *)(totals + 2);
     const SpanWs ws{edge(w), cw(w)};
-    const Paths p{paths->path_off, paths->unitig, paths->pos, paths->count, paths->flags, n_reads, n_steps};
+    const Paths p = paths_of(paths, n_reads, n_steps);
     const Csr g{d_row_off, d_dst};
     const uint64_t n_ids = 2 * n_unitigs;
     const uint32_t hbad = c.check(totals, 32, bad, [&] {

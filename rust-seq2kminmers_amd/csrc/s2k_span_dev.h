@@ -1,5 +1,6 @@
 // s2k_span_dev.h -- which edge of the CSR over the oriented unitigs every step of a read path follows (include/s2k.h, "Step s follows
-// edge e"): what the spans (s2k_span.hip) and the walks (s2k_walk.hip, §3.16) share.  One tile of TB_TILE steps per
+// edge e"): what the spans (s2k_span.hip), the walks (s2k_walk.hip, §3.16) and the lift (s2k_lift.hip, §3.18) share, and the rules that the
+// check kernels of every read-path call have in common.  One tile of TB_TILE steps per
 // workgroup, lane tid holds steps r * TB_THREADS + tid.
 #pragma once
 #include <algorithm>
@@ -12,42 +13,85 @@
 namespace s2k {
 namespace {
 
-constexpr uint32_t SP_NONE = 0xFFFFFFFFu; // no edge (n_edges < 2^32: an index stays below it)
-
-struct Csr {
-    const uint64_t *row_off;
-    const uint32_t *dst;
-};
-
-// the index of B in the row of A (strictly ascending), SP_NONE if it is not there
-__device__ __forceinline__ uint32_t find_edge(const Csr &g, uint32_t A, uint32_t B) {
-    uint64_t lo = g.row_off[A], hi = g.row_off[A + 1];
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        const uint32_t v = g.dst[mid];
-        if (v < B) lo = mid + 1;
-        else if (v > B) hi = mid;
-        else return (uint32_t)mid;
-    }
-    return SP_NONE;
-}
-
-// the CSR rules of s2k_graph_simplify_mask for row u
-__device__ __forceinline__ bool csr_ids_ok(const uint64_t *__restrict__ row_off, const uint32_t *__restrict__ dst, uint64_t u, uint64_t n_ids,
-                                           uint64_t n_edges) {
-    uint64_t a, b;
-    if (!csr_row_ok(row_off, u, n_ids, n_edges, &a, &b)) return false;
-    bool ok = true;
-    for (uint64_t e = a; e < b; e++)
-        if (dst[e] >= n_ids) ok = false;
-    return ok;
-}
+constexpr uint32_t SP_NONE = NONE; // no edge (n_edges < 2^32: an index stays below it)
 
 struct Paths {
     const uint64_t *path_off;
     const uint32_t *unitig, *pos, *count, *flags;
     uint64_t n_reads, n_steps;
 };
+
+// host: a read-path input is all there: path_off, and the step arrays every call reads (item: also item) when there are steps
+inline bool paths_given(const s2k_thread_out *paths, uint64_t n_steps, bool item) {
+    if (!paths || !paths->path_off) return false;
+    return !n_steps || (paths->unitig && paths->pos && paths->count && paths->flags && (!item || paths->item));
+}
+inline Paths paths_of(const s2k_thread_out *paths, uint64_t n_reads, uint64_t n_steps) {
+    return Paths{paths->path_off, paths->unitig, paths->pos, paths->count, paths->flags, n_reads, n_steps};
+}
+
+// ---- what the check kernels of the read-path calls share: every read is clamped to the arrays whatever they hold -------------------
+// path_off runs from 0 to n_steps without decreasing (the reads i0, i0 + stride, ..)
+__device__ __forceinline__ bool path_off_ok(const uint64_t *__restrict__ path_off, uint64_t n_reads, uint64_t n_steps, uint64_t i0, uint64_t stride) {
+    bool ok = true;
+    for (uint64_t r = i0; r <= n_reads; r += stride) {
+        const uint64_t a = path_off[r];
+        if (r == 0 && a != 0) ok = false;
+        if (r == n_reads ? a != n_steps : a > path_off[r + 1]) ok = false;
+    }
+    return ok;
+}
+
+// every step (i0, i0 + stride, ..) lies on a unitig below n_ids, has items and lies inside its unitig (it may run round a circular one)
+__device__ __forceinline__ bool steps_ok(const uint32_t *__restrict__ unitig, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ count,
+                                         uint64_t n_steps, const uint64_t *__restrict__ uni_off, const uint8_t *__restrict__ circular, uint64_t n_ids,
+                                         uint64_t i0, uint64_t stride) {
+    bool ok = true;
+    for (uint64_t s = i0; s < n_steps; s += stride) {
+        const uint64_t U = unitig[s];
+        if (U >= n_ids) {
+            ok = false;
+            continue;
+        }
+        const uint64_t a = uni_off[U >> 1], b = uni_off[(U >> 1) + 1], c = count[s], q = pos[s];
+        if (a >= b || c == 0 || q >= b - a || (!circular[U >> 1] && q + c > b - a)) ok = false;
+    }
+    return ok;
+}
+
+// row u is a CSR row with ids below n_ids; for an even u, uni_off ascends at its unitig, which has fewer than 2^32 members
+__device__ __forceinline__ bool unitig_row_ok(const Csr &g, const uint64_t *__restrict__ uni_off, uint64_t u, uint64_t n_ids, uint64_t n_edges) {
+    bool ok = csr_ids_ok(g.row_off, g.dst, u, n_ids, n_edges);
+    if (!(u & 1)) {
+        const uint64_t a = uni_off[u >> 1], b = uni_off[(u >> 1) + 1];
+        if (a >= b || b - a >= (1ull << 32)) ok = false;
+    }
+    return ok;
+}
+
+// ---- the edge a step follows ----------------------------------------------------------------------------------------------------------
+// TB_Q binary searches side by side: B[r] in dst[lo[r] .. hi[r]) (strictly ascending; an empty range: no search); found(r, index)
+template <typename F>
+__device__ __forceinline__ void search_rows(const Csr &g, uint64_t (&lo)[TB_Q], uint64_t (&hi)[TB_Q], const uint32_t (&B)[TB_Q], F found) {
+    for (;;) {
+        bool more = false;
+#pragma unroll
+        for (int r = 0; r < TB_Q; r++) {
+            if (lo[r] < hi[r]) {
+                const uint64_t mid = (lo[r] + hi[r]) >> 1;
+                const uint32_t v = g.dst[mid];
+                if (v < B[r]) lo[r] = mid + 1;
+                else if (v > B[r]) hi[r] = mid;
+                else {
+                    found(r, mid);
+                    lo[r] = hi[r];
+                }
+                more |= lo[r] < hi[r];
+            }
+        }
+        if (!more) break;
+    }
+}
 
 constexpr uint8_t SF_ATEND = 1, SF_SELF = 2; // the step ends at its unitig's last member; it is linked and begins at position 0
 
@@ -116,24 +160,7 @@ __device__ __forceinline__ void follow_tile(const Paths &p, const Csr &g, const 
         hi[r] = m ? g.row_off[A + 1] : lo[r];
         e[r] = SP_NONE;
     }
-    for (;;) { // TB_Q searches side by side
-        bool more = false;
-#pragma unroll
-        for (int r = 0; r < TB_Q; r++) {
-            if (lo[r] < hi[r]) {
-                const uint64_t mid = (lo[r] + hi[r]) >> 1;
-                const uint32_t v = g.dst[mid], B = U[r];
-                if (v < B) lo[r] = mid + 1;
-                else if (v > B) hi[r] = mid;
-                else {
-                    e[r] = (uint32_t)mid;
-                    lo[r] = hi[r];
-                }
-                more |= lo[r] < hi[r];
-            }
-        }
-        if (!more) break;
-    }
+    search_rows(g, lo, hi, U, [&](int r, uint64_t mid) { e[r] = (uint32_t)mid; });
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) s.E[r * TB_THREADS + tid + 1] = e[r];
     if (tid == 0 && may_follow(TB_TILE + 1)) s.E[TB_TILE + 1] = find_edge(g, s.U[TB_TILE], s.U[TB_TILE + 1]); // the step after the tile

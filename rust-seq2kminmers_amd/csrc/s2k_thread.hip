@@ -5,31 +5,26 @@
 // members[uni_off[t] + pos] >> 1 == i; one flag word, read by the host before anything is written, every read clamped to the arrays
 // whatever they hold), then places_write_kernel (one 16-byte store per node).
 //
-// s2k_table_thread, the stable stream compaction of s2k_compact_dev.h with two masks, tiles of TB_TILE items (lane tid holds items
-// r * 256 + tid):
+// s2k_table_thread, runs of items (s2k_runs_dev.h: the two masks, the scan, the offsets, the pairing of tails with heads and the
+// staged writes are there), tiles of TB_TILE items (lane tid holds items r * 256 + tid):
 //  1. thread_count_kernel: the look-up with ranks fused in, one 16-byte gather of the place record per item, (U, q) per item to
 //     workspace (8 B).  The tile's items and one halo item on either side (the item before the tile by lane 64, the one after it by
 //     lane 0, looked up once more) go to LDS; the read starts in [t0, t0 + TB_TILE] are marked from the reads a binary search of
-//     km_off finds there.  Two ballots per 64 items: heads (solid, does not continue its predecessor) and tails (solid, its successor
-//     does not continue it); per word the heads / tails before it inside the tile, per tile both totals and whether a step is open
-//     at the tile's first item.  A record that names a unitig >= n_unitigs or a position outside it sets the flag word.
-//  2. launch_scan_u32 over the heads per tile.  Tails before a tile = heads before it - open: no second scan.
-//  3. thread_offsets_kernel: path_off[r] = heads before km_off[r].
-//  4. thread_write_kernel (when step arrays are wanted and fit, or d_uni_items is given): step s is the s-th head and the s-th tail.
-//     The heads' tile-relative item indices go to LDS at their slots; a tail at tile-relative slot k finds its head at slot k - open
-//     there, and the one tail per tile whose head lies in an earlier tile finds it by a search of tile_off, the tile's 32 word
-//     prefixes and one mask (one lane; nothing walks a step).  unitig, pos, item, flags and start come from the head, count and end
-//     from the tail; each array is staged in LDS and leaves with leave_run (16-byte pieces where the run allows).  One integer
-//     atomic per step adds count to d_uni_items.
+//     km_off finds there.  Heads: solid, does not continue its predecessor; tails: solid, its successor does not continue it.  A
+//     record that names a unitig >= n_unitigs or a position outside it sets the flag word.
+//  2. run_offsets_kernel: path_off[r] = heads before km_off[r].
+//  3. thread_write_kernel (when step arrays are wanted and fit, or d_uni_items is given): step s is the s-th head and the s-th tail.
+//     unitig, pos, item, flags and start come from the head, count and end from the tail.  One integer atomic per step adds count
+//     to d_uni_items.
 //
 // Workspace (the context's grow-only count workspace): 8 B per item, and per mask 8 B + 4 B per 64 items and 4 B + 8 B per tile.
 #include <algorithm>
 
 #include "../../include/s2k.h"
 #include "s2k_call.h"
-#include "s2k_compact_dev.h"
 #include "s2k_dev.h"
 #include "s2k_hostcopy.h"
+#include "s2k_runs_dev.h"
 #include "s2k_table_dev.h"
 
 namespace s2k {
@@ -72,9 +67,8 @@ __global__ __launch_bounds__(256) void places_write_kernel(Unitigs g, s2k_node_p
 constexpr uint32_t TH_NONE = 0xFFFFFFFFu; // U of an item that is not solid (an oriented unitig stays below 2^32 - 2: < 2^31 nodes)
 
 struct ThreadWs {
-    uint2 *uq;           // per item: (U, q), U == TH_NONE when it is not solid
-    uint32_t *tile_open; // per tile: 1 when its first item continues the item before it
-    CompactWs h, t;      // heads; tails (of the tails only wmask, wpre and tile_kept are used)
+    uint2 *uq; // per item: (U, q), U == TH_NONE when it is not solid
+    RunWs run;
 };
 
 struct Item { // what the step rule reads of one item
@@ -100,9 +94,8 @@ __global__ __launch_bounds__(TB_THREADS) void thread_count_kernel(TableView tv, 
     // index x + 1 <-> item t0 + x: index 0 is the item before the tile, index TB_TILE + 1 the one after it
     __shared__ uint32_t sU[TB_TILE + 2], sq[TB_TILE + 2];
     __shared__ uint8_t swrap[TB_TILE + 2], sstart[TB_TILE + 2]; // sstart: the item starts a read
-    __shared__ uint32_t wch[TB_WORDS], wct[TB_WORDS];
     __shared__ uint64_t sreads[2];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     uint64_t q[TB_Q];
     uint32_t c[TB_Q], pos[TB_Q];
@@ -161,32 +154,10 @@ __global__ __launch_bounds__(TB_THREADS) void thread_count_kernel(TableView tv, 
         const uint32_t a = sU[i - 1], b = sU[i];
         return a != TH_NONE && b == a && !sstart[i] && (sq[i] == sq[i - 1] + 1u || (swrap[i - 1] && sq[i] == 0u));
     };
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) {
-        const int i = r * TB_THREADS + tid + 1;
-        const bool solid = sU[i] != TH_NONE;
-        const uint64_t mh = __ballot(solid && !continues(i)), mt = __ballot(solid && !continues(i + 1));
-        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wch[r * 4 + wv] = (uint32_t)__popcll(mh);
-            wct[r * 4 + wv] = (uint32_t)__popcll(mt);
-            if (w0 < n_items) {
-                ws.h.wmask[w0 >> 6] = mh;
-                ws.t.wmask[w0 >> 6] = mt;
-            }
-        }
-    }
-    if (tid == 0) ws.tile_open[blockIdx.x] = continues(1);
-    __syncthreads();
-    tile_prefixes(wch, t0, n_items, ws.h);
-    tile_prefixes(wct, t0, n_items, ws.t);
-}
-
-__global__ __launch_bounds__(256) void thread_offsets_kernel(const uint64_t *__restrict__ km_off, uint64_t n_reads, uint64_t n_items, uint64_t n_tiles,
-                                                             CompactWs heads, uint64_t *__restrict__ path_off) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > n_reads) return;
-    path_off[r] = kept_before(heads, n_items, n_tiles, km_off[r]);
+    auto solid = [&](int i) { return sU[i] != TH_NONE; };
+    run_count_end(
+        ws.run, t0, n_items, [&](int, int i) { return solid(i) && !continues(i); }, [&](int, int i) { return solid(i) && !continues(i + 1); },
+        [&] { return continues(1); });
 }
 
 struct ThreadIo {
@@ -199,71 +170,48 @@ struct ThreadIo {
 
 __global__ __launch_bounds__(TB_THREADS) void thread_write_kernel(ThreadIo io, uint64_t n_items, ThreadWs ws) {
     __shared__ uint4 stage4[TB_TILE / 4 + 1]; // a run of 32-bit elements starts at most 3 elements into its first 16-byte piece
-    __shared__ uint32_t shead[TB_TILE];       // by head slot: the head's item, relative to the tile
-    __shared__ uint64_t sread[2], sopen;
-    uint32_t *stage = (uint32_t *)stage4;
+    __shared__ uint64_t sread[2];
     const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE, t1 = std::min<uint64_t>(t0 + TB_TILE, n_items);
-    const uint64_t hbase = ws.h.tile_off[blockIdx.x];
-    const uint32_t htot = (uint32_t)(ws.h.tile_off[blockIdx.x + 1] - hbase), ttot = ws.t.tile_kept[blockIdx.x];
-    if (htot == 0 && ttot == 0) return;
-    const uint32_t open = ws.tile_open[blockIdx.x];
-    const uint64_t tbase = hbase - open; // tails before the tile: every head before it has its tail but the open one
-    uint32_t hslot[TB_Q], tslot[TB_Q];
-    const uint32_t hkeep = tile_slots(ws.h, t0, n_items, hslot), tkeep = tile_slots(ws.t, t0, n_items, tslot);
-    if (tid < 2 && (io.o_item || io.o_flags)) // the reads that hold the tile's first and last item
-        sread[tid] = read_of(io.km_off, 0, io.n_reads - 1, tid == 0 ? t0 : t1 - 1);
-    if (tid == 64 && open && ttot) sopen = head_item(ws.h, blockIdx.x, tbase);
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++)
-        if ((hkeep >> r) & 1u) shead[hslot[r]] = (uint32_t)(r * TB_THREADS + tid);
-    __syncthreads();
-#define TH_LEAVE(OUT, KEEP, SLOT, BASE, TOT, VAL)                                           \
-    do {                                                                                    \
-        const uint32_t sh = shift_of(OUT + BASE);                                           \
-        _Pragma("unroll") for (int r = 0; r < TB_Q; r++) if ((KEEP >> r) & 1u) {            \
-            const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;                         \
-            (void)j;                                                                        \
-            stage[sh + SLOT[r]] = (VAL);                                                    \
-        }                                                                                   \
-        __syncthreads();                                                                    \
-        leave_run(OUT + BASE, stage, sh, TOT);                                              \
-    } while (0)
-    if (htot) {
-        if (io.o_unitig) TH_LEAVE(io.o_unitig, hkeep, hslot, hbase, htot, ws.uq[j].x);
-        if (io.o_pos) TH_LEAVE(io.o_pos, hkeep, hslot, hbase, htot, ws.uq[j].y);
-        if (io.o_start) TH_LEAVE(io.o_start, hkeep, hslot, hbase, htot, io.start[j]);
+    RunTile rt;
+    if (!run_tile(ws.run, n_items, true, rt, [&] {
+            if (tid < 2 && (io.o_item || io.o_flags)) // the reads that hold the tile's first and last item
+                sread[tid] = read_of(io.km_off, 0, io.n_reads - 1, tid == 0 ? t0 : t1 - 1);
+        }))
+        return;
+    if (rt.htot) {
+        rt.leave_heads(io.o_unitig, stage4, [&](int, uint64_t j) { return ws.uq[j].x; });
+        rt.leave_heads(io.o_pos, stage4, [&](int, uint64_t j) { return ws.uq[j].y; });
+        rt.leave_heads(io.o_start, stage4, [&](int, uint64_t j) { return io.start[j]; });
         if (io.o_item || io.o_flags) {
             const uint64_t rlo = sread[0], rhi = sread[1];
             uint32_t item[TB_Q];
 #pragma unroll
             for (int r = 0; r < TB_Q; r++) {
                 const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
-                item[r] = (hkeep >> r) & 1u ? (uint32_t)(j - io.km_off[read_of(io.km_off, rlo, rhi, j)]) : 0u;
+                item[r] = (rt.hkeep >> r) & 1u ? (uint32_t)(j - io.km_off[read_of(io.km_off, rlo, rhi, j)]) : 0u;
             }
-            if (io.o_item) TH_LEAVE(io.o_item, hkeep, hslot, hbase, htot, item[r]);
+            rt.leave_heads(io.o_item, stage4, [&](int r, uint64_t) { return item[r]; });
             // linked: not its read's first item, and the item before it is solid
-            if (io.o_flags) TH_LEAVE(io.o_flags, hkeep, hslot, hbase, htot, item[r] && ws.uq[j - 1].x != TH_NONE ? S2K_STEP_LINKED : 0u);
+            rt.leave_heads(io.o_flags, stage4, [&](int r, uint64_t j) { return item[r] && ws.uq[j - 1].x != TH_NONE ? S2K_STEP_LINKED : 0u; });
         }
     }
-    if (ttot) {
-        if (io.o_end) TH_LEAVE(io.o_end, tkeep, tslot, tbase, ttot, io.end[j]);
+    if (rt.ttot) {
+        rt.leave_tails(io.o_end, stage4, [&](int, uint64_t j) { return io.end[j]; });
         if (io.o_count || io.uni_items) {
             uint32_t count[TB_Q];
 #pragma unroll
             for (int r = 0; r < TB_Q; r++) {
                 count[r] = 0;
-                if ((tkeep >> r) & 1u) {
+                if ((rt.tkeep >> r) & 1u) {
                     const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
-                    const uint64_t head = tslot[r] >= open ? t0 + shead[tslot[r] - open] : sopen;
-                    count[r] = (uint32_t)(j - head + 1);
+                    count[r] = (uint32_t)(j - rt.head_of(r) + 1);
                     if (io.uni_items) atomicAdd(io.uni_items + (ws.uq[j].x >> 1), (unsigned long long)count[r]);
                 }
             }
-            if (io.o_count) TH_LEAVE(io.o_count, tkeep, tslot, tbase, ttot, count[r]);
+            rt.leave_tails(io.o_count, stage4, [&](int r, uint64_t) { return count[r]; });
         }
     }
-#undef TH_LEAVE
 }
 
 } // namespace
@@ -321,11 +269,10 @@ s2k_status s2k_table_thread(s2k_table *t, uint64_t n_reads, const s2k_device_out
     Layout L;
     const auto flag = L.bytes<uint32_t>(64);
     const auto uq = L.take<uint2>(n_items);
-    const auto topen = L.take<uint32_t>(nt);
-    const auto hw = carve(L, n_items, nt), tw = carve(L, n_items, nt);
+    const auto runs = carve_runs(L, n_items, nt);
     char *w = L.alloc(t->ctx);
     if (!w) return c.nomem();
-    const ThreadWs ws{uq(w), topen(w), hw(w), tw(w)};
+    const ThreadWs ws{uq(w), runs(w)};
     uint32_t *bad = flag(w);
     const uint32_t minc = min_count ? min_count : 1u;
     uint64_t total = 0;
@@ -333,15 +280,13 @@ s2k_status s2k_table_thread(s2k_table *t, uint64_t n_reads, const s2k_device_out
         hipLaunchKernelGGL(thread_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, t->view(), in->km_off, n_reads, in->hash, in->rev,
                            n_items, minc, (const uint4 *)d_place, n_unitigs, ws, bad);
         c.launched();
-        c.scan(ws.h.tile_kept, nt, ws.h.tile_off, hw.scan_tmp(w));
-        c.fetch(&total, ws.h.tile_off + nt, 8);
+        c.scan(ws.run.h.tile_kept, nt, ws.run.h.tile_off, runs.h.scan_tmp(w));
+        c.fetch(&total, ws.run.h.tile_off + nt, 8);
     });
     if (!c.ok()) return c.device_error();
     if (hbad) return c.invalid("a place record that names a unitig >= n_unitigs or a position outside its unitig");
     *n_steps = total;
-    hipLaunchKernelGGL(thread_offsets_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, c.st, in->km_off, n_reads, n_items, nt, ws.h,
-                       out->path_off);
-    c.launched();
+    launch_run_offsets(c, in->km_off, n_reads, n_items, nt, ws.run, out->path_off);
     const bool want = out->unitig || out->pos || out->count || out->item || out->flags || out->start || out->end;
     const bool fits = total <= out->capacity;
     if (c.ok() && total && ((want && fits) || (d_uni_items && !want))) {

@@ -38,24 +38,6 @@
 namespace s2k {
 namespace {
 
-struct Csr {
-    const uint64_t *row_off;
-    const uint32_t *dst;
-};
-
-// the index of B in the row of A (strictly ascending), NONE if it is not there; both bounds are loaded before the first probe
-__device__ __forceinline__ uint32_t find_edge(const Csr &g, uint32_t A, uint32_t B) {
-    uint64_t lo = g.row_off[A], hi = g.row_off[A + 1];
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        const uint32_t v = g.dst[mid];
-        if (v < B) lo = mid + 1;
-        else if (v > B) hi = mid;
-        else return (uint32_t)mid;
-    }
-    return NONE;
-}
-
 // ---- the check: nothing here trusts what it reads ---------------------------------------------------------------------------------
 struct Unchecked {
     Csr g;

@@ -5,21 +5,17 @@
 // s2k_unitig_member_offsets: the stitch's piece-length, last-member, scan and offset passes (s2k_stitch_dev.h) without the copy
 // kernel; the scan's first n_nodes entries are the member offsets.
 //
-// s2k_paths_walks, the stable stream compaction of s2k_compact_dev.h with two masks, as s2k_table_thread, over tiles of TB_TILE steps
-// (lane tid holds steps r * 256 + tid):
-//  1. walks_check_kernel: the rules of spans_check_kernel; every step has count >= 1, pos < len, and pos + count <= len unless its
-//     unitig is circular; uni_off runs from 0 to n_nodes; out_off does not decrease and no unitig has 2^32 bases or more; every
-//     member < 2 n_nodes, its offset inside its unitig's bases (the unitig by a search of uni_off).  One flag word, read by the host
-//     before anything is written; every read is clamped to the arrays whatever they hold.
-//  2. walks_count_kernel: follow_tile (s2k_span_dev.h: the row searches of spans_count_kernel, side by side) gives the edge every
-//     step follows, to workspace and LDS.  Heads (the step follows no edge) and tails (the step after it follows none): two ballots
-//     per 64 steps, tile_prefixes twice, and whether a walk is open at the tile's first step.  Per step adv(U) to workspace.
-//  3. launch_scan_u32 over the heads per tile (tails before a tile = heads before it - open), over adv and over count: a walk's
-//     path_len, path_end and items are differences of two prefix entries.
-//  4. walks_offsets_kernel: walk_off[r] = heads before path_off[r].
-//  5. walks_write_kernel: walk s is the s-th head and the s-th tail, paired as in thread_write_kernel (heads' indices in LDS by slot;
-//     the one tail per tile whose head lies in an earlier tile finds it by head_item).  The tail's lane gathers the head's step, the
-//     two prefixes and the two base intervals; each array is staged in LDS and leaves with leave_run.  No lane walks a walk.
+// s2k_paths_walks, runs of steps (s2k_runs_dev.h), tiles of TB_TILE steps (lane tid holds steps r * 256 + tid):
+//  1. walks_check_kernel: the shared rules of s2k_span_dev.h (path_off_ok, steps_ok, unitig_row_ok); uni_off runs from 0 to n_nodes;
+//     out_off does not decrease and no unitig has 2^32 bases or more; every member < 2 n_nodes, its offset inside its unitig's bases
+//     (the unitig by a search of uni_off).  One flag word, read by the host before anything is written; every read is clamped to
+//     the arrays whatever they hold.
+//  2. walks_count_kernel: follow_tile (s2k_span_dev.h) gives the edge every step follows, to workspace and LDS.  Heads: the step
+//     follows no edge; tails: the step after it follows none.  Per step adv(U) to workspace.
+//  3. launch_scan_u32 over adv and over count: a walk's path_len, path_end and items are differences of two prefix entries.
+//  4. run_offsets_kernel: walk_off[r] = heads before path_off[r].
+//  5. walks_write_kernel: walk s is the s-th head and the s-th tail.  The tail's lane gathers the head's step, the two prefixes and
+//     the two base intervals.
 //
 // Workspace (the context's grow-only count workspace): member offsets 12 B per member; walks 24 B per step (edge 4, adv 4, two
 // prefixes 8 + 8), and per mask 8 B + 4 B per 64 steps and 4 B + 8 B per tile.
@@ -27,10 +23,10 @@
 
 #include "../../include/s2k.h"
 #include "s2k_call.h"
-#include "s2k_compact_dev.h"
 #include "s2k_dev.h"
 #include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
+#include "s2k_runs_dev.h"
 #include "s2k_span_dev.h"
 #include "s2k_stitch_dev.h"
 #include "s2k_table_dev.h"
@@ -49,8 +45,7 @@ struct Lift {
 struct WalkWs {
     uint32_t *edge, *adv; // per step: the edge it follows (SP_NONE: none); adv(unitig)
     uint64_t *A, *C;      // n_steps + 1: the exclusive prefixes of adv and of count
-    uint32_t *tile_open;  // per tile: 1 when its first step follows an edge
-    CompactWs h, t;       // heads; tails (of the tails only wmask, wpre and tile_kept are used)
+    RunWs run;            // open: the tile's first step follows an edge
 };
 
 // the last t in [0, n_unitigs - 1] with uni_off[t] <= x: every index stays inside uni_off whatever it holds
@@ -65,28 +60,15 @@ __device__ inline uint64_t unitig_of(const uint64_t *__restrict__ uni_off, uint6
 }
 
 __global__ __launch_bounds__(UT) void walks_check_kernel(Paths p, Csr g, Lift v, uint64_t n_edges, uint32_t *__restrict__ bad) {
-    bool ok = true;
     const uint64_t n_ids = 2 * v.n_unitigs;
     const uint64_t i0 = (uint64_t)blockIdx.x * UT + threadIdx.x, stride = (uint64_t)gridDim.x * UT;
-    for (uint64_t r = i0; r <= p.n_reads; r += stride) {
-        const uint64_t a = p.path_off[r];
-        if (r == 0 && a != 0) ok = false;
-        if (r == p.n_reads ? a != p.n_steps : a > p.path_off[r + 1]) ok = false;
-    }
-    for (uint64_t s = i0; s < p.n_steps; s += stride) {
-        const uint64_t U = p.unitig[s];
-        if (U >= n_ids) {
-            ok = false;
-            continue;
-        }
-        const uint64_t a = v.uni_off[U >> 1], b = v.uni_off[(U >> 1) + 1], c = p.count[s], q = p.pos[s];
-        if (a >= b || c == 0 || q >= b - a || (!v.circular[U >> 1] && q + c > b - a)) ok = false;
-    }
+    bool ok = path_off_ok(p.path_off, p.n_reads, p.n_steps, i0, stride);
+    if (!steps_ok(p.unitig, p.pos, p.count, p.n_steps, v.uni_off, v.circular, n_ids, i0, stride)) ok = false;
     for (uint64_t u = i0; u < n_ids; u += stride) {
-        if (!csr_ids_ok(g.row_off, g.dst, u, n_ids, n_edges)) ok = false;
+        if (!unitig_row_ok(g, v.uni_off, u, n_ids, n_edges)) ok = false;
         if (u & 1) continue;
         const uint64_t t = u >> 1, a = v.uni_off[t], b = v.uni_off[t + 1], oa = v.out_off[t], ob = v.out_off[t + 1];
-        if (a >= b || b > v.n_nodes || (t == 0 && a != 0) || (t == v.n_unitigs - 1 && b != v.n_nodes)) ok = false;
+        if (b > v.n_nodes || (t == 0 && a != 0) || (t == v.n_unitigs - 1 && b != v.n_nodes)) ok = false; // n_nodes < 2^31
         if (oa > ob || ob - oa >= (1ull << 32)) ok = false;
     }
     for (uint64_t x = i0; x < v.n_nodes; x += stride) {
@@ -100,8 +82,7 @@ __global__ __launch_bounds__(UT) void walks_check_kernel(Paths p, Csr g, Lift v,
 __global__ __launch_bounds__(TB_THREADS) void walks_count_kernel(Paths p, Csr g, Lift v, WalkWs ws,
                                                                  unsigned long long *__restrict__ totals /* followed, off-graph */) {
     __shared__ FollowLds s;
-    __shared__ uint32_t wch[TB_WORDS], wct[TB_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     uint32_t U[TB_Q], ps[TB_Q], cnt[TB_Q], fl[TB_Q], e[TB_Q];
     uint64_t len[TB_Q];
@@ -122,33 +103,11 @@ __global__ __launch_bounds__(TB_THREADS) void walks_count_kernel(Paths p, Csr g,
             n[1] += (fl[r] & S2K_STEP_LINKED) && e[r] == SP_NONE;
         }
     }
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++) {
-        const int i = r * TB_THREADS + tid + 1;
-        const bool valid = t0 + (i - 1) < p.n_steps;
-        const uint64_t mh = __ballot(valid && s.E[i] == SP_NONE), mt = __ballot(valid && s.E[i + 1] == SP_NONE);
-        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wch[r * 4 + wv] = (uint32_t)__popcll(mh);
-            wct[r * 4 + wv] = (uint32_t)__popcll(mt);
-            if (w0 < p.n_steps) {
-                ws.h.wmask[w0 >> 6] = mh;
-                ws.t.wmask[w0 >> 6] = mt;
-            }
-        }
-    }
-    if (tid == 0) ws.tile_open[blockIdx.x] = s.E[1] != SP_NONE;
-    __syncthreads();
-    tile_prefixes(wch, t0, p.n_steps, ws.h);
-    tile_prefixes(wct, t0, p.n_steps, ws.t);
+    auto valid = [&](int i) { return t0 + (i - 1) < p.n_steps; };
+    run_count_end(
+        ws.run, t0, p.n_steps, [&](int, int i) { return valid(i) && s.E[i] == SP_NONE; }, [&](int, int i) { return valid(i) && s.E[i + 1] == SP_NONE; },
+        [&] { return s.E[1] != SP_NONE; });
     block_add(n, totals);
-}
-
-__global__ __launch_bounds__(256) void walks_offsets_kernel(const uint64_t *__restrict__ path_off, uint64_t n_reads, uint64_t n_steps, uint64_t n_tiles,
-                                                            CompactWs heads, uint64_t *__restrict__ walk_off) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > n_reads) return;
-    walk_off[r] = kept_before(heads, n_steps, n_tiles, path_off[r]);
 }
 
 // The base interval [*lo, *hi) of position q of the oriented unitig U on its own strand (include/s2k.h, "Base interval of a
@@ -179,32 +138,18 @@ struct WalkIo {
 
 __global__ __launch_bounds__(TB_THREADS) void walks_write_kernel(Paths p, Lift v, WalkIo io, WalkWs ws) {
     __shared__ uint4 stage4[(TB_TILE + STAGE_PAD) / 2]; // TB_TILE 64-bit elements, and a run's shift
-    __shared__ uint32_t shead[TB_TILE];                 // by head slot: the head's step, relative to the tile
-    __shared__ uint64_t sopen;
-    uint64_t *stage8 = (uint64_t *)stage4;
-    uint32_t *stage = (uint32_t *)stage4;
     const int tid = threadIdx.x;
-    const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
-    const uint64_t hbase = ws.h.tile_off[blockIdx.x];
-    const uint32_t ttot = ws.t.tile_kept[blockIdx.x];
-    if (ttot == 0) return;
-    const uint32_t open = ws.tile_open[blockIdx.x];
-    const uint64_t tbase = hbase - open; // tails before the tile: every head before it has its tail but the open one
-    uint32_t hslot[TB_Q], tslot[TB_Q];
-    const uint32_t hkeep = tile_slots(ws.h, t0, p.n_steps, hslot), tkeep = tile_slots(ws.t, t0, p.n_steps, tslot);
-    if (tid == 64 && open) sopen = head_item(ws.h, blockIdx.x, tbase);
-#pragma unroll
-    for (int r = 0; r < TB_Q; r++)
-        if ((hkeep >> r) & 1u) shead[hslot[r]] = (uint32_t)(r * TB_THREADS + tid);
-    __syncthreads();
+    RunTile rt;
+    if (!run_tile(ws.run, p.n_steps, rt)) return;
+    const uint64_t t0 = rt.t0;
     uint64_t hd[TB_Q], pstart[TB_Q], pend[TB_Q], plen[TB_Q];
     uint32_t circ = 0;
 #pragma unroll
     for (int r = 0; r < TB_Q; r++) {
         hd[r] = pstart[r] = pend[r] = plen[r] = 0;
-        if ((tkeep >> r) & 1u) {
+        if ((rt.tkeep >> r) & 1u) {
             const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;
-            const uint64_t h = tslot[r] >= open ? t0 + shead[tslot[r] - open] : sopen;
+            const uint64_t h = rt.head_of(r);
             const uint32_t Uh = p.unitig[h], Uj = p.unitig[j];
             const uint64_t last = (uint64_t)p.pos[j] + p.count[j] - 1, lenj = v.uni_off[(Uj >> 1) + 1] - v.uni_off[Uj >> 1];
             const uint64_t dA = ws.A[j] - ws.A[h];
@@ -220,29 +165,15 @@ __global__ __launch_bounds__(TB_THREADS) void walks_write_kernel(Paths p, Lift v
             circ |= (v.circular[Uj >> 1] ? 1u : 0u) << r;
         }
     }
-#define WK_LEAVE(OUT, STAGE, VAL)                                                           \
-    do {                                                                                    \
-        if (OUT) {                                                                          \
-            const uint32_t sh = shift_of(OUT + tbase);                                      \
-            _Pragma("unroll") for (int r = 0; r < TB_Q; r++) if ((tkeep >> r) & 1u) {       \
-                const uint64_t j = t0 + (uint64_t)r * TB_THREADS + tid;                     \
-                (void)j;                                                                    \
-                STAGE[sh + tslot[r]] = (VAL);                                               \
-            }                                                                               \
-            __syncthreads();                                                                \
-            leave_run(OUT + tbase, STAGE, sh, ttot);                                        \
-        }                                                                                   \
-    } while (0)
-    WK_LEAVE(io.first_step, stage8, hd[r]);
-    WK_LEAVE(io.items, stage8, ws.C[j + 1] - ws.C[hd[r]]);
-    WK_LEAVE(io.path_len, stage8, plen[r]);
-    WK_LEAVE(io.path_start, stage8, pstart[r]);
-    WK_LEAVE(io.path_end, stage8, pend[r]);
-    WK_LEAVE(io.n_steps, stage, (uint32_t)(j - hd[r] + 1));
-    WK_LEAVE(io.qstart, stage, io.start[hd[r]]);
-    WK_LEAVE(io.qend, stage, io.end[j] + 1u);
-    WK_LEAVE(io.flags, stage, (circ >> r) & 1u);
-#undef WK_LEAVE
+    rt.leave_tails(io.first_step, stage4, [&](int r, uint64_t) { return hd[r]; });
+    rt.leave_tails(io.items, stage4, [&](int r, uint64_t j) { return ws.C[j + 1] - ws.C[hd[r]]; });
+    rt.leave_tails(io.path_len, stage4, [&](int r, uint64_t) { return plen[r]; });
+    rt.leave_tails(io.path_start, stage4, [&](int r, uint64_t) { return pstart[r]; });
+    rt.leave_tails(io.path_end, stage4, [&](int r, uint64_t) { return pend[r]; });
+    rt.leave_tails(io.n_steps, stage4, [&](int r, uint64_t j) { return j - hd[r] + 1; });
+    rt.leave_tails(io.qstart, stage4, [&](int r, uint64_t) { return io.start[hd[r]]; });
+    rt.leave_tails(io.qend, stage4, [&](int, uint64_t j) { return io.end[j] + 1u; });
+    rt.leave_tails(io.flags, stage4, [&](int r, uint64_t) { return (circ >> r) & 1u; });
 }
 
 } // namespace
@@ -308,8 +239,7 @@ s2k_status s2k_paths_walks(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out 
     if (n_walks) *n_walks = 0;
     if (n_followed) *n_followed = 0;
     if (n_off_graph) *n_off_graph = 0;
-    if (!ctx || !paths || !n_walks || !n_followed || !n_off_graph || !paths->path_off) return S2K_ERR_INVALID_ARG;
-    if (n_steps && (!paths->unitig || !paths->pos || !paths->count || !paths->flags)) return S2K_ERR_INVALID_ARG;
+    if (!ctx || !n_walks || !n_followed || !n_off_graph || !paths_given(paths, n_steps, false)) return S2K_ERR_INVALID_ARG;
     if (out && n_steps && ((out->qstart && !paths->start) || (out->qend && !paths->end))) return S2K_ERR_INVALID_ARG;
     Call c(ctx, "s2k_paths_walks");
     if (n_unitigs >= (1ull << 31) || n_edges >= (1ull << 32))
@@ -326,14 +256,13 @@ s2k_status s2k_paths_walks(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out 
     const auto edge = L.take<uint32_t>(n_steps), adv = L.take<uint32_t>(n_steps);
     const auto A = L.take<uint64_t>(n_steps + 1), C = L.take<uint64_t>(n_steps + 1);
     const auto stmp = L.bytes<uint64_t>(scan_tmp_bytes(n_steps));
-    const auto topen = L.take<uint32_t>(nt);
-    const auto hw = carve(L, n_steps, nt), tw = carve(L, n_steps, nt);
+    const auto runs = carve_runs(L, n_steps, nt);
     char *w = L.alloc(ctx);
     if (!w) return c.nomem();
     unsigned long long *totals = words(w);
     uint32_t *bad = (uint32_t *)(totals + 2);
-    const WalkWs ws{edge(w), adv(w), A(w), C(w), topen(w), hw(w), tw(w)};
-    const Paths p{paths->path_off, paths->unitig, paths->pos, paths->count, paths->flags, n_reads, n_steps};
+    const WalkWs ws{edge(w), adv(w), A(w), C(w), runs(w)};
+    const Paths p = paths_of(paths, n_reads, n_steps);
     const Csr g{d_row_off, d_dst};
     const Lift v{d_uni_off, d_member_off, d_out_off, d_members, d_seq_len, d_overlap, d_circular, n_unitigs, n_nodes};
     const uint32_t hbad = c.check(totals, 32, bad, [&] {
@@ -357,23 +286,16 @@ s2k_status s2k_paths_walks(s2k_ctx *ctx, uint64_t n_reads, const s2k_thread_out 
     }
     uint64_t total = 0;
     unsigned long long h[2] = {0, 0};
-    hipLaunchKernelGGL(walks_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, p, g, v, ws, totals);
-    c.launched();
-    c.scan(ws.h.tile_kept, nt, ws.h.tile_off, hw.scan_tmp(w));
-    c.fetch(&total, ws.h.tile_off + nt, 8);
-    c.fetch(h, totals, sizeof(h));
-    if (!c.sync()) return c.device_error();
+    if (!count_runs(c, ws.run, nt, runs.h.scan_tmp(w), [&] { hipLaunchKernelGGL(walks_count_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, p, g, v, ws, totals); },
+                    &total, totals, h, 2))
+        return c.device_error();
     *n_walks = total;
     *n_followed = h[0];
     *n_off_graph = h[1];
     if (!out) return S2K_OK;
     if (records && total > out->capacity) return S2K_ERR_CAPACITY;
     if (out->edge) c.copy(out->edge, ws.edge, n_steps * 4, hipMemcpyDeviceToDevice);
-    if (out->walk_off) {
-        hipLaunchKernelGGL(walks_offsets_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, c.st, paths->path_off, n_reads, n_steps, nt, ws.h,
-                           out->walk_off);
-        c.launched();
-    }
+    if (out->walk_off) launch_run_offsets(c, paths->path_off, n_reads, n_steps, nt, ws.run, out->walk_off);
     if (records) {
         c.scan(ws.adv, n_steps, ws.A, stmp(w));
         c.scan(paths->count, n_steps, ws.C, stmp(w));
