@@ -946,6 +946,87 @@ typedef struct s2k_align_out { /* device pointers, each may be NULL; capacity in
 s2k_status s2k_align_pairs(s2k_ctx *ctx, const uint8_t *d_query, uint64_t n_query_bytes, const uint8_t *d_target, uint64_t n_target_bytes,
                            const uint64_t *d_q_begin, const uint64_t *d_q_end, const uint64_t *d_t_begin, const uint64_t *d_t_end, uint64_t n_pairs,
                            uint32_t max_edits, const s2k_align_out *out, uint64_t *n_ops_bound);
+/* ---- pile-up and consensus: the aligned walks vote on the unitigs' bases ---------------------------------------------
+ * Pile-up.  Inputs: the walk records, d_step_unitig, d_out_off, d_out (n_bases bytes), d_overlap and n_unitigs exactly as
+ * s2k_walks_targets takes them; the query pool d_query (n_query_bytes) and per walk d_q_begin, where its query interval starts; per walk
+ * the alignment's d_align_flags, d_ops_off (n_walks + 1), d_n_ops, and d_ops (n_ops_total runs, len << 4 | op) as s2k_align_pairs wrote
+ * them for the pairs (query interval, target of the walk); max_shift <= S2K_PILEUP_MAX_SHIFT.
+ * The pile (s2k_pile, device pointers, the caller's): eleven planes of n_bases uint32_t each, indexed by position in d_out, the forward
+ * strand of the unitig: match, del, sub[4], ins[4], ins_long -- 44 B per base, plain counts.  Zeroed before the first batch and carried
+ * from batch to batch and from file to file, as d_best above.  The pile is a function of the multiset of walks, whatever the batch cut.
+ * Which walks vote: a walk with d_align_flags[w] != 0 (S2K_ALIGN_OVER, S2K_ALIGN_BAD_PATH) votes nothing and is counted; every other
+ * walk votes by the rule below.  A walk that s2k_walks_targets calls bad has an empty target here too.
+ * Source of a target byte: byte x of walk w's target comes from the step j and the offset o in s_j from which s2k_walks_targets copies
+ * it: overlapped bytes belong to the earlier step; on a circular walk o = (path_start + x) mod L, and a round (path_start + x) / L
+ * counts as a step of its own below.  Its forward position is p = out_off[t] + o on an even unitig and out_off[t] + L - 1 - o on an odd
+ * one.  A query byte that votes on an odd step is complemented.  Codes: A/a 0, C/c 1, G/g 2, T/t 3; an X byte without a code casts no
+ * vote and is counted (n_other).
+ * Pieces: runs of =, X and D are cut where the step of the target byte changes; each piece covers a forward interval [a, b) of one
+ * unitig.  An I run of n bytes between target bytes x - 1 and x belongs to the step of byte x - 1 (of byte 0 at x == 0; with an empty
+ * target it is dropped and counted, n_empty_ins); its forward gap g, the position it is inserted before, is p(x - 1) + 1 on an even step
+ * (p(0) at x == 0) and p(x - 1) on an odd one (p(0) + 1 at x == 0).
+ * Normalisation: gaps are left-aligned on the forward strand.  The forward-left neighbour of a gap run (I or D) is the run before it in
+ * the CIGAR on an even step and the run behind it on an odd one.  The shift d is 0 unless that neighbour is =, the gap run is one piece,
+ * and the neighbour's piece next to the gap lies in the same step, e its length; then d is the largest d <= min(e, max_shift) with, for
+ * i = 1 .. d, out[a - i] == out[b - i] for D, and out[g - i] == c[n - 1 - ((i - 1) mod n)] for I, c the inserted bytes in forward
+ * orientation (reversed and complemented on an odd step); bytes are compared as they are.
+ * Votes: D: del += 1 over [a - d, b - d), and the neighbouring = piece votes match += 1 over its interval without [a - d, a) and with
+ * [b - d, b) in its place; every other = piece match += 1 over its interval; X: sub[code][p] += 1 per byte; an I run of one byte with
+ * a code: ins[code][g - d] += 1; any other I run: ins_long[g - d] += 1 (an I shift leaves match as it was); a gap at g - d == the
+ * unitig's end is dropped and counted (n_end_ins).
+ * stats (host, S2K_PILEUP_STATS words, always set, zeros on a refusal): walks used, walks skipped, n_other, n_end_ins, gaps shifted,
+ * n_empty_ins, 0, 0.
+ * Checked on the device before anything is written, S2K_ERR_INVALID_ARG and nothing written otherwise (flag words read by the host):
+ * the checks of s2k_walks_targets; ops_off does not decrease and ends inside n_ops_total, n_ops[w] <= ops_off[w + 1] - ops_off[w];
+ * every run of a voting walk has a known code and a length above 0; the runs of a voting walk consume exactly its target's length; its
+ * query interval [q_begin, q_begin + the query bytes of its runs) lies inside the pool.  On the host: max_shift above
+ * S2K_PILEUP_MAX_SHIFT, a plane that is NULL, n_walks >= 2^32.
+ * One lane per run slot; a run's offsets in target and query are differences of two scans over all slots; no lane walks a match run:
+ * = and D pieces add +1 / -1 at their ends to two difference planes in the workspace, which a scan each adds into match and del; X
+ * bytes and I runs are one 32-bit atomic add each.  Integer sums are the only atomics on an output: two calls on equal piles give
+ * equal piles.  Workspace (the context's grow-only count workspace): 24 B per step, 13 B per walk, 28 B per run slot, 16 B per base.
+ * Runs on the context's stream; returns when the pile is written.
+ * Not done: votes on both copies of an overlapped base (a unitig's head that is entered along an edge is voted only by walks that start
+ * in it); insertions of two or more bases (counted in ins_long, never called); quality values; a pile over several devices. */
+#define S2K_PILEUP_MAX_SHIFT 64u
+#define S2K_PILEUP_STATS 8
+#define S2K_CONSENSUS_STATS 8
+typedef struct s2k_pile { /* device pointers, n_bases uint32_t each */
+    uint32_t *match;
+    uint32_t *del;
+    uint32_t *sub[4];
+    uint32_t *ins[4];
+    uint32_t *ins_long;
+} s2k_pile;
+s2k_status s2k_walks_pileup(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_first_step, const uint32_t *d_n_steps, const uint64_t *d_path_start,
+                            const uint64_t *d_path_end, const uint32_t *d_flags, const uint32_t *d_step_unitig, uint64_t n_steps, const uint64_t *d_out_off,
+                            const uint8_t *d_out, uint64_t n_bases, const uint32_t *d_overlap, uint64_t n_unitigs, const uint8_t *d_query,
+                            uint64_t n_query_bytes, const uint64_t *d_q_begin, const uint32_t *d_align_flags, const uint64_t *d_ops_off,
+                            const uint32_t *d_n_ops, const uint32_t *d_ops, uint64_t n_ops_total, uint32_t max_shift, const s2k_pile *pile, uint64_t *stats);
+/* Consensus, once per graph; the pile is only read, so more batches may be added afterwards.  Per position p of a unitig, cur = the code
+ * of out[p] (none for another byte): tot[c] = sub[c][p] + (c == cur ? match[p] : 0); for a byte without a code match[p] counts for
+ * the byte itself as a fifth candidate; depth = match + the four sub + del.  depth < min_cov: the byte is kept, nothing is inserted,
+ * n_low counts it.  Otherwise, first the insertion before p: best = the code with the largest ins[c][p], the smallest among equals; if
+ * 2 ins[best][p] > depth the letter ACGT[best] is emitted (n_ins).  Then the base: if del[p] is strictly above every candidate nothing
+ * is emitted (n_del); otherwise, if the current byte's count equals the largest, the byte is kept as it is, case included; otherwise
+ * the upper-case letter of the smallest code with the largest count is emitted (n_sub).  A position with 2 ins_long[p] > depth is
+ * counted (n_long) and otherwise left alone.
+ * Outputs (each may be NULL): d_new_out_off (n_unitigs + 1); d_new_out (16-byte aligned; capacity in bytes; for s2k_walks_targets to
+ * read it its allocation must be whole 8-byte words, as d_out's); d_pos_map (n_bases + 1): the new position of every old one, an
+ * inserted letter belongs to the position it precedes, pos_map[n_bases] = *n_new_bases; d_new_overlap (2 n_unitigs): with ov' =
+ * min(overlap[U], L) and pm relative to the unitig, newL - pm(L - ov') for an even U and pm(ov') for an odd one.  *n_new_bases is always
+ * set; d_new_out NULL is the sizes call (the other outputs given are written); *n_new_bases > capacity with d_new_out given is
+ * S2K_ERR_CAPACITY and nothing at all is written.  stats (host, S2K_CONSENSUS_STATS words): n_low, n_sub, n_del, n_ins, n_long, 0, 0,
+ * 0; zeros on a refusal.  S2K_ERR_INVALID_ARG, nothing written: out_off that decreases or passes n_bases, a unitig of 2^31 bases or
+ * more (found on the device); a NULL plane, d_new_out not 16-byte aligned (on the host).  Positions outside [out_off[0],
+ * out_off[n_unitigs]) emit nothing.
+ * One lane per position decides its 0 to 2 bytes, one scan gives pos_map, then input-ordered stores: lane p writes its bytes at
+ * pos_map[p].  No atomic on an output: two calls are bit-identical.  Workspace: 14 B per base.  Runs on the context's stream; returns
+ * when the outputs are written.
+ * Not done: a second round on the polished coordinates (walks and member offsets are not remapped). */
+s2k_status s2k_pileup_consensus(s2k_ctx *ctx, const s2k_pile *pile, const uint64_t *d_out_off, const uint8_t *d_out, uint64_t n_bases,
+                                const uint32_t *d_overlap, uint64_t n_unitigs, uint32_t min_cov, uint64_t *d_new_out_off, uint8_t *d_new_out,
+                                uint64_t capacity, uint64_t *d_pos_map, uint32_t *d_new_overlap, uint64_t *n_new_bases, uint64_t *stats);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

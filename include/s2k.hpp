@@ -382,6 +382,37 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return n_ops_bound;
     }
+    // s2k_walks_pileup: the aligned walks of one batch vote on the unitigs' bases (`walks` as for walks_targets; query.begin: where every
+    // walk's query interval starts, query.end is not read; al: what align_pairs wrote for the walks, al.capacity = the runs d_ops holds).
+    // The pile is the caller's, zeroed before the first batch.  Returns the S2K_PILEUP_STATS counters.
+    struct PileupStats {
+        uint64_t v[S2K_PILEUP_STATS];
+    };
+    PileupStats walks_pileup(const s2k_walk_out &walks, const uint32_t *d_step_unitig, uint64_t n_steps, const uint64_t *d_out_off, const uint8_t *d_out,
+                             uint64_t n_bases, const uint32_t *d_overlap, uint64_t n_unitigs, const Pool &query, const s2k_align_out &al, const s2k_pile &pile,
+                             uint32_t max_shift = S2K_PILEUP_MAX_SHIFT) {
+        PileupStats t{};
+        s2k_status st = s2k_walks_pileup(ctx_, walks.capacity, walks.first_step, walks.n_steps, walks.path_start, walks.path_end, walks.flags, d_step_unitig,
+                                         n_steps, d_out_off, d_out, n_bases, d_overlap, n_unitigs, query.bytes, query.n_bytes, query.begin, al.flags, al.ops_off,
+                                         al.n_ops, al.ops, al.capacity, max_shift, &pile, t.v);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
+    // s2k_pileup_consensus: the polished bases of every unitig.  d_new_out nullptr: the sizes only.  Returns the new bases and the
+    // S2K_CONSENSUS_STATS counters; throws on S2K_ERR_CAPACITY too (nothing written).
+    struct Consensus {
+        uint64_t n_new_bases;
+        uint64_t stats[S2K_CONSENSUS_STATS];
+    };
+    Consensus pileup_consensus(const s2k_pile &pile, const uint64_t *d_out_off, const uint8_t *d_out, uint64_t n_bases, const uint32_t *d_overlap,
+                               uint64_t n_unitigs, uint32_t min_cov, uint64_t *d_new_out_off = nullptr, uint8_t *d_new_out = nullptr, uint64_t capacity = 0,
+                               uint64_t *d_pos_map = nullptr, uint32_t *d_new_overlap = nullptr) {
+        Consensus t{};
+        s2k_status st = s2k_pileup_consensus(ctx_, &pile, d_out_off, d_out, n_bases, d_overlap, n_unitigs, min_cov, d_new_out_off, d_new_out, capacity, d_pos_map,
+                                             d_new_overlap, &t.n_new_bases, t.stats);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "s2k_unitig_copy_places", "s2k_paths_lift",
     "s2k_table_vote_keys", "s2k_table_vote_representatives", "s2k_vote_ordinals",
     "s2k_walks_targets", "s2k_align_pairs",
+    "s2k_walks_pileup", "s2k_pileup_consensus",
 ]
 
 
@@ -67,6 +68,11 @@ ALIGN_MAX_EDITS = 255  # s2k_align_pairs: the largest max_edits
 ALIGN_WAVES = 2048  # s2k_align_pairs: the waves of its persistent grid
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # s2k_align_out.ops: len << 4 | op, the BAM codes
 CIGAR_CHARS = {CIGAR_I: "I", CIGAR_D: "D", CIGAR_EQ: "=", CIGAR_X: "X"}
+PILEUP_MAX_SHIFT = 64  # s2k_walks_pileup: the largest max_shift
+PILEUP_PLANES = ("match", "del", "sub0", "sub1", "sub2", "sub3", "ins0", "ins1", "ins2", "ins3", "ins_long")  # s2k_pile, in its order
+PILEUP_STATS = ("walks_used", "walks_skipped", "n_other", "n_end_ins", "n_shifted", "n_empty_ins")  # s2k_walks_pileup: stats[0 .. 6)
+CONSENSUS_STATS = ("n_low", "n_sub", "n_del", "n_ins", "n_long")  # s2k_pileup_consensus: stats[0 .. 5)
+PILEUP_STATS_WORDS = CONSENSUS_STATS_WORDS = 8
 
 
 class S2kError(RuntimeError):
@@ -131,6 +137,10 @@ class WalkOut(C.Structure):
 class AlignOut(C.Structure):
     _fields_ = [("capacity", C.c_uint64), ("edits", C.c_void_p), ("flags", C.c_void_p), ("ops_off", C.c_void_p), ("n_ops", C.c_void_p),
                 ("matches", C.c_void_p), ("ops", C.c_void_p)]
+
+
+class Pile(C.Structure):
+    _fields_ = [("match", C.c_void_p), ("del_", C.c_void_p), ("sub", C.c_void_p * 4), ("ins", C.c_void_p * 4), ("ins_long", C.c_void_p)]
 
 
 # s2k_node_place: where the forward oriented node 2 i lies on the oriented unitigs
@@ -259,6 +269,11 @@ def load_library(path=None):
                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.s2k_align_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                   C.c_uint32, C.POINTER(AlignOut), C.POINTER(C.c_uint64)]
+    L.s2k_walks_pileup.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                   C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(Pile), C.POINTER(C.c_uint64)]
+    L.s2k_pileup_consensus.argtypes = [C.c_void_p, C.POINTER(Pile), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -1060,6 +1075,70 @@ class Engine:
         out["n_ops_bound"] = m
         return out
 
+    @staticmethod
+    def _pile_struct(planes, n_bases):
+        """the s2k_pile over an (11, n_bases) int32 GPU tensor, rows in the order of PILEUP_PLANES"""
+        if planes.dim() != 2 or planes.shape[0] != len(PILEUP_PLANES) or planes.shape[1] != max(n_bases, 1) or planes.element_size() != 4 or not planes.is_contiguous():
+            raise ValueError("the pile is a contiguous (11, n_bases) 32-bit tensor, one row per plane of PILEUP_PLANES")
+        p = Pile()
+        row = [planes[i].data_ptr() for i in range(len(PILEUP_PLANES))]
+        p.match, p.del_, p.ins_long = row[0], row[1], row[10]
+        for c in range(4):
+            p.sub[c], p.ins[c] = row[2 + c], row[6 + c]
+        return p
+
+    def walks_pileup(self, walks, step_unitig, out_off, out, overlap, query, q_begin, alignments, planes, max_shift=PILEUP_MAX_SHIFT):
+        """The votes of one batch's aligned walks added to a pile (s2k_walks_pileup; the rule is in include/s2k.h).  walks, step_unitig,
+        out_off, out, overlap: as walks_targets takes them; query: the batch's bases (uint8 GPU tensor); q_begin: where every walk's
+        read interval starts in them (int64); alignments: a WalkAlignments (or anything with flags, ops_off, n_ops, ops) of these
+        walks; planes: the (11, n_bases) int32 GPU tensor of the pile, rows in the order of PILEUP_PLANES, zeroed before the first
+        batch -- it gains the votes.  -> dict of the PILEUP_STATS counters of this call."""
+        import torch
+
+        rec = [getattr(walks, f).contiguous() for f in ("first_step", "n_steps", "path_start", "path_end", "flags")]
+        step_unitig, out_off, out, overlap, query, q_begin = (x.contiguous() for x in (step_unitig, out_off, out, overlap, query, q_begin))
+        al = [getattr(alignments, f).contiguous() for f in ("flags", "ops_off", "n_ops", "ops")]
+        nw, ns, t, dev = rec[0].numel(), step_unitig.numel(), out_off.numel() - 1, out_off.device
+        if (any(x.numel() != nw for x in rec) or [x.element_size() for x in rec] != [8, 4, 8, 8, 4] or step_unitig.element_size() != 4
+                or out_off.element_size() != 8 or out.element_size() != 1 or overlap.numel() != 2 * t or overlap.element_size() != 4):
+            raise ValueError("walks_pileup wants the walk records, one 32-bit unitig per step, and the out_off, out and overlap of the unitig sequences")
+        if (query.element_size() != 1 or q_begin.numel() != nw or q_begin.element_size() != 8 or [x.element_size() for x in al] != [4, 8, 4, 4]
+                or al[0].numel() < nw or al[2].numel() < nw or al[1].numel() != nw + 1):
+            raise ValueError("walks_pileup wants the batch's bases, one 64-bit interval start per walk and the alignment arrays of these walks")
+        pile = self._pile_struct(planes, out.numel())
+        stats = (C.c_uint64 * PILEUP_STATS_WORDS)()
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_walks_pileup(self.ctx, nw, *(_p(x, nw) for x in rec), _p(step_unitig, ns), ns, _p(out_off), _p(out, out.numel()), out.numel(),
+                                              _p(overlap, t), t, _p(query, query.numel()), query.numel(), _p(q_begin, nw), _p(al[0], nw), _p(al[1]), _p(al[2], nw),
+                                              _p(al[3], al[3].numel()), al[3].numel(), int(max_shift), C.byref(pile), stats))
+        return {f: int(stats[i]) for i, f in enumerate(PILEUP_STATS)}
+
+    def pileup_consensus(self, planes, out_off, out, overlap, min_cov=3):
+        """The polished bases of every unitig from a pile (s2k_pileup_consensus; the rule is in include/s2k.h).  planes: the pile, only
+        read; out_off, out, overlap: the draft the pile was taken on.  Two calls: the size, then the bytes.  -> dict of GPU tensors
+        out_off (int64, n_unitigs + 1), out (uint8), pos_map (int64, n_bases + 1), overlap (int32, 2 n_unitigs), the int n_bases and
+        the CONSENSUS_STATS counters in stats."""
+        import torch
+
+        out_off, out, overlap = (x.contiguous() for x in (out_off, out, overlap))
+        t, nb, dev = out_off.numel() - 1, out.numel(), out_off.device
+        if out_off.element_size() != 8 or out.element_size() != 1 or overlap.numel() != 2 * t or overlap.element_size() != 4:
+            raise ValueError("pileup_consensus wants the out_off, out and overlap of the unitig sequences")
+        pile = self._pile_struct(planes, nb)
+        args = (self.ctx, C.byref(pile), _p(out_off), _p(out, nb), nb, _p(overlap, t), t, int(min_cov))
+        n, stats = C.c_uint64(0), (C.c_uint64 * CONSENSUS_STATS_WORDS)()
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_pileup_consensus(*args, None, None, 0, None, None, C.byref(n), stats))
+        m = int(n.value)
+        new_off = torch.zeros(t + 1, dtype=torch.int64, device=dev)
+        new_out = torch.zeros((max(m, 1) + 7) // 8 * 8, dtype=torch.uint8, device=dev)  # whole 8-byte words: walks_targets can read it
+        pos_map = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+        new_ov = torch.zeros(max(2 * t, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_pileup_consensus(*args, _p(new_off), _p(new_out), m, _p(pos_map), _p(new_ov, t), C.byref(n), stats))
+        return {"out_off": new_off, "out": new_out[:m], "pos_map": pos_map, "overlap": new_ov[:2 * t], "n_bases": m,
+                "stats": {f: int(stats[i]) for i, f in enumerate(CONSENSUS_STATS)}}
+
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""
         self._check(self.lib.s2k_partition_device(self.ctx, C.c_void_p(d_hash or 0), n, n_parts, C.c_void_p(d_out or 0), C.c_void_p(d_part_off)))
@@ -1667,6 +1746,14 @@ class UnitigGraph:
         zero = lambda x: torch.where(bad, torch.zeros_like(x), x) if nw else x  # noqa: E731
         return WalkAlignments(a["edits"], zero(a["matches"]), zero(a["n_ops"]), a["ops_off"], a["ops"], flags)
 
+    def pileup(self, engine, sequences):
+        """An empty pile over this graph's draft bases -> Pileup.  sequences: the pair self.sequences returned.  Pileup.add takes the
+        walks and alignments of one batch after self.align; Pileup.consensus gives the polished bases.  It works as it is on
+        simplified graphs and on the contigs of untangle_map with lifted paths."""
+        if getattr(self, "overlap", None) is None:
+            raise ValueError("pileup wants the pair that self.sequences(engine, node_seqs) returned")
+        return Pileup(self, sequences)
+
     def write_gfa(self, path, members=False, sequences=None):
         """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
         members=True an nd:Z: tag that lists node index and orientation in path order) and an L line per twin pair of edges, by the rule
@@ -1878,6 +1965,64 @@ def alignment_block_len(ops_off, n_ops, ops):
     ln = np.concatenate([[0], np.cumsum(np.asarray(ops).astype(np.uint64) >> np.uint64(4))]).astype(np.uint64)
     a = np.asarray(ops_off).astype(np.int64)[:-1]
     return ln[a + np.asarray(n_ops).astype(np.int64)] - ln[a]
+
+
+class Pileup:
+    """The votes of aligned read walks on the bases of a UnitigGraph's draft (UnitigGraph.pileup; include/s2k.h: s2k_walks_pileup,
+    s2k_pileup_consensus): planes, an (11, n_bases) int32 GPU tensor with one row per plane of PILEUP_PLANES (match, del, sub0..3,
+    ins0..3, ins_long), indexed by position in the draft `sequences` = (out_off, out); graph, the UnitigGraph.  add() once per batch,
+    from file to file; consensus() whenever wanted, the pile is only read."""
+
+    def __init__(self, graph, sequences):
+        import torch
+
+        self.graph, self.sequences = graph, sequences
+        self.planes = torch.zeros((len(PILEUP_PLANES), max(sequences[1].numel(), 1)), dtype=torch.int32, device=sequences[1].device)
+        self.stats = {f: 0 for f in PILEUP_STATS}
+
+    def add(self, engine, walks, alignments, bases, read_off, max_shift=PILEUP_MAX_SHIFT):
+        """One batch's votes: walks, the ReadWalks graph.walks returned; alignments, the WalkAlignments graph.align returned for them;
+        bases, read_off: the batch's bases and read offsets on the GPU.  -> the PILEUP_STATS counters of this batch (self.stats sums
+        them)."""
+        qb, _ = walk_query_intervals(walks, read_off)
+        st = engine.walks_pileup(walks, walks.paths.unitig, self.sequences[0], self.sequences[1], self.graph.overlap, bases, qb, alignments, self.planes,
+                                 max_shift)
+        for f, v in st.items():
+            self.stats[f] += v
+        return st
+
+    def depth(self):
+        """match + the four sub + del per position: the walks whose alignment covers it (int64 GPU tensor)"""
+        import torch
+
+        n = self.sequences[1].numel()
+        return (self.planes[:6, :n].to(torch.int64) & 0xFFFFFFFF).sum(0)
+
+    def host(self):
+        """-> dict of numpy uint32 arrays, one per plane of PILEUP_PLANES"""
+        n = self.sequences[1].numel()
+        h = self.planes[:, :n].cpu().numpy().view(np.uint32)
+        return {f: h[i] for i, f in enumerate(PILEUP_PLANES)}
+
+    def consensus(self, engine, min_cov=3):
+        """The polished bases (Engine.pileup_consensus) -> PolishedSequences"""
+        import copy
+
+        c = engine.pileup_consensus(self.planes, self.sequences[0], self.sequences[1], self.graph.overlap, min_cov)
+        g = copy.copy(self.graph)
+        g.overlap = c["overlap"]
+        g._member_offsets = None  # member offsets are not remapped onto the polished coordinates
+        return PolishedSequences((c["out_off"], c["out"]), c["overlap"], c["pos_map"], c["stats"], g)
+
+
+class PolishedSequences:
+    """What Pileup.consensus returns: sequences, the (out_off, out) pair that write_fasta and write_gfa(sequences=) take; overlap, the
+    overlap that leaves every oriented unitig in the new coordinates; pos_map (int64, n_bases + 1), the new position of every draft
+    position (an inserted letter belongs to the position it precedes); stats, the CONSENSUS_STATS counters; graph, a shallow copy of
+    the unitig graph that carries the new overlaps: graph.write_gfa(path, sequences=polished.sequences)."""
+
+    def __init__(self, sequences, overlap, pos_map, stats, graph):
+        self.sequences, self.overlap, self.pos_map, self.stats, self.graph = sequences, overlap, pos_map, stats, graph
 
 
 class SpanTable:

@@ -39,6 +39,7 @@
 #include "s2k_dev.h"
 #include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
+#include "s2k_targets_dev.h"
 
 namespace s2k {
 namespace {
@@ -49,76 +50,9 @@ constexpr int32_t AL_NONE = -(1 << 30);        // an H that does not exist
 constexpr size_t AL_TRACE_BUDGET = 256u << 20; // bytes of wavefront storage over all waves in flight
 static_assert(2 * S2K_ALIGN_MAX_EDITS + 1 <= 64 * AL_CH, "the chunks must cover every diagonal");
 static_assert(S2K_ALIGN_WAVES % (AL_T / 64) == 0, "whole blocks");
+static_assert(AL_T == TG_T, "the step and length passes are launched with AL_T threads");
 
-// the last i in [lo, hi] with off[i] <= x (off[lo] <= x holds)
-__device__ inline uint64_t last_le(const uint64_t *__restrict__ off, uint64_t lo, uint64_t hi, uint64_t x) {
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// ---- targets ----------------------------------------------------------------------------------------------------------------------
-struct TgIn {
-    const uint64_t *first_step, *path_start, *path_end;
-    const uint32_t *n_steps, *flags, *unitig;
-    const uint64_t *out_off;
-    const uint8_t *out;
-    const uint32_t *overlap;
-    uint64_t n_walks, n_all_steps, n_unitigs, n_bases;
-};
-
-__device__ __forceinline__ uint64_t unitig_len(const TgIn &in, uint32_t U) { return in.out_off[(U >> 1) + 1] - in.out_off[U >> 1]; }
-
-__global__ __launch_bounds__(UT) void tg_check_kernel(TgIn in, uint32_t *__restrict__ bad) {
-    bool ok = true;
-    const uint64_t i0 = (uint64_t)blockIdx.x * UT + threadIdx.x, stride = (uint64_t)gridDim.x * UT;
-    for (uint64_t g = i0; g < in.n_all_steps; g += stride)
-        if (in.unitig[g] >= 2 * in.n_unitigs) ok = false;
-    for (uint64_t t = i0; t < in.n_unitigs; t += stride) {
-        const uint64_t a = in.out_off[t], b = in.out_off[t + 1];
-        if (a > b || b > in.n_bases || b - a >= (1ull << 32)) ok = false;
-    }
-    for (uint64_t w = i0; w < in.n_walks; w += stride) {
-        const uint64_t f = in.first_step[w];
-        if (f > in.n_all_steps || in.n_steps[w] > in.n_all_steps - f) ok = false;
-    }
-    if (!ok) atomicOr(bad, 1u);
-}
-
-__global__ __launch_bounds__(AL_T) void tg_steps_kernel(TgIn in, uint32_t *__restrict__ adv, uint32_t *__restrict__ broken) {
-    const uint64_t g = (uint64_t)blockIdx.x * AL_T + threadIdx.x;
-    if (g >= in.n_all_steps) return;
-    const uint32_t U = in.unitig[g];
-    const uint64_t L = unitig_len(in, U); // the check pass: below 2^32
-    adv[g] = (uint32_t)(L - std::min<uint64_t>(in.overlap[U], L));
-    uint32_t b = 0;
-    if (g) {
-        const uint32_t P = in.unitig[g - 1];
-        b = in.overlap[P] > std::min(unitig_len(in, P), L);
-    }
-    broken[g] = b;
-}
-
-__global__ __launch_bounds__(AL_T) void tg_len_kernel(TgIn in, const uint64_t *__restrict__ G, const uint64_t *__restrict__ J, uint32_t *__restrict__ len,
-                                                      uint8_t *__restrict__ bad8, uint32_t *__restrict__ bad) {
-    const uint64_t w = (uint64_t)blockIdx.x * AL_T + threadIdx.x;
-    if (w >= in.n_walks) return;
-    const uint64_t f = in.first_step[w], n = in.n_steps[w], ps = in.path_start[w], pe = in.path_end[w];
-    bool b = ps > pe;
-    if (in.flags[w] & S2K_WALK_CIRCULAR) b = b || n == 0 || unitig_len(in, in.unitig[f]) == 0;
-    else {
-        const uint64_t total = n ? G[f + n - 1] - G[f] + unitig_len(in, in.unitig[f + n - 1]) : 0;
-        b = b || pe > total || (n > 1 && J[f + n] != J[f + 1]);
-    }
-    const uint64_t l = b ? 0 : pe - ps;
-    if (l >= (1ull << 32)) atomicOr(bad, 2u);
-    len[w] = (uint32_t)l;
-    bad8[w] = b ? 1 : 0;
-}
-
+// ---- targets (the inputs, the check, step and length passes: s2k_targets_dev.h) -------------------------------------------------------
 __global__ __launch_bounds__(AL_T) void tg_copy_kernel(TgIn in, const uint64_t *__restrict__ G, const uint64_t *__restrict__ toff, uint8_t *__restrict__ tgt,
                                                        uint64_t total) {
     __shared__ uint64_t srange[2];
