@@ -1027,6 +1027,113 @@ s2k_status s2k_walks_pileup(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_fi
 s2k_status s2k_pileup_consensus(s2k_ctx *ctx, const s2k_pile *pile, const uint64_t *d_out_off, const uint8_t *d_out, uint64_t n_bases,
                                 const uint32_t *d_overlap, uint64_t n_unitigs, uint32_t min_cov, uint64_t *d_new_out_off, uint8_t *d_new_out,
                                 uint64_t capacity, uint64_t *d_pos_map, uint32_t *d_new_overlap, uint64_t *n_new_bases, uint64_t *stats);
+/* ---- segmented alignment: long walks cut at anchor k-min-mers, aligned piece by piece, joined --------------------------
+ * s2k_align_pairs aligns at most S2K_ALIGN_MAX_EDITS edits per pair, and a walk of a long noisy read passes that.  Every solid item of
+ * a threaded step is an exact anchor between the read and the walk's stitched path; s2k_walks_segments cuts a walk at a thinned,
+ * strictly increasing subset of them into segment pairs that s2k_align_pairs takes as they are, and s2k_align_join puts the segments'
+ * CIGARs back together, one alignment per walk, in the layout s2k_walks_pileup and the GAF writer take.
+ * Inputs of s2k_walks_segments.  walks: the records s2k_paths_walks wrote (walk_off over n_reads reads, first_step, n_steps, qstart,
+ * qend, path_start, path_end, flags; n_walks of each; the other fields are not read); paths: unitig, pos and count of the n_steps steps
+ * the walks were made on (path_off is not read); the decomposition and where its members lie in base space exactly as
+ * s2k_paths_walks takes them (d_uni_off, d_members, d_circular, d_member_off, d_out_off, d_overlap, d_seq_len; n_unitigs, n_nodes); per
+ * walk d_q_begin, where its query interval starts in the batch's bases (as s2k_walks_pileup takes it), and d_tgt_off (n_walks + 1) and
+ * d_bad as s2k_walks_targets wrote them; src: the SOURCE paths, what s2k_table_thread wrote for the same reads (path_off, pos, count
+ * and item are required; n_src_steps), on which item i of step r is exactly the read's item item[r] + i at position pos[r] + i of the
+ * step's oriented unitig; in: km_off and start of the batch's s2k_device_out.  Two optional maps, one entry per source step:
+ * d_src_step[r], the step of `paths` that source step r went into, S2K_NO_STEP for none (NULL: the identity, the walks were made on src
+ * itself), and d_src_pos[r], the position of r's first item on that step's oriented unitig (NULL: src->pos).  s2k_paths_bridge keeps
+ * unitig and position, so after it src_step[r] = (the source steps r' <= r with join[r'] != 1) - 1 and src_pos = src->pos.  seg_len, in
+ * bases: 0 means S2K_SEGMENT_LEN; a value below S2K_SEGMENT_MIN_LEN is refused.
+ * Candidates, in source-item order (read by read, step by step, item by item).  Item i of source step r of read R is the read's item j
+ * = km_off[R] + item[r] + i.  S = src_step[r], w = the walk with first_step[w] <= S < first_step[w] + n_steps[w], x = src_pos[r] + i.
+ * The item is OUTSIDE -- counted, never an error -- when S is S2K_NO_STEP, when no walk holds S, when x is not in [pos[S], pos[S] +
+ * count[S]) or not below the members of the step's unitig, when walk w has S2K_WALK_CIRCULAR, or when d_bad[w] != 0.  Every other item
+ * is a candidate of walk w with, as integers that may be negative,
+ *   qc = in->start[j] - qstart[w]                                  (its offset in the walk's query interval) and
+ *   tc = G_w[S] + lo(unitig[S], x) - path_start[w]                 (its offset in the walk's target),
+ * lo the first base of position x of the oriented unitig exactly as "Base interval of a position" above has it, and G_w[S] the sum of
+ * adv(unitig) over the walk's steps before S, adv as for s2k_paths_walks.  Both sides start at the first base of the item's first
+ * minimizer, so on an error-free read query byte qc IS target byte tc.
+ * Admissible: with m = qend[w] - qstart[w] and n = tgt_off[w + 1] - tgt_off[w], a candidate is admissible iff 0 < qc < m, 0 < tc < n, qc
+ * is strictly above the qc of EVERY earlier candidate of the walk (admissible or not) and tc strictly above the tc of every earlier
+ * candidate of the walk.  Admissible anchors of a walk therefore increase strictly in both coordinates, whatever the representatives
+ * of erroneous reads did to the member offsets.
+ * Chosen: an admissible candidate is chosen iff qc / seg_len >= 1 and the admissible candidate of the same walk before it, if there is
+ * one, has another qc / seg_len (integer division): the first admissible anchor of every bucket of seg_len query bases but the first.
+ * Segments: a walk with a chosen anchors gives a + 1 segments between the cuts (0, 0), the chosen (qc, tc) in order, (m, n): segment
+ * k is query [q_begin[w] + qc_k, q_begin[w] + qc_(k+1)) against target [tgt_off[w] + tc_k, tgt_off[w] + tc_(k+1)).  A circular walk
+ * and a walk without a chosen anchor give one segment, the whole pair; a bad walk one segment that is empty on both sides, at
+ * (q_begin[w], tgt_off[w]).  Every walk has at least one segment; a cut walk's segments are non-empty on both sides.
+ * s2k_segment_out (device pointers, each may be NULL; capacity in segments): seg_off (n_walks + 1): the segments of walk w are
+ * [seg_off[w], seg_off[w + 1]); q_begin, q_end, t_begin, t_end, one uint64_t per segment, absolute in the two pools: they go to
+ * s2k_align_pairs unchanged.  *n_segments is always set.  stats (host, S2K_SEGMENT_STATS words, always set, zeros on a refusal):
+ * candidates, outside, admissible, chosen, walks cut at least once, 0, 0, 0.  out NULL or without the four interval arrays asks for the
+ * sizes (seg_off, when given, is written whenever the call returns S2K_OK); *n_segments > out->capacity with an interval array given
+ * is S2K_ERR_CAPACITY and nothing at all is written.
+ * Checked on the device before anything is written, flag words read by the host, S2K_ERR_INVALID_ARG otherwise: the checks of
+ * s2k_walks_targets on the walks and the steps' unitigs (every walk's steps inside the paths, every unitig < 2 n_unitigs, out_off not
+ * decreasing, no unitig of 2^32 bases or more) and those of s2k_paths_walks on the steps and the decomposition (count >= 1, pos < len,
+ * pos + count <= len unless the unitig is circular; uni_off strictly ascending from 0 to n_nodes; every member < 2 n_nodes; every
+ * member_off inside its unitig's bases); walk_off and src->path_off run from 0 to n_walks and to n_src_steps without decreasing; the
+ * walks' step ranges ascend without overlapping (first_step[w] + n_steps[w] <= first_step[w + 1]); qstart <= qend; tgt_off does not
+ * decrease and no target has 2^32 bytes or more; km_off does not decrease and km_off[R] + item[r] + count[r] <= km_off[R + 1];
+ * src_step[r] is below n_steps or S2K_NO_STEP; the walk that holds src_step[r] is a walk of r's read; src_step does not decrease from
+ * a source step to the next one of its read where both have a step, nor does the walk of a candidate lie before the walk of an
+ * earlier one.  On the host: seg_len below S2K_SEGMENT_MIN_LEN, n_unitigs or n_nodes or n_walks >= 2^31.  d_seq_len, d_q_begin and the
+ * contents of d_overlap and d_bad are trusted, and in->start is trusted to hold km_off[n_reads] entries.
+ * One lane per source step, then one lane per item: the two "strictly above" tests are exclusive max-scans over all items of the
+ * batch (a walk's index in the high half of the scanned word keeps the walks apart: walks come in read order), the admissible
+ * anchors are compacted, the chosen ones are the heads of a mask over the compacted stream and are compacted again, seg_off is a
+ * search per walk and the intervals are written one lane per segment.  No lane walks a walk.  The counters are integer sums and no
+ * atomic touches an output: two calls are bit-identical.  Workspace (the context's grow-only count workspace): 28 B per item (two
+ * scanned words, three compacted words) and twice 12 B per 64 items and 12 B per tile of 2 048 for the masks; 20 B per source step;
+ * 16 B per step of the paths; 8 B per walk.  Runs on the context's stream; returns when the outputs are written.
+ * Not done: the map through s2k_paths_lift (ContigLift.lift) is not composed anywhere: d_src_step / d_src_pos carry it, nothing
+ * computes them, and until then walks on lifted paths are aligned whole (s2k_align_pairs); re-anchoring (an anchor is never searched
+ * for, moved or verified against the bases); choosing among walks; affine gaps; a globally optimal score -- the joined alignment is
+ * a valid alignment of the walk, optimal between its cuts only. */
+#define S2K_NO_STEP 0xFFFFFFFFFFFFFFFFull
+#define S2K_SEGMENT_LEN 512u
+#define S2K_SEGMENT_MIN_LEN 64u
+#define S2K_SEGMENT_STATS 8
+typedef struct s2k_segment_out { /* device pointers, each may be NULL; capacity in segments */
+    uint64_t capacity;
+    uint64_t *seg_off; /* n_walks + 1 */
+    uint64_t *q_begin;
+    uint64_t *q_end;
+    uint64_t *t_begin;
+    uint64_t *t_end;
+} s2k_segment_out;
+s2k_status s2k_walks_segments(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out *walks, uint64_t n_walks, const s2k_thread_out *paths,
+                              uint64_t n_steps, const uint64_t *d_uni_off, const uint32_t *d_members, const uint8_t *d_circular,
+                              uint64_t n_unitigs, const uint64_t *d_member_off, const uint64_t *d_out_off, const uint32_t *d_overlap,
+                              const uint32_t *d_seq_len, uint64_t n_nodes, const uint64_t *d_q_begin, const uint64_t *d_tgt_off,
+                              const uint8_t *d_bad, const s2k_thread_out *src, uint64_t n_src_steps, const uint64_t *d_src_step,
+                              const uint32_t *d_src_pos, const s2k_device_out *in, uint32_t seg_len, const s2k_segment_out *out,
+                              uint64_t *n_segments, uint64_t *stats);
+/* Join.  Inputs: d_seg_off (n_walks + 1) and d_bad (one byte per walk) as above, and seg, the arrays s2k_align_pairs wrote for the
+ * n_segments segment pairs (edits, flags, ops_off, n_ops, matches, ops; seg->capacity = the runs ops holds).  Output: `out`, one
+ * alignment per walk in the layout of s2k_align_pairs, but compact: ops_off (n_walks + 1) is the exclusive scan of the joined n_ops.
+ * A bad walk (d_bad[w] != 0) gets flags = S2K_ALIGN_BAD_PATH and edits = n_ops = matches = 0.  Otherwise a walk with a segment that
+ * has S2K_ALIGN_OVER gets flags = S2K_ALIGN_OVER, n_ops = matches = 0 and edits = the sum over its segments, a lower bound (an over
+ * segment counts max_edits + 1).  Every other walk gets flags = 0, edits and matches = the sums over its segments, and as its CIGAR the
+ * segments' runs in order, where the first run of a segment after the walk's first is merged into the run before it when the segment
+ * before it has a run and that segment's last run has the same op; a chain of all-'=' segments thus becomes one run.  A run is a HEAD
+ * unless it is so merged; n_ops = the heads of the walk, and a head's length is the sum of its run and the merged runs behind it.
+ * *n_ops_total = ops_off[n_walks] is always set.  out NULL asks for the sizes; *n_ops_total > out->capacity with out->ops given is
+ * S2K_ERR_CAPACITY and nothing at all is written; otherwise every array of `out` that is given is written.  Checked on the device
+ * before anything is written (S2K_ERR_INVALID_ARG): seg_off runs from 0 to n_segments without decreasing; the segments' ops_off does not
+ * decrease and ends inside seg->capacity, n_ops[s] <= ops_off[s + 1] - ops_off[s]; every run of a walk that is neither bad nor over has
+ * a known code and a length above 0; no merged run has 2^28 bases or more (the length field is 28 bits); no walk's edits or matches
+ * sum to 2^32 or more.  On the host: n_walks or n_segments >= 2^32.
+ * One lane per run slot of the segments: its segment and walk by searches of the two offset arrays, one head mask, one compaction;
+ * merged lengths are differences of a prefix over the slots' lengths taken at consecutive heads, the sums differences of prefixes over
+ * the segments; the writes are ordered by output position.  No atomic on an output: two calls are bit-identical.  Workspace: 24 B per
+ * run slot (length and prefix; prefix and op of the joined runs, sized by the slots), the mask's 12 B per 64 slots and per tile, 28 B
+ * per segment.  Runs on the context's stream; returns
+ * when the outputs are written. */
+s2k_status s2k_align_join(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_seg_off, const uint8_t *d_bad, uint64_t n_segments,
+                          const s2k_align_out *seg, const s2k_align_out *out, uint64_t *n_ops_total);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

@@ -413,6 +413,51 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return t;
     }
+    // s2k_walks_segments: every walk cut into segment pairs at a thinned, strictly increasing subset of its anchor k-min-mers (`walks`:
+    // the records s2k_paths_walks wrote, walk_off included; `paths`: unitig, pos, count of the steps they were made on; `lift`: the
+    // decomposition and its base coordinates as paths_walks takes them; d_q_begin, d_tgt_off, d_bad per walk; `source`: the paths
+    // s2k_table_thread wrote for the same reads, where every step of them went (nullptr: the identity / src->pos) and the batch's
+    // extraction).  out nullptr: the sizes only.  Returns the segments and the S2K_SEGMENT_STATS counters; throws on S2K_ERR_CAPACITY
+    // too (nothing written).
+    struct SegmentLift {
+        const uint64_t *uni_off;
+        const uint32_t *members;
+        const uint8_t *circular;
+        uint64_t n_unitigs;
+        const uint64_t *member_off, *out_off;
+        const uint32_t *overlap, *seq_len;
+        uint64_t n_nodes;
+    };
+    struct SegmentSource {
+        const s2k_thread_out *paths;
+        uint64_t n_steps;
+        const uint64_t *step; // per source step, S2K_NO_STEP for none
+        const uint32_t *pos;
+        const s2k_device_out *in;
+    };
+    struct Segments {
+        uint64_t n_segments;
+        uint64_t stats[S2K_SEGMENT_STATS];
+    };
+    Segments walks_segments(uint64_t n_reads, const s2k_walk_out &walks, uint64_t n_walks, const s2k_thread_out &paths, uint64_t n_steps,
+                            const SegmentLift &lift, const uint64_t *d_q_begin, const uint64_t *d_tgt_off, const uint8_t *d_bad, const SegmentSource &source,
+                            uint32_t seg_len = S2K_SEGMENT_LEN, const s2k_segment_out *out = nullptr) {
+        Segments t{};
+        s2k_status st = s2k_walks_segments(ctx_, n_reads, &walks, n_walks, &paths, n_steps, lift.uni_off, lift.members, lift.circular, lift.n_unitigs,
+                                           lift.member_off, lift.out_off, lift.overlap, lift.seq_len, lift.n_nodes, d_q_begin, d_tgt_off, d_bad, source.paths,
+                                           source.n_steps, source.step, source.pos, source.in, seg_len, out, &t.n_segments, t.stats);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
+    // s2k_align_join: the alignments align_pairs wrote for the segment pairs (`seg`, seg.capacity = the runs seg.ops holds) joined into
+    // one alignment per walk.  out nullptr: the size only.  Returns the joined runs; throws on S2K_ERR_CAPACITY too (nothing written).
+    uint64_t align_join(uint64_t n_walks, const uint64_t *d_seg_off, const uint8_t *d_bad, uint64_t n_segments, const s2k_align_out &seg,
+                        const s2k_align_out *out = nullptr) {
+        uint64_t n_ops_total = 0;
+        s2k_status st = s2k_align_join(ctx_, n_walks, d_seg_off, d_bad, n_segments, &seg, out, &n_ops_total);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_ops_total;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "s2k_table_vote_keys", "s2k_table_vote_representatives", "s2k_vote_ordinals",
     "s2k_walks_targets", "s2k_align_pairs",
     "s2k_walks_pileup", "s2k_pileup_consensus",
+    "s2k_walks_segments", "s2k_align_join",
 ]
 
 
@@ -73,6 +74,11 @@ PILEUP_PLANES = ("match", "del", "sub0", "sub1", "sub2", "sub3", "ins0", "ins1",
 PILEUP_STATS = ("walks_used", "walks_skipped", "n_other", "n_end_ins", "n_shifted", "n_empty_ins")  # s2k_walks_pileup: stats[0 .. 6)
 CONSENSUS_STATS = ("n_low", "n_sub", "n_del", "n_ins", "n_long")  # s2k_pileup_consensus: stats[0 .. 5)
 PILEUP_STATS_WORDS = CONSENSUS_STATS_WORDS = 8
+NO_STEP = 0xFFFFFFFFFFFFFFFF  # s2k_walks_segments: d_src_step of a source step that went into no step of the walks' paths
+SEGMENT_LEN = 512  # s2k_walks_segments: the default seg_len, in query bases
+SEGMENT_MIN_LEN = 64  # s2k_walks_segments: the smallest seg_len
+SEGMENT_STATS = ("candidates", "outside", "admissible", "chosen", "walks_cut")  # s2k_walks_segments: stats[0 .. 5)
+SEGMENT_STATS_WORDS = 8
 
 
 class S2kError(RuntimeError):
@@ -137,6 +143,11 @@ class WalkOut(C.Structure):
 class AlignOut(C.Structure):
     _fields_ = [("capacity", C.c_uint64), ("edits", C.c_void_p), ("flags", C.c_void_p), ("ops_off", C.c_void_p), ("n_ops", C.c_void_p),
                 ("matches", C.c_void_p), ("ops", C.c_void_p)]
+
+
+class SegmentOut(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("seg_off", C.c_void_p), ("q_begin", C.c_void_p), ("q_end", C.c_void_p), ("t_begin", C.c_void_p),
+                ("t_end", C.c_void_p)]
 
 
 class Pile(C.Structure):
@@ -274,6 +285,11 @@ def load_library(path=None):
                                    C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(Pile), C.POINTER(C.c_uint64)]
     L.s2k_pileup_consensus.argtypes = [C.c_void_p, C.POINTER(Pile), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_walks_segments.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(WalkOut), C.c_uint64, C.POINTER(ThreadOut), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(ThreadOut), C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(DeviceOut), C.c_uint32, C.POINTER(SegmentOut),
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.s2k_align_join.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(AlignOut), C.POINTER(AlignOut), C.POINTER(C.c_uint64)]
     L.s2k_partition_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.s2k_synth_bases_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.s2k_synth_hifi_lengths.restype = None
@@ -1075,6 +1091,104 @@ class Engine:
         out["n_ops_bound"] = m
         return out
 
+    def walks_segments(self, unitig_graph, walks, offsets, seq_len, q_begin, tgt_off, bad, source, outs, src_step=None, src_pos=None, seg_len=SEGMENT_LEN):
+        """Every walk cut into segment pairs at a thinned, strictly increasing subset of its anchor k-min-mers (s2k_walks_segments; the
+        rule is in include/s2k.h).  walks: a ReadWalks over unitig_graph (its paths give unitig, pos, count per step); offsets, seq_len:
+        as paths_walks takes them; q_begin: where every walk's query interval starts in the batch's bases (int64); tgt_off, bad: what
+        walks_targets returned; source: the ReadPaths that UnitigGraph.thread wrote for the same reads (path_off, pos, count, item);
+        outs: the batch's extraction (km_off, start); src_step (int64 per source step, NO_STEP = -1 for none; None: the identity) and
+        src_pos (int32; None: source.pos): where every source step went.  Two calls: the sizes, then the intervals.  -> dict of int64
+        GPU tensors seg_off (n_walks + 1), q_begin, q_end, t_begin, t_end (one per segment: Engine.align_pairs takes them unchanged),
+        the int n_segments and the SEGMENT_STATS counters in stats."""
+        import torch
+
+        ug, paths, dev = unitig_graph, walks.paths, walks.walk_off.device
+        if walks.qstart is None or walks.qend is None:
+            raise ValueError("walks_segments wants walks whose paths carry start and end")
+        t, n, ns, nr = ug.n_unitigs, ug.members.numel(), paths.n_steps, walks.walk_off.numel() - 1
+        uni_off, members, circular = (x.contiguous() for x in (ug.uni_off, ug.members, ug.circular))
+        member_off, out_off, overlap, seq_len = (x.contiguous() for x in (offsets[0], offsets[1], offsets[2], seq_len))
+        rec = {f: getattr(walks, f).contiguous() for f in ("walk_off", "first_step", "n_steps", "qstart", "qend", "path_start", "path_end", "flags")}
+        nw = rec["first_step"].numel()
+        q_begin, tgt_off, bad = q_begin.contiguous(), tgt_off.contiguous(), bad.contiguous()
+        if (uni_off.numel() != t + 1 or member_off.numel() != n or member_off.element_size() != 8 or out_off.numel() != t + 1 or overlap.numel() != 2 * t
+                or overlap.element_size() != 4 or seq_len.numel() != n or seq_len.element_size() != 4):
+            raise ValueError("walks_segments wants a UnitigGraph, the offsets Engine.unitig_member_offsets returned for it and one 32-bit seq_len per node")
+        if (any(rec[f].numel() != nw for f in rec if f != "walk_off") or [rec[f].element_size() for f in rec] != [8, 8, 4, 4, 4, 8, 8, 4]
+                or q_begin.numel() != nw or q_begin.element_size() != 8 or tgt_off.numel() != nw + 1 or tgt_off.element_size() != 8
+                or bad.numel() != nw or bad.element_size() != 1):
+            raise ValueError("walks_segments wants the walk records, one 64-bit q_begin and one bad byte per walk, and tgt_off of n_walks + 1 entries")
+        km_off, start = outs["km_off"].contiguous(), outs["start"].contiguous()
+        nsrc = source.n_steps
+        if source.path_off.numel() != nr + 1 or km_off.numel() != nr + 1 or km_off.element_size() != 8 or start.element_size() != 4:
+            raise ValueError("walks_segments wants the source paths and the extraction of the walks' reads")
+        maps = [None if x is None else x.contiguous() for x in (src_step, src_pos)]
+        if any(x is not None and (x.numel() != nsrc or x.element_size() != sz) for x, sz in zip(maps, (8, 4))):
+            raise ValueError("src_step holds one 64-bit entry and src_pos one 32-bit entry per source step")
+        wo = WalkOut()
+        wo.capacity = nw
+        for f, x in rec.items():
+            setattr(wo, f, x.data_ptr() if x.numel() else 0)
+        po, keep_p = _paths_struct(paths, ("unitig", "pos", "count"), ns)
+        so, keep_s = _paths_struct(source, ("pos", "count", "item"), nsrc)
+        d = DeviceOut()
+        d.km_off, d.start = km_off.data_ptr(), start.data_ptr() if start.numel() else 0
+        args = (self.ctx, nr, C.byref(wo), nw, C.byref(po), ns, _p(uni_off), _p(members, n), _p(circular, t), t, _p(member_off, n), _p(out_off), _p(overlap, t),
+                _p(seq_len, n), n, _p(q_begin, nw), _p(tgt_off), _p(bad, nw), C.byref(so), nsrc, _p(maps[0], nsrc), _p(maps[1], nsrc), C.byref(d), int(seg_len))
+        total, stats = C.c_uint64(0), (C.c_uint64 * SEGMENT_STATS_WORDS)()
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_walks_segments(*args, None, C.byref(total), stats))
+        m = int(total.value)
+        res = {"seg_off": torch.zeros(nw + 1, dtype=torch.int64, device=dev)}
+        for f in ("q_begin", "q_end", "t_begin", "t_end"):
+            res[f] = torch.zeros(max(m, 1), dtype=torch.int64, device=dev)
+        o = SegmentOut()
+        o.capacity = m
+        for f, x in res.items():
+            setattr(o, f, x.data_ptr())
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_walks_segments(*args, C.byref(o), C.byref(total), stats))
+        out = {f: (x if f == "seg_off" else x[:m]) for f, x in res.items()}
+        out.update(n_segments=m, stats={f: int(stats[i]) for i, f in enumerate(SEGMENT_STATS)})
+        return out
+
+    def align_join(self, seg_off, bad, segments):
+        """The segments' alignments put back together, one per walk (s2k_align_join; the rule is in include/s2k.h).  seg_off, bad: what
+        walks_segments and walks_targets returned; segments: what align_pairs returned for the segment pairs (anything with edits,
+        flags, ops_off, n_ops, matches, ops as attributes or keys).  Two calls: the size, then the runs.  -> dict of GPU tensors edits,
+        flags, n_ops, matches (int32 per walk), ops_off (int64, n_walks + 1, compact), ops (int32 per joined run) and the int
+        n_ops_total."""
+        import torch
+
+        get = segments.get if isinstance(segments, dict) else lambda f: getattr(segments, f)
+        sg = {f: get(f).contiguous() for f in ("edits", "flags", "ops_off", "n_ops", "matches", "ops")}
+        seg_off, bad = seg_off.contiguous(), bad.contiguous()
+        nw, nsg, dev = seg_off.numel() - 1, sg["ops_off"].numel() - 1, seg_off.device
+        if (seg_off.element_size() != 8 or bad.numel() != nw or bad.element_size() != 1 or sg["ops_off"].element_size() != 8
+                or any(sg[f].element_size() != 4 or sg[f].numel() < nsg for f in ("edits", "flags", "n_ops", "matches")) or sg["ops"].element_size() != 4):
+            raise ValueError("align_join wants seg_off, one bad byte per walk and the arrays align_pairs wrote for the segments")
+        si = AlignOut()
+        si.capacity = sg["ops"].numel()
+        for f, x in sg.items():
+            setattr(si, f, x.data_ptr() if x.numel() else 0)
+        args = (self.ctx, nw, _p(seg_off), _p(bad, nw), nsg, C.byref(si))
+        total = C.c_uint64(0)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_align_join(*args, None, C.byref(total)))
+        m = int(total.value)
+        res = {f: torch.zeros(max(nw, 1), dtype=torch.int32, device=dev) for f in ("edits", "flags", "n_ops", "matches")}
+        res["ops_off"] = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
+        res["ops"] = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)
+        o = AlignOut()
+        o.capacity = m
+        for f, x in res.items():
+            setattr(o, f, x.data_ptr())
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.s2k_align_join(*args, C.byref(o), C.byref(total)))
+        out = {f: (x if f == "ops_off" else x[:m] if f == "ops" else x[:nw]) for f, x in res.items()}
+        out["n_ops_total"] = m
+        return out
+
     @staticmethod
     def _pile_struct(planes, n_bases):
         """the s2k_pile over an (11, n_bases) int32 GPU tensor, rows in the order of PILEUP_PLANES"""
@@ -1693,7 +1807,7 @@ class UnitigGraph:
         lift = ContigLift(self, resolved, partner, u["copy_off"], place, tc, o["n_unitigs"])
         return contigs, x["node_origin"], {"copies": tc, "duplicated": u["n_duplicated"], "contigs": o["n_unitigs"]}, lift
 
-    def bridge(self, engine, paths, max_gap=16, max_slip=2):
+    def bridge(self, engine, paths, max_gap=16, max_slip=2, origin=False):
         """One batch's ReadPaths with the gaps that read errors cut into them bridged along this graph (Engine.paths_bridge;
         include/s2k.h: s2k_paths_bridge) -> (ReadPaths, stats).  Two consecutive steps of a read are joined when they lie on one unitig
         (merged into one step), or on two unitigs that an edge joins (the first extended to its unitig's end, the second back to position
@@ -1703,10 +1817,17 @@ class UnitigGraph:
         (a walk's items then counts positions).  stats = {"steps_in", "steps_out", "merged", "bridged"}.
         The defaults 16 and 2 come from the repeat fixture of the tests at l = 12, k = 5 with 1 % substitutions (one substitution
         removes up to k consecutive k-min-mers); they are not tuned on real data.  Not bridged: a wholly missing unitig between two
-        steps, and anything on a circular unitig; a gap is judged in items, not in bases."""
-        b = engine.paths_bridge(self, paths, max_gap, max_slip)
+        steps, and anything on a circular unitig; a gap is judged in items, not in bases.
+        origin=True asks Engine.paths_bridge for join and attaches the attribute origin, a PathOrigin, to the returned paths: the
+        source paths and where every source step went, which is what align_segmented needs to find the anchors of the bridged walks."""
+        import torch
+
+        b = engine.paths_bridge(self, paths, max_gap, max_slip, join=origin)
         stats = {"steps_in": paths.n_steps, "steps_out": b["n_steps"], "merged": b["n_merged"], "bridged": b["n_bridged"]}
-        return ReadPaths(b["path_off"], **{f: b[f] for f in ReadPaths.STEP_FIELDS + ("matched",) if f in b}), stats
+        out = ReadPaths(b["path_off"], **{f: b[f] for f in ReadPaths.STEP_FIELDS + ("matched",) if f in b})
+        if origin:  # an output step begins at every source step that is not merged into the one before it
+            out.origin = PathOrigin(paths, torch.cumsum(b["join"].ne(1), 0, dtype=torch.int64) - 1, paths.pos)
+        return out, stats
 
     def member_offsets(self, engine, node_seqs):
         """Where every member's piece starts in the unitigs' bases (Engine.unitig_member_offsets) -> (member_off, out_off, overlap,
@@ -1746,6 +1867,31 @@ class UnitigGraph:
         zero = lambda x: torch.where(bad, torch.zeros_like(x), x) if nw else x  # noqa: E731
         return WalkAlignments(a["edits"], zero(a["matches"]), zero(a["n_ops"]), a["ops_off"], a["ops"], flags)
 
+    def align_segmented(self, engine, walks, bases, read_off, sequences, node_seqs, outs, source=None, seg_len=SEGMENT_LEN, max_edits=ALIGN_MAX_EDITS):
+        """align for long, noisy reads: every walk is cut at anchor k-min-mers into pieces of about seg_len query bases, the pieces are
+        aligned by Engine.align_pairs and their CIGARs joined (Engine.walks_targets, Engine.walks_segments, Engine.align_pairs,
+        Engine.align_join; include/s2k.h) -> WalkAlignments, as align returns it, with the extra attribute segments: a dict of
+        n_segments, the SEGMENT_STATS counters and n_over_segments.  A walk is over only when one of its PIECES passes max_edits.
+        walks, bases, read_off, sequences: as for align; node_seqs: the NodeSequences self.walks took; outs: the batch's extraction
+        (km_off, start); source: a PathOrigin, the paths the reads were threaded into and where every step of them went -- None takes
+        walks.paths.origin where UnitigGraph.bridge(origin=True) left one, and otherwise the walks' own paths with the identity map.
+        The joined alignment is a valid global alignment of the walk; it is optimal between its cuts, not over the whole walk.  Walks
+        on paths that ContigLift.lift returned have no map yet (include/s2k.h: Not done): use align for them."""
+        if walks.qstart is None or walks.qend is None:
+            raise ValueError("align_segmented wants walks whose paths carry start and end (extract with start / end kept)")
+        if getattr(self, "overlap", None) is None:
+            raise ValueError("align_segmented wants the pair that self.sequences(engine, node_seqs) returned")
+        src = source or walks.paths.origin or PathOrigin(walks.paths)
+        t = engine.walks_targets(walks, walks.paths.unitig, sequences[0], sequences[1], self.overlap)
+        qb, _ = walk_query_intervals(walks, read_off)
+        sg = engine.walks_segments(self, walks, self.member_offsets(engine, node_seqs), node_seqs.seq_len, qb, t["tgt_off"], t["bad"], src.paths, outs,
+                                   src.src_step, src.src_pos, seg_len)
+        a = engine.align_pairs(bases, t["tgt"], sg["q_begin"], sg["q_end"], sg["t_begin"], sg["t_end"], max_edits)
+        j = engine.align_join(sg["seg_off"], t["bad"], a)
+        al = WalkAlignments(j["edits"], j["matches"], j["n_ops"], j["ops_off"], j["ops"], j["flags"])
+        al.segments = dict(sg["stats"], n_segments=sg["n_segments"], n_over_segments=int((a["flags"] & ALIGN_OVER).ne(0).sum()))
+        return al
+
     def pileup(self, engine, sequences):
         """An empty pile over this graph's draft bases -> Pileup.  sequences: the pair self.sequences returned.  Pileup.add takes the
         walks and alignments of one batch after self.align; Pileup.consensus gives the polished bases.  It works as it is on
@@ -1766,6 +1912,15 @@ class UnitigGraph:
             seq = (sequences[0].cpu().numpy().view(np.uint64), sequences[1].cpu().numpy(), self.overlap.cpu().numpy().view(np.uint32))
         write_unitig_gfa(path, self.uni_off.cpu().numpy().view(np.uint64), self.members.cpu().numpy().view(np.uint32), self.counts.cpu().numpy(),
                          self.edge_keys.cpu().numpy().view(np.uint64), self.edge_counts.cpu().numpy().view(np.uint32), members=members, sequences=seq)
+
+
+class PathOrigin:
+    """Where the steps of a batch's ReadPaths came from (UnitigGraph.bridge(origin=True); include/s2k.h: s2k_walks_segments): paths, the
+    source ReadPaths that UnitigGraph.thread wrote; src_step (int64 per source step, NO_STEP = -1 for none; None: the identity), the
+    step it went into; src_pos (int32; None: paths.pos), the position of its first item on that step's oriented unitig."""
+
+    def __init__(self, paths, src_step=None, src_pos=None):
+        self.paths, self.src_step, self.src_pos = paths, src_step, src_pos
 
 
 class ContigLift:
@@ -1804,6 +1959,7 @@ class ReadPaths:
     def __init__(self, path_off, unitig, pos, count, item, flags, start=None, end=None, matched=None):
         self.path_off, self.unitig, self.pos, self.count, self.item, self.flags, self.start, self.end = path_off, unitig, pos, count, item, flags, start, end
         self.matched = matched
+        self.origin = None  # a PathOrigin on the paths UnitigGraph.bridge(origin=True) returned
 
     @property
     def n_steps(self):

@@ -6,10 +6,10 @@
 // kernel; the scan's first n_nodes entries are the member offsets.
 //
 // s2k_paths_walks, runs of steps (s2k_runs_dev.h), tiles of TB_TILE steps (lane tid holds steps r * 256 + tid):
-//  1. walks_check_kernel: the shared rules of s2k_span_dev.h (path_off_ok, steps_ok, unitig_row_ok); uni_off runs from 0 to n_nodes;
-//     out_off does not decrease and no unitig has 2^32 bases or more; every member < 2 n_nodes, its offset inside its unitig's bases
-//     (the unitig by a search of uni_off).  One flag word, read by the host before anything is written; every read is clamped to
-//     the arrays whatever they hold.
+//  1. walks_check_kernel: the shared rules of s2k_span_dev.h (path_off_ok, steps_ok, unitig_row_ok) and of s2k_coords_dev.h
+//     (lift_unitig_ok, lift_member_ok): uni_off runs from 0 to n_nodes; out_off does not decrease and no unitig has 2^32 bases or
+//     more; every member < 2 n_nodes, its offset inside its unitig's bases (the unitig by a search of uni_off).  One flag word, read
+//     by the host before anything is written; every read is clamped to the arrays whatever they hold.
 //  2. walks_count_kernel: follow_tile (s2k_span_dev.h) gives the edge every step follows, to workspace and LDS.  Heads: the step
 //     follows no edge; tails: the step after it follows none.  Per step adv(U) to workspace.
 //  3. launch_scan_u32 over adv and over count: a walk's path_len, path_end and items are differences of two prefix entries.
@@ -23,6 +23,7 @@
 
 #include "../../include/s2k.h"
 #include "s2k_call.h"
+#include "s2k_coords_dev.h"
 #include "s2k_dev.h"
 #include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
@@ -34,30 +35,11 @@
 namespace s2k {
 namespace {
 
-// the decomposition and where its members lie in base space
-struct Lift {
-    const uint64_t *uni_off, *member_off, *out_off;
-    const uint32_t *members, *seq_len, *overlap;
-    const uint8_t *circular;
-    uint64_t n_unitigs, n_nodes;
-};
-
 struct WalkWs {
     uint32_t *edge, *adv; // per step: the edge it follows (SP_NONE: none); adv(unitig)
     uint64_t *A, *C;      // n_steps + 1: the exclusive prefixes of adv and of count
     RunWs run;            // open: the tile's first step follows an edge
 };
-
-// the last t in [0, n_unitigs - 1] with uni_off[t] <= x: every index stays inside uni_off whatever it holds
-__device__ inline uint64_t unitig_of(const uint64_t *__restrict__ uni_off, uint64_t n_unitigs, uint64_t x) {
-    uint64_t lo = 0, hi = n_unitigs - 1;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (uni_off[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(UT) void walks_check_kernel(Paths p, Csr g, Lift v, uint64_t n_edges, uint32_t *__restrict__ bad) {
     const uint64_t n_ids = 2 * v.n_unitigs;
@@ -66,16 +48,10 @@ __global__ __launch_bounds__(UT) void walks_check_kernel(Paths p, Csr g, Lift v,
     if (!steps_ok(p.unitig, p.pos, p.count, p.n_steps, v.uni_off, v.circular, n_ids, i0, stride)) ok = false;
     for (uint64_t u = i0; u < n_ids; u += stride) {
         if (!unitig_row_ok(g, v.uni_off, u, n_ids, n_edges)) ok = false;
-        if (u & 1) continue;
-        const uint64_t t = u >> 1, a = v.uni_off[t], b = v.uni_off[t + 1], oa = v.out_off[t], ob = v.out_off[t + 1];
-        if (b > v.n_nodes || (t == 0 && a != 0) || (t == v.n_unitigs - 1 && b != v.n_nodes)) ok = false; // n_nodes < 2^31
-        if (oa > ob || ob - oa >= (1ull << 32)) ok = false;
+        if (!(u & 1) && !lift_unitig_ok(v, u >> 1)) ok = false;
     }
-    for (uint64_t x = i0; x < v.n_nodes; x += stride) {
-        if (v.members[x] >= 2 * v.n_nodes) ok = false;
-        const uint64_t t = unitig_of(v.uni_off, v.n_unitigs, x), o = v.member_off[x];
-        if (o < v.out_off[t] || o > v.out_off[t + 1]) ok = false;
-    }
+    for (uint64_t x = i0; x < v.n_nodes; x += stride)
+        if (!lift_member_ok(v, x)) ok = false;
     if (!ok) atomicOr(bad, 1u);
 }
 
@@ -108,26 +84,6 @@ __global__ __launch_bounds__(TB_THREADS) void walks_count_kernel(Paths p, Csr g,
         ws.run, t0, p.n_steps, [&](int, int i) { return valid(i) && s.E[i] == SP_NONE; }, [&](int, int i) { return valid(i) && s.E[i + 1] == SP_NONE; },
         [&] { return s.E[1] != SP_NONE; });
     block_add(n, totals);
-}
-
-// The base interval [*lo, *hi) of position q of the oriented unitig U on its own strand (include/s2k.h, "Base interval of a
-// position"), *L = the unitig's bases.  A linear unitig clamps hi to L.  A circular one does not; on its twin strand the interval is
-// shifted by *w, the multiple of L that brings lo into [0, L) (0 elsewhere).
-__device__ __forceinline__ void interval(const Lift &v, uint32_t U, uint64_t q, uint64_t *lo, uint64_t *hi, uint64_t *L, uint64_t *w) {
-    const uint64_t t = U >> 1, a = v.uni_off[t], len = v.uni_off[t + 1] - a, o0 = v.out_off[t];
-    const uint64_t x = a + ((U & 1u) ? len - 1 - q : q);
-    const uint64_t o = v.member_off[x] - o0;
-    uint64_t e = o + v.seq_len[v.members[x] >> 1];
-    *L = v.out_off[t + 1] - o0;
-    *w = 0;
-    if (!v.circular[t]) e = std::min(e, *L);
-    if (!(U & 1u)) {
-        *lo = o, *hi = e;
-        return;
-    }
-    if (e > *L) *w = *L ? ((e - 1) / *L) * *L : e;
-    *lo = *w + *L - e;
-    *hi = *w + *L - o;
 }
 
 struct WalkIo {
