@@ -241,6 +241,8 @@ struct s2k_ctx {
     uint32_t lookback_giveups = 0;                // HpcSimd calls that were run again because a look-back gave up; two make the pre-pass the default of the context
     bool force_full_runs = false;                 // S2K_FULL_RUNS=1 (A/B, tests): HpcSimd counts the runs of every read in a pre-pass instead of looking back from tile to tile
     bool trace = false;                           // S2K_TRACE: one line on stderr whenever a call is run again (record pool too small, a fall-back to another path)
+    bool poison_ws = false;                       // S2K_POISON_WS=<0..255> (tests): every hand-out of count_tab is filled with that byte first
+    uint8_t poison_byte = 0;
     uint64_t host_batch = 1ull << 29;             // bases per sub-batch of s2k_extract (s2k_set_host_batch)
     // counters, XOR shards and the tile cursors of up to MAX_DESC_CHUNKS launches are ONE allocation (d_counts is its start): one memset
     // per call instead of three (every launch in front of the first minimizer kernel is ~7 us of an otherwise idle device)
@@ -336,7 +338,15 @@ hipError_t ctx_sync(s2k_ctx *c) {
 }
 int ctx_device(s2k_ctx *c) { return c->device; }
 void ctx_set_error(s2k_ctx *c, const char *what) { c->err = what; }
-void *ctx_count_table(s2k_ctx *c, size_t bytes) { return c->count_tab.ensure(bytes) == hipSuccess ? c->count_tab.p : nullptr; }
+void *ctx_count_table(s2k_ctx *c, size_t bytes) {
+    if (c->count_tab.ensure(bytes) != hipSuccess) return nullptr;
+    // S2K_POISON_WS: the whole buffer, on the stream every caller queues its work on, so nothing of an earlier hand-out survives this one
+    if (c->poison_ws && c->count_tab.p) {
+        if (hipMemsetAsync(c->count_tab.p, c->poison_byte, c->count_tab.bytes, ctx_stream(c)) != hipSuccess) return nullptr;
+        if (c->trace) fprintf(stderr, "s2k: workspace poisoned: 0x%02x x %zu bytes\n", (unsigned)c->poison_byte, c->count_tab.bytes);
+    }
+    return c->count_tab.p;
+}
 } // namespace s2k
 
 namespace {
@@ -883,6 +893,8 @@ s2k_ctx *s2k_create(int device, s2k_status *status) {
     if (const char *e = getenv("S2K_DESC_CHUNKS")) // tuning / A-B runs: chunks of tiles per call on the descriptor path (1 = no second stream)
         if (atoi(e) >= 1 && atoi(e) <= 64) ctx->desc_chunks = (uint32_t)atoi(e);
     if (const char *e = getenv("S2K_TRACE")) ctx->trace = atoi(e) != 0;
+    if (const char *e = getenv("S2K_POISON_WS")) // tests: poison the count workspace at every hand-out (ctx_count_table)
+        if (*e && atoi(e) >= 0 && atoi(e) <= 255) ctx->poison_ws = true, ctx->poison_byte = (uint8_t)atoi(e);
     if (const char *e = getenv("S2K_FULL_RUNS")) ctx->force_full_runs = atoi(e) != 0;
     {
         std::lock_guard<std::mutex> lk(g_ctx_mu);

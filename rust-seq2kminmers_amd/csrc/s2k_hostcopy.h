@@ -93,7 +93,8 @@ hipError_t ctx_mark(s2k_ctx *c);
 hipError_t ctx_sync(s2k_ctx *c);
 int ctx_device(s2k_ctx *c);
 void ctx_set_error(s2k_ctx *c, const char *what);
-// grow-only device buffer of the context for s2k_count_device / s2k_partition_device (nullptr: allocation failed)
+// grow-only device buffer of the context: the workspace of every call built on s2k_call.h (nullptr: allocation failed).  Never cleared;
+// under S2K_POISON_WS the whole buffer is filled with the poison byte on ctx_stream(c) before the pointer is returned.
 void *ctx_count_table(s2k_ctx *c, size_t bytes);
 } // namespace s2k
 

@@ -385,25 +385,34 @@ def _raw_adjacency(eng, ek, n_nodes, want_dst=True, guard=8):
     return s, ro.cpu().numpy(), dst.cpu().numpy()
 
 
+def _random_edge_table(rng, n_nodes, m):
+    """about m distinct edge keys over 2 n_nodes oriented ids, the smallest and the largest key among them (none when m == 0)"""
+    ids = 2 * n_nodes
+    if not m:
+        return np.zeros(0, dtype=np.uint64)
+    e = np.unique(rng.integers(0, ids, size=m, dtype=np.uint64) << np.uint64(32) | rng.integers(0, ids, size=m, dtype=np.uint64))
+    return np.unique(np.concatenate([e, [np.uint64(0), np.uint64(ids - 1) << np.uint64(32) | np.uint64(ids - 1)]]))
+
+
+def _check_adjacency(eng, e, n_nodes):
+    """s2k_graph_adjacency against adjacency_reference, with and without d_dst, guards untouched"""
+    ids = 2 * n_nodes
+    ro_w, dst_w = adjacency_reference(e, n_nodes)
+    for want_dst in (True, False):
+        s, ro, dst = _raw_adjacency(eng, e, n_nodes, want_dst)
+        assert s == 0
+        assert ro[:ids + 1].view(np.uint64).tobytes() == ro_w.tobytes() and (ro[ids + 1:] == -3).all()
+        if want_dst:
+            assert dst[:len(e)].view(np.uint32).tobytes() == dst_w.tobytes() and (dst[len(e):] == -3).all()
+        else:
+            assert (dst == -3).all()
+
+
 @pytest.mark.gpu
 def test_adjacency_random_tables_and_refusals(eng):
     rng = np.random.default_rng(33)
     for n_nodes, m in ((1, 3), (3, 5), (1000, 3000), (1000, 30), (200000, 900000), (3, 0)):
-        ids = 2 * n_nodes
-        if m:
-            e = np.unique(rng.integers(0, ids, size=m, dtype=np.uint64) << np.uint64(32) | rng.integers(0, ids, size=m, dtype=np.uint64))
-            e = np.unique(np.concatenate([e, [np.uint64(0), np.uint64(ids - 1) << np.uint64(32) | np.uint64(ids - 1)]]))
-        else:
-            e = np.zeros(0, dtype=np.uint64)
-        ro_w, dst_w = adjacency_reference(e, n_nodes)
-        for want_dst in (True, False):
-            s, ro, dst = _raw_adjacency(eng, e, n_nodes, want_dst)
-            assert s == 0
-            assert ro[:ids + 1].view(np.uint64).tobytes() == ro_w.tobytes() and (ro[ids + 1:] == -3).all()
-            if want_dst:
-                assert dst[:len(e)].view(np.uint32).tobytes() == dst_w.tobytes() and (dst[len(e):] == -3).all()
-            else:
-                assert (dst == -3).all()
+        _check_adjacency(eng, _random_edge_table(rng, n_nodes, m), n_nodes)
     # an unsorted table, a duplicate, and node ids out of range are refused with nothing written
     e = np.unique(rng.integers(0, 2000, size=5000, dtype=np.uint64) << np.uint64(32) | rng.integers(0, 2000, size=5000, dtype=np.uint64))
     bad = []
