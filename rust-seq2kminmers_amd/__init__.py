@@ -370,6 +370,33 @@ def _paths_result(res, per_step, m, n_steps, **totals):
     return {**{f: (x if f == "path_off" else x[:n_steps] if f in per_step else x[:m]) for f, x in res.items()}, "n_steps": m, **totals}
 
 
+def _walk_args(name, walks, step_unitig, out_off, out, overlap):
+    """what walks_targets and walks_pileup (name) share -> (n_walks, device, the C arguments n_walks .. n_unitigs, the tensors to keep alive)"""
+    rec = [getattr(walks, f).contiguous() for f in ("first_step", "n_steps", "path_start", "path_end", "flags")]
+    step_unitig, out_off, out, overlap = keep = [x.contiguous() for x in (step_unitig, out_off, out, overlap)]
+    nw, ns, t = rec[0].numel(), step_unitig.numel(), out_off.numel() - 1
+    if (any(x.numel() != nw for x in rec) or [x.element_size() for x in rec] != [8, 4, 8, 8, 4] or step_unitig.element_size() != 4
+            or out_off.element_size() != 8 or out.element_size() != 1 or overlap.numel() != 2 * t or overlap.element_size() != 4):
+        raise ValueError(name + " wants the walk records, one 32-bit unitig per step, and the out_off, out and overlap of the unitig sequences")
+    return nw, out_off.device, (nw, *(_p(x, nw) for x in rec), _p(step_unitig, ns), ns, _p(out_off), _p(out, out.numel()), out.numel(), _p(overlap, t), t), rec + keep
+
+
+def _align_out(n, dev, m=None, res=None, fields=None):
+    """the results of align_pairs / align_join over n records -> (AlignOut, res, cut): res holds edits, flags, n_ops, matches (int32 per record),
+    ops_off (int64, n + 1) and, once the number of runs m is known, ops; the struct names `fields` (None: all) with capacity m; cut(): res as returned"""
+    import torch
+
+    if res is None:
+        res = {f: torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for f in ("edits", "flags", "n_ops", "matches")}
+        res["ops_off"] = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    o = AlignOut(m or 0)
+    if m is not None:
+        res["ops"] = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)
+    for f in fields or res:
+        setattr(o, f, res[f].data_ptr())
+    return o, res, lambda: {f: (x if f == "ops_off" else x[:m] if f == "ops" else x[:n]) for f, x in res.items()}
+
+
 class Engine:
     """One s2k_ctx (one per thread and device, like one KminmersIterator per thread in src/main.rs:65-79)."""
 
@@ -1040,22 +1067,16 @@ class Engine:
         GPU tensors tgt_off (int64, n_walks + 1), tgt (uint8), bad (uint8 per walk), and the int n_bytes."""
         import torch
 
-        rec = [getattr(walks, f).contiguous() for f in ("first_step", "n_steps", "path_start", "path_end", "flags")]
-        step_unitig, out_off, out, overlap = (x.contiguous() for x in (step_unitig, out_off, out, overlap))
-        nw, ns, t, dev = rec[0].numel(), step_unitig.numel(), out_off.numel() - 1, out_off.device
-        if (any(x.numel() != nw for x in rec) or [x.element_size() for x in rec] != [8, 4, 8, 8, 4] or step_unitig.element_size() != 4
-                or out_off.element_size() != 8 or out.element_size() != 1 or overlap.numel() != 2 * t or overlap.element_size() != 4):
-            raise ValueError("walks_targets wants the walk records, one 32-bit unitig per step, and the out_off, out and overlap of the unitig sequences")
-        args = (self.ctx, nw, *(_p(x, nw) for x in rec), _p(step_unitig, ns), ns, _p(out_off), _p(out, out.numel()), out.numel(), _p(overlap, t), t)
+        nw, dev, args, keep = _walk_args("walks_targets", walks, step_unitig, out_off, out, overlap)
         tgt_off = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
         bad = torch.zeros(max(nw, 1), dtype=torch.uint8, device=dev)
         nb = C.c_uint64(0)
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_walks_targets(*args, None, None, None, 0, C.byref(nb)))
+        self._check(self.lib.s2k_walks_targets(self.ctx, *args, None, None, None, 0, C.byref(nb)))
         n = int(nb.value)
         tgt = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_walks_targets(*args, _p(tgt_off), _p(tgt), _p(bad), n, C.byref(nb)))
+        self._check(self.lib.s2k_walks_targets(self.ctx, *args, _p(tgt_off), _p(tgt), _p(bad), n, C.byref(nb)))
         return {"tgt_off": tgt_off, "tgt": tgt[:n], "bad": bad[:nw], "n_bytes": n}
 
     def align_pairs(self, query, target, q_begin, q_end, t_begin, t_end, max_edits=ALIGN_MAX_EDITS):
@@ -1072,24 +1093,15 @@ class Engine:
         if any(x.numel() != n or x.element_size() != 8 for x in iv) or query.element_size() != 1 or target.element_size() != 1:
             raise ValueError("align_pairs wants two byte pools and four 64-bit interval arrays of one length")
         args = (self.ctx, _p(query, query.numel()), query.numel(), _p(target, target.numel()), target.numel(), *(_p(x, n) for x in iv), n, int(max_edits))
-        res = {f: torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for f in ("edits", "flags", "n_ops", "matches")}
-        res["ops_off"] = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        o = AlignOut()
-        for f in ("edits", "flags", "ops_off"):
-            setattr(o, f, res[f].data_ptr())
+        o, res, _ = _align_out(n, dev, fields=("edits", "flags", "ops_off"))
         nb = C.c_uint64(0)
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_align_pairs(*args, C.byref(o), C.byref(nb)))
         m = int(nb.value)
-        res["ops"] = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)
-        o.capacity = m
-        for f in ("n_ops", "matches", "ops"):
-            setattr(o, f, res[f].data_ptr())
+        o, res, cut = _align_out(n, dev, m, res)
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_align_pairs(*args, C.byref(o), C.byref(nb)))
-        out = {f: (x if f == "ops_off" else x[:m] if f == "ops" else x[:n]) for f, x in res.items()}
-        out["n_ops_bound"] = m
-        return out
+        return {**cut(), "n_ops_bound": m}
 
     def walks_segments(self, unitig_graph, walks, offsets, seq_len, q_begin, tgt_off, bad, source, outs, src_step=None, src_pos=None, seg_len=SEGMENT_LEN):
         """Every walk cut into segment pairs at a thinned, strictly increasing subset of its anchor k-min-mers (s2k_walks_segments; the
@@ -1176,18 +1188,10 @@ class Engine:
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_align_join(*args, None, C.byref(total)))
         m = int(total.value)
-        res = {f: torch.zeros(max(nw, 1), dtype=torch.int32, device=dev) for f in ("edits", "flags", "n_ops", "matches")}
-        res["ops_off"] = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
-        res["ops"] = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)
-        o = AlignOut()
-        o.capacity = m
-        for f, x in res.items():
-            setattr(o, f, x.data_ptr())
+        o, _, cut = _align_out(nw, dev, m)
         torch.cuda.synchronize(dev)
         self._check(self.lib.s2k_align_join(*args, C.byref(o), C.byref(total)))
-        out = {f: (x if f == "ops_off" else x[:m] if f == "ops" else x[:nw]) for f, x in res.items()}
-        out["n_ops_total"] = m
-        return out
+        return {**cut(), "n_ops_total": m}
 
     @staticmethod
     def _pile_struct(planes, n_bases):
@@ -1209,21 +1213,16 @@ class Engine:
         batch -- it gains the votes.  -> dict of the PILEUP_STATS counters of this call."""
         import torch
 
-        rec = [getattr(walks, f).contiguous() for f in ("first_step", "n_steps", "path_start", "path_end", "flags")]
-        step_unitig, out_off, out, overlap, query, q_begin = (x.contiguous() for x in (step_unitig, out_off, out, overlap, query, q_begin))
+        nw, dev, wargs, keep = _walk_args("walks_pileup", walks, step_unitig, out_off, out, overlap)
+        query, q_begin = query.contiguous(), q_begin.contiguous()
         al = [getattr(alignments, f).contiguous() for f in ("flags", "ops_off", "n_ops", "ops")]
-        nw, ns, t, dev = rec[0].numel(), step_unitig.numel(), out_off.numel() - 1, out_off.device
-        if (any(x.numel() != nw for x in rec) or [x.element_size() for x in rec] != [8, 4, 8, 8, 4] or step_unitig.element_size() != 4
-                or out_off.element_size() != 8 or out.element_size() != 1 or overlap.numel() != 2 * t or overlap.element_size() != 4):
-            raise ValueError("walks_pileup wants the walk records, one 32-bit unitig per step, and the out_off, out and overlap of the unitig sequences")
         if (query.element_size() != 1 or q_begin.numel() != nw or q_begin.element_size() != 8 or [x.element_size() for x in al] != [4, 8, 4, 4]
                 or al[0].numel() < nw or al[2].numel() < nw or al[1].numel() != nw + 1):
             raise ValueError("walks_pileup wants the batch's bases, one 64-bit interval start per walk and the alignment arrays of these walks")
         pile = self._pile_struct(planes, out.numel())
         stats = (C.c_uint64 * PILEUP_STATS_WORDS)()
         torch.cuda.synchronize(dev)
-        self._check(self.lib.s2k_walks_pileup(self.ctx, nw, *(_p(x, nw) for x in rec), _p(step_unitig, ns), ns, _p(out_off), _p(out, out.numel()), out.numel(),
-                                              _p(overlap, t), t, _p(query, query.numel()), query.numel(), _p(q_begin, nw), _p(al[0], nw), _p(al[1]), _p(al[2], nw),
+        self._check(self.lib.s2k_walks_pileup(self.ctx, *wargs, _p(query, query.numel()), query.numel(), _p(q_begin, nw), _p(al[0], nw), _p(al[1]), _p(al[2], nw),
                                               _p(al[3], al[3].numel()), al[3].numel(), int(max_shift), C.byref(pile), stats))
         return {f: int(stats[i]) for i, f in enumerate(PILEUP_STATS)}
 

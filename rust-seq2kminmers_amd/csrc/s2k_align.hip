@@ -36,6 +36,7 @@
 #include "../../include/s2k.h"
 #include "s2k_bytes_dev.h"
 #include "s2k_call.h"
+#include "s2k_cigar_dev.h"
 #include "s2k_dev.h"
 #include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
@@ -260,7 +261,7 @@ __device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_S
 
 // a run to the staging words, which grow downwards from top
 __device__ __forceinline__ void flush_run(int32_t *__restrict__ ws, uint32_t top, uint32_t &n, uint32_t op, uint32_t len) {
-    if (len) ws[top - 1 - n++] = (int32_t)(len << 4 | op);
+    if (len) ws[top - 1 - n++] = (int32_t)run_pack(op, len);
 }
 
 __global__ __launch_bounds__(AL_T) void al_trace_kernel(Pairs ps, unsigned long long *__restrict__ ctr, int32_t *__restrict__ wave_ws, uint32_t ws_words,
@@ -345,20 +346,14 @@ s2k_status s2k_walks_targets(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_f
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return S2K_ERR_DEVICE;
     Layout L;
     const auto flag = L.bytes<uint32_t>(16);
-    const auto adv_p = L.take<uint32_t>(n_steps), brk_p = L.take<uint32_t>(n_steps);
-    const auto G_p = L.take<uint64_t>(n_steps + 1), J_p = L.take<uint64_t>(n_steps + 1);
-    const auto len_p = L.take<uint32_t>(n_walks);
-    const auto bad_p = L.take<uint8_t>(n_walks);
+    const TgPieces tp = carve_targets(L, n_steps, n_walks, true);
     const auto off_p = L.take<uint64_t>(n_walks + 1);
     const auto tmp_p = L.bytes<uint64_t>(scan_tmp_bytes(std::max(n_steps, n_walks)));
     char *w = L.alloc(ctx);
     if (!w) return c.nomem();
     uint32_t *bad = flag(w);
     const TgIn in{d_first_step, d_path_start, d_path_end, d_n_steps, d_flags, d_step_unitig, d_out_off, d_out, d_overlap, n_walks, n_steps, n_unitigs, n_bases};
-    uint32_t hbad = c.check(bad, 16, bad, [&] {
-        hipLaunchKernelGGL(tg_check_kernel, dim3(grid_for(std::max<uint64_t>(std::max(n_steps, n_walks), std::max<uint64_t>(n_unitigs, 1)))), dim3(UT), 0, c.st,
-                           in, bad);
-    });
+    uint32_t hbad = c.check(bad, 16, bad, [&] { launch_tg_check(c, in, bad); });
     if (!c.ok()) return c.device_error();
     if (hbad)
         return c.invalid("a walk whose steps lie outside the paths, a step on a unitig >= n_unitigs, out_off that decreases or passes n_bases, or a unitig "
@@ -370,17 +365,9 @@ s2k_status s2k_walks_targets(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_f
         }
         return S2K_OK;
     }
-    if (n_steps) {
-        hipLaunchKernelGGL(tg_steps_kernel, dim3((unsigned)((n_steps + AL_T - 1) / AL_T)), dim3(AL_T), 0, c.st, in, adv_p(w), brk_p(w));
-        c.launched();
-        c.scan(adv_p(w), n_steps, G_p(w), tmp_p(w));
-        c.scan(brk_p(w), n_steps, J_p(w), tmp_p(w));
-    }
-    if (c.ok()) {
-        hipLaunchKernelGGL(tg_len_kernel, dim3((unsigned)((n_walks + AL_T - 1) / AL_T)), dim3(AL_T), 0, c.st, in, G_p(w), J_p(w), len_p(w), bad_p(w), bad);
-        c.launched();
-    }
-    c.scan(len_p(w), n_walks, off_p(w), tmp_p(w));
+    launch_tg_steps(c, in, tp, w, tmp_p(w));
+    launch_tg_lens(c, in, tp, w, bad);
+    c.scan(tp.len(w), n_walks, off_p(w), tmp_p(w));
     uint64_t total = 0;
     c.fetch(&total, off_p(w) + n_walks, 8);
     c.fetch(&hbad, bad, 4);
@@ -391,11 +378,8 @@ s2k_status s2k_walks_targets(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_f
     const uint64_t nb = (total + AL_T * 16 - 1) / (AL_T * 16);
     if (d_tgt && nb >= (1ull << 31)) return c.invalid("2^43 bytes or more");
     if (d_tgt_off) c.copy(d_tgt_off, off_p(w), (n_walks + 1) * 8, hipMemcpyDeviceToDevice);
-    if (d_bad) c.copy(d_bad, bad_p(w), n_walks, hipMemcpyDeviceToDevice);
-    if (c.ok() && d_tgt && total) {
-        hipLaunchKernelGGL(tg_copy_kernel, dim3((unsigned)nb), dim3(AL_T), 0, c.st, in, G_p(w), off_p(w), d_tgt, total);
-        c.launched();
-    }
+    if (d_bad) c.copy(d_bad, tp.bad8(w), n_walks, hipMemcpyDeviceToDevice);
+    if (d_tgt && total) c.launch(tg_copy_kernel, (unsigned)nb, AL_T, in, tp.G(w), off_p(w), d_tgt, total);
     if (!c.sync()) return c.device_error();
     return S2K_OK;
 }
@@ -434,11 +418,10 @@ s2k_status s2k_align_pairs(s2k_ctx *ctx, const uint8_t *d_query, uint64_t n_quer
         if (!w) return c.nomem();
         unsigned long long *ctr = words(w);
         uint32_t *bad = (uint32_t *)(ctr + 1), *dmax = bad + 1;
-        const uint32_t hbad = c.check(ctr, 64, bad, [&] { hipLaunchKernelGGL(al_check_kernel, dim3(grid_for(n_pairs)), dim3(UT), 0, c.st, ps, bad); });
+        const uint32_t hbad = c.check(ctr, 64, bad, [&] { c.launch(al_check_kernel, grid_for(n_pairs), UT, ps, bad); });
         if (!c.ok()) return c.device_error();
         if (hbad) return c.invalid("a begin above its end, an interval outside its pool, or an interval of 2^31 bytes or more");
-        hipLaunchKernelGGL(al_score_kernel, dim3(blocks), dim3(AL_T), 0, c.st, ps, max_edits, ctr, dmax, edits_p(w), flags_p(w), slots_p(w));
-        c.launched();
+        c.launch(al_score_kernel, blocks, AL_T, ps, max_edits, ctr, dmax, edits_p(w), flags_p(w), slots_p(w));
         c.scan(slots_p(w), n_pairs, off_p(w), tmp_p(w));
         c.fetch(&total, off_p(w) + n_pairs, 8);
         c.fetch(&emax, dmax, 4);
@@ -462,11 +445,7 @@ s2k_status s2k_align_pairs(s2k_ctx *ctx, const uint8_t *d_query, uint64_t n_quer
     char *w = L.alloc(ctx);
     if (!w) return c.nomem();
     c.zero(words(w), 64);
-    if (c.ok()) {
-        hipLaunchKernelGGL(al_trace_kernel, dim3(tblocks), dim3(AL_T), 0, c.st, ps, words(w), h_p(w), ws_words, out->edits, out->ops_off, out->ops,
-                           out->n_ops, out->matches);
-        c.launched();
-    }
+    c.launch(al_trace_kernel, tblocks, AL_T, ps, words(w), h_p(w), ws_words, out->edits, out->ops_off, out->ops, out->n_ops, out->matches);
     if (!c.sync()) return c.device_error();
     return S2K_OK;
 }

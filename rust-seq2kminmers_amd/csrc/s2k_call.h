@@ -60,6 +60,12 @@ struct Call {
     void launched() { // after hipLaunchKernelGGL
         if (ok()) e = hipGetLastError();
     }
+    template <typename K, typename... A>
+    void launch(K kernel, unsigned grid, unsigned block, const A &...args) { // the kernel on st, and its launch error
+        if (!ok()) return;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, args...);
+        e = hipGetLastError();
+    }
     void scan(const uint32_t *in, uint64_t n, uint64_t *out /*n+1*/, uint64_t *tmp) {
         if (ok()) e = launch_scan_u32(in, n, out, tmp, 0, st);
     }
@@ -67,18 +73,24 @@ struct Call {
         if (ok()) e = ctx_sync(ctx);
         return ok();
     }
-    // zero `bytes` at z, launch() the kernels that set *flag (inside z's range), fetch it, wait: the flag, for the caller's refusal
-    template <typename F>
-    uint32_t check(void *z, size_t bytes, const uint32_t *flag, F launch) {
+    // zero `bytes` at z, queue() the kernels that set *flag (inside z's range), fetch it, more() (the caller's further fetches), wait:
+    // the flag, for the caller's refusal
+    template <typename F, typename M>
+    uint32_t check(void *z, size_t bytes, const uint32_t *flag, F queue, M more) {
         uint32_t h = 0;
         zero(z, bytes);
         if (ok()) {
-            launch();
+            queue();
             launched();
         }
         fetch(&h, flag, 4);
+        more();
         sync();
         return h;
+    }
+    template <typename F>
+    uint32_t check(void *z, size_t bytes, const uint32_t *flag, F queue) {
+        return check(z, bytes, flag, queue, [] {});
     }
 
     s2k_status refuse(s2k_status s, const char *what) const {

@@ -1,8 +1,8 @@
 // s2k_compact_dev.h -- the stable stream compaction over tiles of TB_TILE items that the filter and the edges (s2k_table.hip,
 // DESIGN.md §3.8, §3.9) and the induced subgraph (s2k_simplify.hip, §3.12) share, and the one workgroup scan.
 //
-// Lane tid of a tile's workgroup holds items r * TB_THREADS + tid, r = 0 .. TB_Q - 1.  A count kernel ballots its items (word
-// r * 4 + wave of the tile), stores the mask and its popcount and ends in tile_prefixes; launch_scan_u32 over tile_kept gives
+// Lane tid of a tile's workgroup holds items r * TB_THREADS + tid, r = 0 .. TB_Q - 1.  A count kernel ballots its items round by round
+// (tile_ballot: word r * 4 + wave of the tile, the mask and its popcount) and ends in a barrier and tile_prefixes; launch_scan_u32 over tile_kept gives
 // tile_off; a write kernel takes its slots from tile_slots, stages what it keeps in LDS at them and lets the run go with leave_run.
 #pragma once
 #include <algorithm>
@@ -49,7 +49,21 @@ struct CompactWs {
     uint64_t *tile_off;  // n_tiles + 1
 };
 
-// after the TB_Q ballots of a tile (wc[r * 4 + wave] = the popcount of that word): the words' prefixes and the tile's total
+// round r of a count kernel: the wave's ballot of `kept` (false for an item past n), its popcount to wc and the mask to its word.
+// (filter_count_kernel, s2k_table.hip, and vote_count_kernel, s2k_vote.hip, write the same lines out: through this function their
+// fused look-ups are scheduled into 91 and 90 VGPRs against 78, a wave per SIMD less.)
+__device__ __forceinline__ void tile_ballot(uint32_t *wc, int r, uint64_t t0, uint64_t n, const CompactWs &ws, bool kept) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint64_t m = __ballot(kept);
+    const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64; // first item of this wave's word
+    if (lane == 0) {
+        wc[r * 4 + wv] = (uint32_t)__popcll(m);
+        if (w0 < n) ws.wmask[w0 >> 6] = m;
+    }
+}
+
+// after the TB_Q ballots of a tile (wc[r * 4 + wave] = the popcount of that word) and a barrier: the words' prefixes and the tile's
+// total
 __device__ __forceinline__ void tile_prefixes(const uint32_t *wc, uint64_t t0, uint64_t n_items, const CompactWs &ws) {
     const int tid = threadIdx.x;
     if (tid < TB_WORDS) { // word k of the tile = items t0 + 64 k ..: r = k / 4, wave k % 4

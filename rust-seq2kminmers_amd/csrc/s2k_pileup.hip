@@ -2,8 +2,9 @@
 // (include/s2k.h: s2k_walks_pileup, s2k_pileup_consensus).
 //
 // s2k_walks_pileup, one lane per run slot of the batch's CIGARs (no lane walks a match run):
-//  1. tg_check_kernel (s2k_targets_dev.h) and pl_offsets_kernel: the checks of s2k_walks_targets; ops_off does not decrease, ends inside
-//     the n_ops_total runs, n_ops[w] fits walk w's slots.  One flag word; the host also takes ops_off[0] and ops_off[n_walks].
+//  1. tg_check_kernel (s2k_targets_dev.h, with the host side of this prelude and the step cursor) and pl_offsets_kernel: the checks of
+//     s2k_walks_targets; ops_off does not decrease, ends inside the n_ops_total runs, n_ops[w] fits walk w's slots (ops_off_ok,
+//     s2k_cigar_dev.h, which also has the run word).  One flag word; the host also takes ops_off[0] and ops_off[n_walks].
 //  2. tg_steps_kernel, two scans, tg_len_kernel: every walk's target length as s2k_walks_targets has it (0 for a bad walk).
 //  3. pl_slots_kernel, one lane per slot: its walk (a search of ops_off), and the target and query bytes its run consumes (0 for a
 //     slot behind a walk's runs or of a walk that does not vote); a run of length 0 or with an unknown code raises the flag.  Two
@@ -31,6 +32,7 @@
 
 #include "../../include/s2k.h"
 #include "s2k_call.h"
+#include "s2k_cigar_dev.h"
 #include "s2k_dev.h"
 #include "s2k_graph_dev.h"
 #include "s2k_hostcopy.h"
@@ -69,13 +71,8 @@ __device__ __forceinline__ uint32_t comp_byte(uint32_t c) {
 __device__ __forceinline__ uint32_t letter_of(uint32_t k) { return (0x54474341u >> (8 * k)) & 0xFFu; }
 
 __global__ __launch_bounds__(UT) void pl_offsets_kernel(PlIn in, uint32_t *__restrict__ bad) {
-    bool ok = true;
     const uint64_t i0 = (uint64_t)blockIdx.x * UT + threadIdx.x, stride = (uint64_t)gridDim.x * UT;
-    for (uint64_t w = i0; w < in.tg.n_walks; w += stride) {
-        const uint64_t a = in.ops_off[w], b = in.ops_off[w + 1];
-        if (a > b || b > in.n_ops_total || in.n_ops[w] > b - a) ok = false;
-    }
-    if (!ok) atomicOr(bad, 1u);
+    if (!ops_off_ok(in.ops_off, in.n_ops, in.tg.n_walks, in.n_ops_total, i0, stride)) atomicOr(bad, 1u);
 }
 
 __global__ __launch_bounds__(UT) void pl_slots_kernel(PlIn in, uint64_t r0, uint64_t n_slots, uint32_t *__restrict__ wk, uint32_t *__restrict__ tl,
@@ -86,10 +83,10 @@ __global__ __launch_bounds__(UT) void pl_slots_kernel(PlIn in, uint64_t r0, uint
         const uint64_t r = r0 + i, w = last_le(in.ops_off, 0, in.tg.n_walks - 1, r);
         uint32_t t = 0, q = 0;
         if (in.aflags[w] == 0 && r - in.ops_off[w] < in.n_ops[w]) {
-            const uint32_t v = in.ops[r], op = v & 15u, len = v >> 4;
-            if (len == 0 || !(op == S2K_CIGAR_I || op == S2K_CIGAR_D || op == S2K_CIGAR_EQ || op == S2K_CIGAR_X)) ok = false;
-            t = op != S2K_CIGAR_I ? len : 0;
-            q = op != S2K_CIGAR_D ? len : 0;
+            const uint32_t v = in.ops[r];
+            if (!run_legal(v)) ok = false;
+            t = run_target(v);
+            q = run_query(v);
         }
         wk[i] = (uint32_t)w;
         tl[i] = t;
@@ -117,23 +114,12 @@ __global__ __launch_bounds__(UT) void pl_walks_kernel(PlIn in, uint64_t r0, cons
 }
 
 // The bytes of a walk's stitched path that one step gives (on a circular walk: one round): path coordinates [lo, hi), byte X lies
-// at offset X - start of the step's string.
-struct Walk {
-    uint64_t f, n, ps, pe, g0;
-    bool circ;
-};
+// at offset X - start of the step's string.  (Walk, walk_of, end_of, owner_step: s2k_targets_dev.h.)
 struct Seg {
     uint64_t j, start, lo, hi, L, off;
     uint32_t U;
 };
 
-__device__ __forceinline__ Walk walk_of(const TgIn &in, const uint64_t *__restrict__ G, uint64_t w) {
-    const uint64_t f = in.first_step[w];
-    return Walk{f, in.n_steps[w], in.path_start[w], in.path_end[w], G[f], (in.flags[w] & S2K_WALK_CIRCULAR) != 0};
-}
-__device__ __forceinline__ uint64_t end_of(const TgIn &in, const uint64_t *__restrict__ G, const Walk &k, uint64_t j) {
-    return G[k.f + j] - k.g0 + unitig_len(in, in.unitig[k.f + j]);
-}
 // step j (round j of a circular walk)
 __device__ __forceinline__ Seg seg_at(const TgIn &in, const uint64_t *__restrict__ G, const Walk &k, uint64_t j) {
     Seg s;
@@ -151,16 +137,9 @@ __device__ __forceinline__ Seg seg_at(const TgIn &in, const uint64_t *__restrict
     }
     return s;
 }
-// the step that owns byte X of the path, as tg_copy_kernel (s2k_align.hip) finds it: the last j with j == 0 or the end of step j - 1 <= X
+// the step that owns byte X of the path (the round, on a circular walk)
 __device__ __forceinline__ Seg locate(const TgIn &in, const uint64_t *__restrict__ G, const Walk &k, uint64_t X) {
-    if (k.circ) return seg_at(in, G, k, X / unitig_len(in, in.unitig[k.f]));
-    uint64_t j = 0;
-    for (uint64_t b = k.n - 1; j < b;) {
-        const uint64_t mid = (j + b + 1) >> 1;
-        if (end_of(in, G, k, mid - 1) <= X) j = mid;
-        else b = mid - 1;
-    }
-    return seg_at(in, G, k, j);
+    return seg_at(in, G, k, k.circ ? X / unitig_len(in, in.unitig[k.f]) : owner_step(in, G, k, X));
 }
 // the forward position of byte X of the path, which lies in s
 __device__ __forceinline__ uint64_t fwd_pos(const Seg &s, uint64_t X) { return (s.U & 1u) ? s.off + s.L - 1 - (X - s.start) : s.off + (X - s.start); }
@@ -201,7 +180,7 @@ __global__ __launch_bounds__(UT) void pl_vote_kernel(PlIn in, uint64_t r0, uint6
     for (uint64_t i = i0; i < n_slots; i += stride) {
         if (tl[i] == 0 && ql[i] == 0) continue; // no run of a voting walk
         const uint64_t w = wk[i], first = in.ops_off[w] - r0;
-        const uint32_t v = in.ops[r0 + i], op = v & 15u, n = v >> 4;
+        const uint32_t v = in.ops[r0 + i], op = run_op(v), n = run_len(v);
         const Walk k = walk_of(in.tg, G, w);
         const uint64_t T = len[w], x0 = TP[i] - TP[first], qo = in.qb[w] + (QP[i] - QP[first]);
         const bool has_prev = i > first, has_next = i + 1 - first < in.n_ops[w];
@@ -218,9 +197,9 @@ __global__ __launch_bounds__(UT) void pl_vote_kernel(PlIn in, uint64_t r0, uint6
             uint64_t e = 0;
             if (odd ? has_next : has_prev) {
                 const uint32_t nb = in.ops[r0 + (odd ? i + 1 : i - 1)];
-                if ((nb & 15u) == S2K_CIGAR_EQ) {
+                if (run_op(nb) == S2K_CIGAR_EQ) {
                     const uint64_t room = odd ? std::min(s.hi, k.pe) - k.ps - x0 : x0 - (std::max(s.lo, k.ps) - k.ps);
-                    e = std::min<uint64_t>(nb >> 4, room);
+                    e = std::min<uint64_t>(run_len(nb), room);
                 }
             }
             const uint32_t lim = (uint32_t)std::min<uint64_t>(e, max_shift);
@@ -282,9 +261,9 @@ __global__ __launch_bounds__(UT) void pl_vote_kernel(PlIn in, uint64_t r0, uint6
         uint64_t e = 0;
         if (odd ? has_next : has_prev) {
             const uint32_t nb = in.ops[r0 + (odd ? i + 1 : i - 1)];
-            if ((nb & 15u) == S2K_CIGAR_EQ) {
+            if (run_op(nb) == S2K_CIGAR_EQ) {
                 const uint64_t room = odd ? std::min(s.hi, k.pe) - k.ps - x1 : x0 - (std::max(s.lo, k.ps) - k.ps);
-                e = std::min<uint64_t>(nb >> 4, room);
+                e = std::min<uint64_t>(run_len(nb), room);
             }
         }
         const uint32_t lim = (uint32_t)std::min<uint64_t>(e, max_shift);
@@ -321,11 +300,11 @@ __global__ __launch_bounds__(UT) void pl_match_b_kernel(PlIn in, uint64_t r0, ui
         uint64_t x = 0, x1 = 0, xe = 0, a = 0, b = 0;
         if (i < n_slots && tl[i]) {
             const uint32_t v = in.ops[r0 + i];
-            if ((v & 15u) == S2K_CIGAR_EQ) {
+            if (run_op(v) == S2K_CIGAR_EQ) {
                 const uint64_t w = wk[i];
                 k = walk_of(in.tg, G, w);
                 x = TP[i] - TP[in.ops_off[w] - r0];
-                x1 = x + (v >> 4);
+                x1 = x + run_len(v);
                 s = locate(in.tg, G, k, k.ps + x);
                 mine = next_piece(in.tg, G, k, s, &x, x1, &xe, &a, &b);
             }
@@ -488,28 +467,21 @@ s2k_status s2k_walks_pileup(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_fi
     // the walks' part of the workspace first: its size does not depend on the runs
     Layout L;
     const auto words_p = L.bytes<unsigned long long>(PL_WORDS * 8);
-    const auto adv_p = L.take<uint32_t>(n_steps), brk_p = L.take<uint32_t>(n_steps);
-    const auto G_p = L.take<uint64_t>(n_steps + 1), J_p = L.take<uint64_t>(n_steps + 1);
-    const auto len_p = L.take<uint32_t>(n_walks);
-    const auto bad_p = L.take<uint8_t>(n_walks);
+    const TgPieces tp = carve_targets(L, n_steps, n_walks, true);
     uint64_t r0 = 0, r1 = 0;
     uint32_t hbad = 0;
     {
-        Layout L0 = L;
-        char *w = L0.alloc(ctx);
+        char *w = L.alloc(ctx);
         if (!w) return c.nomem();
         uint32_t *bad = (uint32_t *)words_p(w);
-        c.zero(words_p(w), PL_WORDS * 8);
-        if (c.ok()) {
-            hipLaunchKernelGGL(tg_check_kernel, dim3(grid_for(std::max<uint64_t>(std::max(n_steps, n_walks), std::max<uint64_t>(n_unitigs, 1)))), dim3(UT), 0, c.st, tg,
-                               bad);
-            hipLaunchKernelGGL(pl_offsets_kernel, dim3(grid_for(n_walks)), dim3(UT), 0, c.st, in, bad);
-            c.launched();
-        }
-        c.fetch(&hbad, bad, 4);
-        c.fetch(&r0, d_ops_off, 8);
-        c.fetch(&r1, d_ops_off + n_walks, 8);
-        if (!c.sync()) return c.device_error();
+        hbad = c.check(
+            bad, PL_WORDS * 8, bad,
+            [&] {
+                launch_tg_check(c, tg, bad);
+                c.launch(pl_offsets_kernel, grid_for(n_walks), UT, in, bad);
+            },
+            [&] { fetch_ops_ends(c, d_ops_off, n_walks, &r0, &r1); });
+        if (!c.ok()) return c.device_error();
         if (hbad)
             return c.invalid("a walk whose steps lie outside the paths, a step on a unitig >= n_unitigs, out_off that decreases or passes n_bases, a unitig of "
                              "2^32 bases or more, ops_off that decreases or passes n_ops_total, or n_ops above a walk's slots");
@@ -525,26 +497,12 @@ s2k_status s2k_walks_pileup(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_fi
     unsigned long long *words = words_p(w);
     uint32_t *bad = (uint32_t *)words;
     c.zero(words, PL_WORDS * 8);
-    if (c.ok() && n_steps) {
-        hipLaunchKernelGGL(tg_steps_kernel, dim3((unsigned)((n_steps + TG_T - 1) / TG_T)), dim3(TG_T), 0, c.st, tg, adv_p(w), brk_p(w));
-        c.launched();
-        c.scan(adv_p(w), n_steps, G_p(w), tmp_p(w));
-        c.scan(brk_p(w), n_steps, J_p(w), tmp_p(w));
-    }
-    if (c.ok()) {
-        hipLaunchKernelGGL(tg_len_kernel, dim3((unsigned)((n_walks + TG_T - 1) / TG_T)), dim3(TG_T), 0, c.st, tg, G_p(w), J_p(w), len_p(w), bad_p(w), bad);
-        c.launched();
-    }
-    if (c.ok() && n_slots) {
-        hipLaunchKernelGGL(pl_slots_kernel, dim3(grid_for(n_slots)), dim3(UT), 0, c.st, in, r0, n_slots, wk_p(w), tl_p(w), ql_p(w), bad);
-        c.launched();
-    }
+    launch_tg_steps(c, tg, tp, w, tmp_p(w));
+    launch_tg_lens(c, tg, tp, w, bad);
+    if (n_slots) c.launch(pl_slots_kernel, grid_for(n_slots), UT, in, r0, n_slots, wk_p(w), tl_p(w), ql_p(w), bad);
     c.scan(tl_p(w), n_slots, TP_p(w), tmp_p(w));
     c.scan(ql_p(w), n_slots, QP_p(w), tmp_p(w));
-    if (c.ok()) {
-        hipLaunchKernelGGL(pl_walks_kernel, dim3(grid_for(n_walks)), dim3(UT), 0, c.st, in, r0, TP_p(w), QP_p(w), len_p(w), words);
-        c.launched();
-    }
+    c.launch(pl_walks_kernel, grid_for(n_walks), UT, in, r0, TP_p(w), QP_p(w), tp.len(w), words);
     c.fetch(&hbad, bad, 4);
     if (!c.sync()) return c.device_error();
     if (hbad)
@@ -556,22 +514,12 @@ s2k_status s2k_walks_pileup(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_fi
     if (n_slots) {
         c.zero(dm_p(w), (n_bases + 1) * 4);
         c.zero(dd_p(w), (n_bases + 1) * 4);
-        if (c.ok()) {
-            if (B) {
-                hipLaunchKernelGGL(pl_vote_kernel<true>, dim3(grid_for(n_slots)), dim3(UT), 0, c.st, in, r0, n_slots, wk_p(w), tl_p(w), ql_p(w), TP_p(w), QP_p(w),
-                                   G_p(w), len_p(w), max_shift, pl, words);
-                hipLaunchKernelGGL(pl_match_b_kernel, dim3(grid_for(n_slots)), dim3(UT), 0, c.st, in, r0, n_slots, wk_p(w), tl_p(w), TP_p(w), G_p(w), pl);
-            } else
-                hipLaunchKernelGGL(pl_vote_kernel<false>, dim3(grid_for(n_slots)), dim3(UT), 0, c.st, in, r0, n_slots, wk_p(w), tl_p(w), ql_p(w), TP_p(w), QP_p(w),
-                                   G_p(w), len_p(w), max_shift, pl, words);
-            c.launched();
-        }
+        c.launch(B ? pl_vote_kernel<true> : pl_vote_kernel<false>, grid_for(n_slots), UT, in, r0, n_slots, wk_p(w), tl_p(w), ql_p(w), TP_p(w), QP_p(w), tp.G(w),
+                 tp.len(w), max_shift, pl, words);
+        if (B) c.launch(pl_match_b_kernel, grid_for(n_slots), UT, in, r0, n_slots, wk_p(w), tl_p(w), TP_p(w), tp.G(w), pl);
         for (int which = B ? 1 : 0; which < 2; which++) {
             c.scan(which ? dd_p(w) : dm_p(w), n_bases, pre_p(w), tmp_p(w));
-            if (c.ok()) {
-                hipLaunchKernelGGL(pl_apply_kernel, dim3(grid_for(n_bases)), dim3(UT), 0, c.st, pre_p(w), n_bases, which ? pile->del : pile->match);
-                c.launched();
-            }
+            c.launch(pl_apply_kernel, grid_for(n_bases), UT, pre_p(w), n_bases, which ? pile->del : pile->match);
         }
     }
     unsigned long long h[PL_WORDS];
@@ -603,9 +551,8 @@ s2k_status s2k_pileup_consensus(s2k_ctx *ctx, const s2k_pile *pile, const uint64
     unsigned long long *words = words_p(w);
     uint32_t *bad = (uint32_t *)words;
     uint64_t ends[2] = {0, 0};
-    const uint32_t hbad = c.check(words, PL_WORDS * 8, bad, [&] {
-        hipLaunchKernelGGL(cs_check_kernel, dim3(grid_for(std::max<uint64_t>(n_unitigs, 1))), dim3(UT), 0, c.st, d_out_off, n_unitigs, n_bases, bad);
-    });
+    const uint32_t hbad =
+        c.check(words, PL_WORDS * 8, bad, [&] { c.launch(cs_check_kernel, grid_for(std::max<uint64_t>(n_unitigs, 1)), UT, d_out_off, n_unitigs, n_bases, bad); });
     if (!c.ok()) return c.device_error();
     if (hbad) return c.invalid("out_off that decreases or passes n_bases, or a unitig of 2^31 bases or more");
     if (n_unitigs) {
@@ -614,10 +561,7 @@ s2k_status s2k_pileup_consensus(s2k_ctx *ctx, const s2k_pile *pile, const uint64
         if (!c.sync()) return c.device_error();
     }
     uint64_t total = 0;
-    if (n_bases) {
-        hipLaunchKernelGGL(cs_call_kernel, dim3(grid_for(n_bases)), dim3(UT), 0, c.st, *pile, d_out, ends[0], ends[1], n_bases, min_cov, cnt_p(w), byt_p(w), words);
-        c.launched();
-    }
+    if (n_bases) c.launch(cs_call_kernel, grid_for(n_bases), UT, *pile, d_out, ends[0], ends[1], n_bases, min_cov, cnt_p(w), byt_p(w), words);
     c.scan(cnt_p(w), n_bases, pm_p(w), tmp_p(w));
     unsigned long long h[PL_WORDS];
     c.fetch(&total, pm_p(w) + n_bases, 8);
@@ -627,14 +571,8 @@ s2k_status s2k_pileup_consensus(s2k_ctx *ctx, const s2k_pile *pile, const uint64
     if (d_new_out && total > capacity) return S2K_ERR_CAPACITY;
     stats[0] = h[CW_LOW], stats[1] = h[CW_SUB], stats[2] = h[CW_DEL], stats[3] = h[CW_INS], stats[4] = h[CW_LONG];
     if (d_pos_map) c.copy(d_pos_map, pm_p(w), (n_bases + 1) * 8, hipMemcpyDeviceToDevice);
-    if (c.ok() && (d_new_out_off || (d_new_overlap && n_unitigs))) {
-        hipLaunchKernelGGL(cs_units_kernel, dim3(grid_for(n_unitigs + 1)), dim3(UT), 0, c.st, d_out_off, d_overlap, n_unitigs, pm_p(w), d_new_out_off, d_new_overlap);
-        c.launched();
-    }
-    if (c.ok() && d_new_out && n_bases) {
-        hipLaunchKernelGGL(cs_write_kernel, dim3(grid_for(n_bases)), dim3(UT), 0, c.st, cnt_p(w), byt_p(w), pm_p(w), n_bases, d_new_out);
-        c.launched();
-    }
+    if (d_new_out_off || (d_new_overlap && n_unitigs)) c.launch(cs_units_kernel, grid_for(n_unitigs + 1), UT, d_out_off, d_overlap, n_unitigs, pm_p(w), d_new_out_off, d_new_overlap);
+    if (d_new_out && n_bases) c.launch(cs_write_kernel, grid_for(n_bases), UT, cnt_p(w), byt_p(w), pm_p(w), n_bases, d_new_out);
     if (!c.sync()) return c.device_error();
     return S2K_OK;
 }

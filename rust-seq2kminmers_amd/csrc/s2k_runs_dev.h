@@ -73,8 +73,7 @@ __global__ __launch_bounds__(256) void run_offsets_kernel(const uint64_t *__rest
     out_off[r] = kept_before(heads, n, n_tiles, off[r]);
 }
 inline void launch_run_offsets(Call &c, const uint64_t *off, uint64_t n_reads, uint64_t n, uint64_t n_tiles, const RunWs &ws, uint64_t *out_off) {
-    hipLaunchKernelGGL(run_offsets_kernel, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, c.st, off, n_reads, n, n_tiles, ws.h, out_off);
-    c.launched();
+    c.launch(run_offsets_kernel, (unsigned)((n_reads + 1 + 255) / 256), 256, off, n_reads, n, n_tiles, ws.h, out_off);
 }
 
 // lane-private staging of one field: out[base + slot[r]] = val(r, j) for the lane's kept items j, through LDS (stage4: room for

@@ -25,7 +25,8 @@
 //     before w (a search: the chosen are sorted by walk); sg_segments_kernel, one lane per segment, output-ordered.
 //
 // s2k_align_join.  Slots are the run slots of the segments, ops_off[0] .. ops_off[n_segments), in the same tiles:
-//  1. jn_check_kernel: seg_off, ops_off, n_ops.  The host reads the flag and the two ends of ops_off.
+//  1. jn_check_kernel: seg_off, ops_off, n_ops (ops_off_ok and the run word: s2k_cigar_dev.h).  The host reads the flag and the two
+//     ends of ops_off.
 //  2. jn_over_kernel and three launch_scan_u32 over the segments: edits, matches, over.
 //  3. jn_slots_kernel, one lane per slot: its segment and walk by searches; a run of a walk that is neither bad nor over is kept, and
 //     is a head unless it is the first run of a segment after the walk's first whose op equals the last run's of the segment before.
@@ -45,6 +46,7 @@
 
 #include "../../include/s2k.h"
 #include "s2k_call.h"
+#include "s2k_cigar_dev.h"
 #include "s2k_compact_dev.h"
 #include "s2k_coords_dev.h"
 #include "s2k_dev.h"
@@ -233,7 +235,7 @@ __global__ __launch_bounds__(TB_THREADS) void sg_tiles_kernel(SgWs ws, uint64_t 
 __global__ __launch_bounds__(TB_THREADS) void sg_admit_kernel(SgIn in, SgWs ws, uint64_t n_items, CompactWs cw, unsigned long long *__restrict__ words) {
     __shared__ uint64_t part[TB_THREADS / 64][2];
     __shared__ uint32_t wc[TB_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     uint64_t ca = ws.TQ[blockIdx.x], cb = ws.TT[blockIdx.x];
     unsigned long long n_adm = 0;
@@ -251,12 +253,7 @@ __global__ __launch_bounds__(TB_THREADS) void sg_admit_kernel(SgIn in, SgWs ws, 
             adm = qc > 0 && qc < m && tc > 0 && tc < nt && pq < kq && pt < kt;
         }
         n_adm += adm;
-        const uint64_t mask = __ballot(adm);
-        const uint64_t w0 = t0 + (uint64_t)q * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wc[q * 4 + wv] = (uint32_t)__popcll(mask);
-            if (w0 < n_items) cw.wmask[w0 >> 6] = mask;
-        }
+        tile_ballot(wc, q, t0, n_items, cw, adm);
     }
     if (!ok) atomicOr((uint32_t *)(words + SW_BAD), 2u);
     __syncthreads();
@@ -278,7 +275,7 @@ __global__ __launch_bounds__(TB_THREADS) void sg_keep_kernel(SgWs ws, uint64_t n
 
 __global__ __launch_bounds__(TB_THREADS) void sg_heads_kernel(SgWs ws, uint64_t n_adm, uint32_t seg_len, CompactWs ch) {
     __shared__ uint32_t wc[TB_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
 #pragma unroll
     for (int q = 0; q < TB_Q; q++) {
@@ -288,12 +285,7 @@ __global__ __launch_bounds__(TB_THREADS) void sg_heads_kernel(SgWs ws, uint64_t 
             const uint32_t b = ws.aq[i] / seg_len;
             head = b >= 1 && (i == 0 || ws.aw[i - 1] != ws.aw[i] || ws.aq[i - 1] / seg_len != b);
         }
-        const uint64_t mask = __ballot(head);
-        const uint64_t w0 = t0 + (uint64_t)q * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wc[q * 4 + wv] = (uint32_t)__popcll(mask);
-            if (w0 < n_adm) ch.wmask[w0 >> 6] = mask;
-        }
+        tile_ballot(wc, q, t0, n_adm, ch, head);
     }
     __syncthreads();
     tile_prefixes(wc, t0, n_adm, ch);
@@ -370,10 +362,7 @@ struct JnWs {
 __global__ __launch_bounds__(UT) void jn_check_kernel(JnIn in, uint32_t *__restrict__ bad) {
     const uint64_t i0 = (uint64_t)blockIdx.x * UT + threadIdx.x, stride = (uint64_t)gridDim.x * UT;
     bool ok = path_off_ok(in.seg_off, in.n_walks, in.n_segs, i0, stride);
-    for (uint64_t s = i0; s < in.n_segs; s += stride) {
-        const uint64_t a = in.ops_off[s], b = in.ops_off[s + 1];
-        if (a > b || b > in.n_ops_total || in.n_ops[s] > b - a) ok = false;
-    }
+    if (!ops_off_ok(in.ops_off, in.n_ops, in.n_segs, in.n_ops_total, i0, stride)) ok = false;
     if (!ok) atomicOr(bad, 1u);
 }
 
@@ -390,7 +379,7 @@ __device__ __forceinline__ bool joined(const JnIn &in, const JnWs &ws, uint64_t 
 __global__ __launch_bounds__(TB_THREADS) void jn_slots_kernel(JnIn in, JnWs ws, uint64_t r0, uint64_t n_slots, CompactWs ch, uint32_t *__restrict__ bad) {
     __shared__ uint64_t srange[2];
     __shared__ uint32_t wc[TB_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     if (tid < 2) srange[tid] = last_le(in.ops_off, 0, in.n_segs - 1, r0 + (tid ? std::min<uint64_t>(t0 + TB_TILE, n_slots) - 1 : t0));
     __syncthreads();
@@ -403,20 +392,15 @@ __global__ __launch_bounds__(TB_THREADS) void jn_slots_kernel(JnIn in, JnWs ws, 
             const uint64_t w = last_le(in.seg_off, 0, in.n_walks - 1, s);
             uint32_t ln = 0;
             if (k < in.n_ops[s] && joined(in, ws, w)) {
-                const uint32_t v = in.ops[r], op = v & 15u;
-                ln = v >> 4;
-                if (ln == 0 || !(op == S2K_CIGAR_I || op == S2K_CIGAR_D || op == S2K_CIGAR_EQ || op == S2K_CIGAR_X)) ok = false;
+                const uint32_t v = in.ops[r];
+                ln = run_len(v);
+                if (!run_legal(v)) ok = false;
                 head = true;
-                if (k == 0 && s > in.seg_off[w] && in.n_ops[s - 1]) head = (in.ops[in.ops_off[s - 1] + in.n_ops[s - 1] - 1] & 15u) != op;
+                if (k == 0 && s > in.seg_off[w] && in.n_ops[s - 1]) head = run_op(in.ops[in.ops_off[s - 1] + in.n_ops[s - 1] - 1]) != run_op(v);
             }
             ws.len[i] = ln;
         }
-        const uint64_t mask = __ballot(head);
-        const uint64_t w0 = t0 + (uint64_t)q * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wc[q * 4 + wv] = (uint32_t)__popcll(mask);
-            if (w0 < n_slots) ch.wmask[w0 >> 6] = mask;
-        }
+        tile_ballot(wc, q, t0, n_slots, ch, head);
     }
     if (!ok) atomicOr(bad, 1u);
     __syncthreads();
@@ -431,7 +415,7 @@ __global__ __launch_bounds__(TB_THREADS) void jn_heads_kernel(JnIn in, JnWs ws, 
     uint32_t slot[TB_Q];
     const uint32_t keep = tile_slots(ch, t0, n_slots, slot);
     leave_field(ws.HLP, base, keep, slot, tot, stage4, [&](int, uint64_t i) { return ws.LP[i]; });
-    leave_field(ws.hop, base, keep, slot, tot, stage4, [&](int, uint64_t i) { return in.ops[r0 + i] & 15u; });
+    leave_field(ws.hop, base, keep, slot, tot, stage4, [&](int, uint64_t i) { return run_op(in.ops[r0 + i]); });
 }
 
 __global__ __launch_bounds__(UT) void jn_lens_kernel(JnIn in, JnWs ws, uint64_t n_heads, uint32_t *__restrict__ bad) {
@@ -464,7 +448,7 @@ __global__ __launch_bounds__(UT) void jn_walks_kernel(JnIn in, JnWs ws, uint64_t
 
 __global__ __launch_bounds__(UT) void jn_ops_kernel(JnWs ws, uint64_t n_heads, uint32_t *__restrict__ ops) {
     const uint64_t i0 = (uint64_t)blockIdx.x * UT + threadIdx.x, stride = (uint64_t)gridDim.x * UT;
-    for (uint64_t p = i0; p < n_heads; p += stride) ops[p] = (uint32_t)(ws.HLP[p + 1] - ws.HLP[p]) << 4 | ws.hop[p];
+    for (uint64_t p = i0; p < n_heads; p += stride) ops[p] = run_pack(ws.hop[p], (uint32_t)(ws.HLP[p + 1] - ws.HLP[p]));
 }
 
 } // namespace
@@ -509,8 +493,7 @@ s2k_status s2k_walks_segments(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out
     // the part of the workspace whose size the arguments give: the checks, and the number of items
     Layout L;
     const auto words_p = L.bytes<unsigned long long>(SG_WORDS * 8);
-    const auto adv_p = L.take<uint32_t>(n_steps), brk_p = L.take<uint32_t>(n_steps);
-    const auto G_p = L.take<uint64_t>(n_steps + 1);
+    const TgPieces tp = carve_targets(L, n_steps, n_walks, false);
     const auto stepw_p = L.take<uint32_t>(n_src_steps);
     const auto stepj_p = L.take<uint64_t>(n_src_steps), C_p = L.take<uint64_t>(n_src_steps + 1);
     const auto soff_p = L.take<uint64_t>(n_walks + 1);
@@ -521,19 +504,15 @@ s2k_status s2k_walks_segments(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out
         char *w = L0.alloc(ctx);
         if (!w) return c.nomem();
         uint32_t *bad = (uint32_t *)words_p(w);
-        c.zero(words_p(w), SG_WORDS * 8);
-        if (c.ok()) {
-            hipLaunchKernelGGL(tg_check_kernel, dim3(grid_for(std::max<uint64_t>(std::max(n_steps, n_walks), std::max<uint64_t>(n_unitigs, 1)))), dim3(UT), 0, c.st,
-                               tg, bad);
-            hipLaunchKernelGGL(sg_check_kernel, dim3(grid_for(std::max(std::max(n_reads + 1, n_steps), std::max(std::max(n_walks, n_src_steps), n_nodes)))),
-                               dim3(UT), 0, c.st, sg, v, bad);
-            c.launched();
-        }
-        c.scan(src->count, n_src_steps, C_p(w), tmp_p(w));
-        uint32_t hbad = 0;
-        c.fetch(&hbad, bad, 4);
-        c.fetch(&n_items, C_p(w) + n_src_steps, 8);
-        if (!c.sync()) return c.device_error();
+        const uint32_t hbad = c.check(
+            bad, SG_WORDS * 8, bad,
+            [&] {
+                launch_tg_check(c, tg, bad);
+                c.launch(sg_check_kernel, grid_for(std::max(std::max(n_reads + 1, n_steps), std::max(std::max(n_walks, n_src_steps), n_nodes))), UT, sg, v, bad);
+                c.scan(src->count, n_src_steps, C_p(w), tmp_p(w));
+            },
+            [&] { c.fetch(&n_items, C_p(w) + n_src_steps, 8); });
+        if (!c.ok()) return c.device_error();
         if (hbad)
             return c.invalid("a check of s2k_walks_targets or s2k_paths_walks on the walks, the steps or the decomposition; walk_off or src->path_off that does "
                              "not run from 0 to its total without decreasing; walks whose step ranges overlap or descend; qstart above qend; tgt_off that "
@@ -551,20 +530,13 @@ s2k_status s2k_walks_segments(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out
     unsigned long long *words = words_p(w);
     uint32_t *bad = (uint32_t *)words;
     // the chosen anchors reuse the scanned words, which sg_keep_kernel reads last: 12 B per anchor in 16 B per item
-    const SgWs ws{stepw_p(w), stepj_p(w), C_p(w),  G_p(w),  KQ_p(w), KT_p(w), TQ_p(w), TT_p(w), aw_p(w), aq_p(w), at_p(w), (uint32_t *)KQ_p(w),
+    const SgWs ws{stepw_p(w), stepj_p(w), C_p(w),  tp.G(w), KQ_p(w), KT_p(w), TQ_p(w), TT_p(w), aw_p(w), aq_p(w), at_p(w), (uint32_t *)KQ_p(w),
                   (uint32_t *)KQ_p(w) + n_items, (uint32_t *)KT_p(w), soff_p(w)};
     const CompactWs adm = adm_p(w), hd = hd_p(w);
     c.zero(words, SG_WORDS * 8);
     c.scan(src->count, n_src_steps, ws.C, tmp_p(w));
-    if (c.ok() && n_steps) {
-        hipLaunchKernelGGL(tg_steps_kernel, dim3((unsigned)((n_steps + TG_T - 1) / TG_T)), dim3(TG_T), 0, c.st, tg, adv_p(w), brk_p(w));
-        c.launched();
-        c.scan(adv_p(w), n_steps, ws.G, tmp_p(w));
-    }
-    if (c.ok() && n_src_steps) {
-        hipLaunchKernelGGL(sg_steps_kernel, dim3(grid_for(n_src_steps)), dim3(UT), 0, c.st, sg, ws, bad);
-        c.launched();
-    }
+    launch_tg_steps(c, tg, tp, w, tmp_p(w));
+    if (n_src_steps) c.launch(sg_steps_kernel, grid_for(n_src_steps), UT, sg, ws, bad);
     uint32_t hbad = 0;
     c.fetch(&hbad, bad, 4);
     if (!c.sync()) return c.device_error(); // before an item is read through a source step
@@ -574,10 +546,9 @@ s2k_status s2k_walks_segments(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out
     uint64_t n_adm = 0, n_chosen = 0;
     unsigned long long h[SG_WORDS] = {0};
     if (n_items) {
-        hipLaunchKernelGGL(sg_items_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, sg, v, ws, n_items, words);
-        hipLaunchKernelGGL(sg_tiles_kernel, dim3(1), dim3(TB_THREADS), 0, c.st, ws, nt);
-        hipLaunchKernelGGL(sg_admit_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, sg, ws, n_items, adm, words);
-        c.launched();
+        c.launch(sg_items_kernel, (unsigned)nt, TB_THREADS, sg, v, ws, n_items, words);
+        c.launch(sg_tiles_kernel, 1, TB_THREADS, ws, nt);
+        c.launch(sg_admit_kernel, (unsigned)nt, TB_THREADS, sg, ws, n_items, adm, words);
         c.scan(adm.tile_kept, nt, adm.tile_off, adm_p.scan_tmp(w));
         c.fetch(&n_adm, adm.tile_off + nt, 8);
         c.fetch(h, words, sizeof h);
@@ -586,9 +557,8 @@ s2k_status s2k_walks_segments(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out
     }
     const uint64_t nta = (n_adm + TB_TILE - 1) / TB_TILE;
     if (n_adm) {
-        hipLaunchKernelGGL(sg_keep_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, ws, n_items, adm);
-        hipLaunchKernelGGL(sg_heads_kernel, dim3((unsigned)nta), dim3(TB_THREADS), 0, c.st, ws, n_adm, seg_len, hd);
-        c.launched();
+        c.launch(sg_keep_kernel, (unsigned)nt, TB_THREADS, ws, n_items, adm);
+        c.launch(sg_heads_kernel, (unsigned)nta, TB_THREADS, ws, n_adm, seg_len, hd);
         c.scan(hd.tile_kept, nta, hd.tile_off, hd_p.scan_tmp(w));
         c.fetch(&n_chosen, hd.tile_off + nta, 8);
         if (!c.sync()) return c.device_error();
@@ -596,19 +566,10 @@ s2k_status s2k_walks_segments(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out
     const uint64_t total = n_walks + n_chosen;
     *n_segments = total;
     if (records && total > out->capacity) return S2K_ERR_CAPACITY;
-    if (c.ok() && n_chosen) {
-        hipLaunchKernelGGL(sg_chosen_kernel, dim3((unsigned)nta), dim3(TB_THREADS), 0, c.st, ws, n_adm, hd);
-        c.launched();
-    }
-    if (c.ok()) {
-        hipLaunchKernelGGL(sg_off_kernel, dim3(grid_for(n_walks + 1)), dim3(UT), 0, c.st, ws, n_walks, n_chosen, words);
-        c.launched();
-    }
+    if (n_chosen) c.launch(sg_chosen_kernel, (unsigned)nta, TB_THREADS, ws, n_adm, hd);
+    c.launch(sg_off_kernel, grid_for(n_walks + 1), UT, ws, n_walks, n_chosen, words);
     if (out && out->seg_off) c.copy(out->seg_off, ws.seg_off, (n_walks + 1) * 8, hipMemcpyDeviceToDevice);
-    if (c.ok() && records && total) {
-        hipLaunchKernelGGL(sg_segments_kernel, dim3(grid_for(total)), dim3(UT), 0, c.st, sg, ws, total, *out);
-        c.launched();
-    }
+    if (records && total) c.launch(sg_segments_kernel, grid_for(total), UT, sg, ws, total, *out);
     c.fetch(&h[SW_CUT], words + SW_CUT, 8);
     if (!c.sync()) return c.device_error();
     stats[0] = h[SW_CAND], stats[1] = h[SW_OUTSIDE], stats[2] = h[SW_ADM], stats[3] = n_chosen, stats[4] = h[SW_CUT];
@@ -632,19 +593,13 @@ s2k_status s2k_align_join(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_seg_
     uint64_t r0 = 0, r1 = 0;
     uint32_t hbad = 0;
     {
-        Layout L0 = L;
-        char *w = L0.alloc(ctx);
+        char *w = L.alloc(ctx);
         if (!w) return c.nomem();
         uint32_t *bad = words_p(w);
-        c.zero(bad, 16);
-        if (c.ok()) {
-            hipLaunchKernelGGL(jn_check_kernel, dim3(grid_for(std::max(n_walks + 1, n_segments))), dim3(UT), 0, c.st, in, bad);
-            c.launched();
-        }
-        c.fetch(&hbad, bad, 4);
-        c.fetch(&r0, seg->ops_off, 8);
-        c.fetch(&r1, seg->ops_off + n_segments, 8);
-        if (!c.sync()) return c.device_error();
+        hbad = c.check(
+            bad, 16, bad, [&] { c.launch(jn_check_kernel, grid_for(std::max(n_walks + 1, n_segments)), UT, in, bad); },
+            [&] { fetch_ops_ends(c, seg->ops_off, n_segments, &r0, &r1); });
+        if (!c.ok()) return c.device_error();
         if (hbad)
             return c.invalid("seg_off that does not run from 0 to n_segments without decreasing, ops_off that decreases or passes the runs there are, or "
                              "n_ops above a segment's slots");
@@ -661,31 +616,20 @@ s2k_status s2k_align_join(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_seg_
     const JnWs ws{ov_p(w), E_p(w), M_p(w), OV_p(w), len_p(w), LP_p(w), HLP_p(w), hop_p(w)};
     const CompactWs hd = hd_p(w);
     c.zero(bad, 16);
-    if (c.ok() && n_segments) {
-        hipLaunchKernelGGL(jn_over_kernel, dim3(grid_for(n_segments)), dim3(UT), 0, c.st, in, ws.ov);
-        c.launched();
-    }
+    if (n_segments) c.launch(jn_over_kernel, grid_for(n_segments), UT, in, ws.ov);
     c.scan(seg->edits, n_segments, ws.E, tmp_p(w));
     c.scan(seg->matches, n_segments, ws.M, tmp_p(w));
     c.scan(ws.ov, n_segments, ws.OV, tmp_p(w));
-    if (c.ok() && n_slots) { // (slots: there are segments, and with the check pass walks that hold them)
-        hipLaunchKernelGGL(jn_slots_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, in, ws, r0, n_slots, hd, bad);
-        c.launched();
-    }
+    // (slots: there are segments, and with the check pass walks that hold them)
+    if (n_slots) c.launch(jn_slots_kernel, (unsigned)nt, TB_THREADS, in, ws, r0, n_slots, hd, bad);
     c.scan(ws.len, n_slots, ws.LP, tmp_p(w));
     c.scan(hd.tile_kept, nt, hd.tile_off, hd_p.scan_tmp(w));
     uint64_t n_heads = 0;
     c.fetch(&n_heads, hd.tile_off + nt, 8);
     if (!c.sync()) return c.device_error();
-    if (c.ok() && n_heads) {
-        hipLaunchKernelGGL(jn_heads_kernel, dim3((unsigned)nt), dim3(TB_THREADS), 0, c.st, in, ws, r0, n_slots, hd);
-        c.launched();
-    }
+    if (n_heads) c.launch(jn_heads_kernel, (unsigned)nt, TB_THREADS, in, ws, r0, n_slots, hd);
     c.copy(ws.HLP + n_heads, ws.LP + n_slots, 8, hipMemcpyDeviceToDevice);
-    if (c.ok() && (n_heads || n_walks)) {
-        hipLaunchKernelGGL(jn_lens_kernel, dim3(grid_for(std::max(n_heads, n_walks))), dim3(UT), 0, c.st, in, ws, n_heads, bad);
-        c.launched();
-    }
+    if (n_heads || n_walks) c.launch(jn_lens_kernel, grid_for(std::max(n_heads, n_walks)), UT, in, ws, n_heads, bad);
     c.fetch(&hbad, bad, 4);
     if (!c.sync()) return c.device_error();
     if (hbad & 1u) return c.invalid("a run of length 0 or with an unknown code in a walk that is joined");
@@ -693,14 +637,8 @@ s2k_status s2k_align_join(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_seg_
     *n_ops_total = n_heads;
     if (!out) return S2K_OK;
     if (out->ops && n_heads > out->capacity) return S2K_ERR_CAPACITY;
-    if (c.ok()) {
-        hipLaunchKernelGGL(jn_walks_kernel, dim3(grid_for(n_walks + 1)), dim3(UT), 0, c.st, in, ws, r0, n_slots, nt, hd, *out);
-        c.launched();
-    }
-    if (c.ok() && out->ops && n_heads) {
-        hipLaunchKernelGGL(jn_ops_kernel, dim3(grid_for(n_heads)), dim3(UT), 0, c.st, ws, n_heads, out->ops);
-        c.launched();
-    }
+    c.launch(jn_walks_kernel, grid_for(n_walks + 1), UT, in, ws, r0, n_slots, nt, hd, *out);
+    if (out->ops && n_heads) c.launch(jn_ops_kernel, grid_for(n_heads), UT, ws, n_heads, out->ops);
     if (!c.sync()) return c.device_error();
     return S2K_OK;
 }

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(TB_THREADS) void node_count_kernel(const uint8_t *_
                                                                 const uint8_t *__restrict__ remove, uint64_t n_unitigs, uint64_t n_nodes,
                                                                 CompactWs ws, uint32_t *__restrict__ bad) {
     __shared__ uint32_t wc[TB_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     bool ok = true;
 #pragma unroll
@@ -148,12 +148,7 @@ __global__ __launch_bounds__(TB_THREADS) void node_count_kernel(const uint8_t *_
                 else ok = false;
             }
         }
-        const uint64_t m = __ballot(k);
-        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64; // first item of this wave's word
-        if (lane == 0) {
-            wc[r * 4 + wv] = (uint32_t)__popcll(m);
-            if (w0 < n_nodes) ws.wmask[w0 >> 6] = m;
-        }
+        tile_ballot(wc, r, t0, n_nodes, ws, k);
     }
     if (!ok) atomicOr(bad, 1u);
     __syncthreads();
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(TB_THREADS) void node_count_kernel(const uint8_t *_
 __global__ __launch_bounds__(TB_THREADS) void edge_count_kernel(const uint64_t *__restrict__ edge_keys, uint64_t n_edges, uint64_t n_nodes,
                                                                 const uint64_t *__restrict__ node_mask, CompactWs ws, uint32_t *__restrict__ bad) {
     __shared__ uint32_t wc[TB_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     uint64_t key[TB_Q];
 #pragma unroll
@@ -178,12 +173,7 @@ __global__ __launch_bounds__(TB_THREADS) void edge_count_kernel(const uint64_t *
             if (a < n_nodes && b < n_nodes) k = ((node_mask[a >> 6] >> (a & 63)) & (node_mask[b >> 6] >> (b & 63)) & 1ull) != 0;
             else ok = false;
         }
-        const uint64_t m = __ballot(k);
-        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wc[r * 4 + wv] = (uint32_t)__popcll(m);
-            if (w0 < n_edges) ws.wmask[w0 >> 6] = m;
-        }
+        tile_ballot(wc, r, t0, n_edges, ws, k);
     }
     if (!ok) atomicOr(bad, 1u);
     __syncthreads();

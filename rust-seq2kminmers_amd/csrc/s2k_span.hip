@@ -66,7 +66,7 @@ __global__ __launch_bounds__(TB_THREADS) void spans_count_kernel(Paths p, Csr g,
                                                                  unsigned long long *__restrict__ totals /* followed, off-graph */) {
     __shared__ FollowLds s;
     __shared__ uint32_t wc[TB_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t t0 = (uint64_t)blockIdx.x * TB_TILE;
     uint32_t U[TB_Q], ps[TB_Q], cnt[TB_Q], fl[TB_Q], e[TB_Q];
     uint64_t len[TB_Q];
@@ -85,12 +85,7 @@ __global__ __launch_bounds__(TB_THREADS) void spans_count_kernel(Paths p, Csr g,
     for (int r = 0; r < TB_Q; r++) {
         const int i = r * TB_THREADS + tid + 1;
         const bool whole = t0 + (i - 1) < p.n_steps && cnt[r] == len[r];
-        const uint64_t m = __ballot(whole && s.E[i] != SP_NONE && s.E[i + 1] != SP_NONE);
-        const uint64_t w0 = t0 + (uint64_t)r * TB_THREADS + (uint64_t)wv * 64;
-        if (lane == 0) {
-            wc[r * 4 + wv] = (uint32_t)__popcll(m);
-            if (w0 < p.n_steps) ws.c.wmask[w0 >> 6] = m;
-        }
+        tile_ballot(wc, r, t0, p.n_steps, ws.c, whole && s.E[i] != SP_NONE && s.E[i + 1] != SP_NONE);
     }
     __syncthreads();
     tile_prefixes(wc, t0, p.n_steps, ws.c);

@@ -854,6 +854,62 @@ def test_device_pileup_flagged_walks_are_skipped(eng):
     assert all((alone[f] == ref[f]).all() for f in PLANES)
 
 
+def cursor_case():
+    """three unitigs by hand -- 0 walked on its twin strand, 1 whose nine bases are both the overlap that enters it and the one that
+    leaves it (its step gives the path no byte), 2 walked round as a circular one -- and 65 walks, one past a wave, one of them bad
+    -> (walks, su, strings, overlap)"""
+    rng = np.random.default_rng(102)
+    b = ta.random_seq(rng, 9)
+    strings = [tus.revcomp(ta.random_seq(rng, 28) + b), b, b + ta.random_seq(rng, 14)]  # the path of steps 0 .. 2: 28 + 9 + 14 = 51 bytes
+    overlap = np.array([0, 9, 9, 0, 0, 0], dtype=np.uint32)
+    su = np.array([1, 2, 4, 4, 5], dtype=np.uint32)  # steps 0 .. 2: 0- 1+ 2+; step 3: 2+ and step 4: 2-, each walked round
+    specs = [(1, 2, 3, 17, 0),                 # two steps: from inside unitig 1 to inside unitig 2
+             (0, 3, 5, 48, 0),                 # through step 1, which adds no byte
+             (3, 1, 4, 4 + 2 * 23 + 7, 1),     # two rounds and a part
+             (4, 1, 11, 11 + 2 * 23 + 5, 1)]   # and on the twin strand
+    while len(specs) < 65:
+        if len(specs) == 40:
+            specs.append((0, 3, 0, 52, 0))     # the bad one: it ends behind the path
+            continue
+        first, n, total, circ = ((0, 3, 51, 0), (1, 2, 23, 0), (3, 1, 23, 1), (4, 1, 23, 1))[len(specs) % 4]
+        ps = int(rng.integers(0, total))
+        specs.append((first, n, ps, ps + int(rng.integers(1, 70)) if circ else int(rng.integers(ps + 1, total + 1)), circ))
+    return one_walks(specs), su, strings, overlap
+
+
+def device_cursor(eng):
+    """s2k_walks_targets and s2k_walks_pileup find the step of a path byte alike: byte x of a target is the draft's byte at the forward
+    position walk_sources gives x (its complement on an odd unitig), and a walk that matches its whole target votes there once"""
+    walks, su, strings, overlap = cursor_case()
+    off, out = draft_of(strings)
+    u, nw = [int(x) for x in su], len(walks["first_step"])
+    src = [walk_sources(walks, w, u, strings, overlap, off) for w in range(nw)]
+    lens = [len(s[1]) for s in src]
+    bad = [w for w in range(nw) if not lens[w]]
+    assert nw == 65 and bad == [40] and set(src[1][0].tolist()) == {0, 2} and len(set(src[2][0].tolist())) == 3
+    s, nb, got = ta.raw_targets(eng, walks, su, strings, overlap, capacity=sum(lens))
+    assert (s, nb) == (0, sum(lens)), (s, nb, eng.lib.s2k_last_error(eng.ctx))
+    toff = np.concatenate([[0], np.cumsum(lens)])
+    assert got["tgt_off"][:nw + 1].tolist() == toff.tolist() and got["bad"][:nw].tolist() == [int(w in bad) for w in range(nw)]
+    want = np.zeros(len(out), dtype=np.int64)
+    queries = []
+    for w, (seg, pos, odd, end) in enumerate(src):
+        t = got["tgt"][toff[w]:toff[w + 1]]
+        assert t.tobytes() == np.where(odd == 1, _COMP[out[pos]], out[pos]).astype(np.uint8).tobytes(), ("walk", w)
+        want += np.bincount(pos, minlength=len(out))
+        queries.append(t.tobytes())
+    flags = [2 * int(w in bad) for w in range(nw)]
+    s, st, pile = raw_pileup(eng, walks, su, strings, overlap, queries, flags, [[] if w in bad else [(lens[w], EQ)] for w in range(nw)])
+    assert s == 0, (s, eng.lib.s2k_last_error(eng.ctx))
+    assert_pile(pile, {**new_pile(len(out)), "match": want.astype(np.uint32)}, len(out), "cursor")
+    assert st[:2] == [64, 1] and st[2:] == [0] * (len(st) - 2), st
+
+
+@pytest.mark.gpu
+def test_device_targets_and_pileup_share_the_step_cursor(eng):
+    device_cursor(eng)
+
+
 @pytest.mark.gpu
 def test_device_pileup_random_decompositions(eng):
     """random node records give junctions above a length (bad walks, flagged) among sound ones, circular unitigs walked round, both

@@ -699,6 +699,7 @@ def test_pileup(eng):
     q, fl, runs = tp.aligned_case(walks, su, strings, ov, rng, 6)
     for ms in (0, tp.MAX_SHIFT):
         tp.device_pileup(eng, walks, su, strings, ov, q, fl, runs, ("hand", ms), max_shift=ms)
+    tp.device_cursor(eng)
     two = [ta.random_seq(rng, 300), ta.random_seq(rng, 41)]
     z4 = np.zeros(4, dtype=np.uint32)
     for n in SIZES:
