@@ -103,7 +103,7 @@ def main():
     t = u["n_unitigs"]
 
     table = pkg.CountTable(eng, keys, counts)
-    i = pkg._seq_in(out, n_reads)
+    i = pkg.extraction_struct(out, n_reads, ("rev",), mn=True)
     rep = torch.full((n_nodes,), -1, dtype=torch.int64, device=dev)
     torch.cuda.synchronize(dev)
     H = ctypes.c_void_p(table.handle)

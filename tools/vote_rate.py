@@ -52,7 +52,7 @@ def main():
     moved = int((voted.rep != early.rep).sum())
 
     # the steps of the voted build, one by one
-    i, nk = pkg._seq_in(out, n_reads), ctypes.c_uint64(0)
+    i, nk = pkg.extraction_struct(out, n_reads, ("rev",), mn=True), ctypes.c_uint64(0)
     H = ctypes.c_void_p(table.handle)
     args = (H, n_reads, ctypes.byref(i), k, bases.data_ptr(), read_off.data_ptr())
     _, ms_size = timed(torch, dev, lambda: eng._check(eng.lib.s2k_table_vote_keys(*args, None, 0, ctypes.byref(nk))), a.reps, a.warmup)
