@@ -987,10 +987,13 @@ s2k_status s2k_align_pairs(s2k_ctx *ctx, const uint8_t *d_query, uint64_t n_quer
  * equal piles.  Workspace (the context's grow-only count workspace): 24 B per step, 13 B per walk, 28 B per run slot, 16 B per base.
  * Runs on the context's stream; returns when the pile is written.
  * Not done: votes on both copies of an overlapped base (a unitig's head that is entered along an edge is voted only by walks that start
- * in it); insertions of two or more bases (counted in ins_long, never called); quality values; a pile over several devices. */
+ * in it); quality values; a pile over several devices.  Insertions of two or more bases: s2k_walks_pileup_ex below. */
 #define S2K_PILEUP_MAX_SHIFT 64u
 #define S2K_PILEUP_STATS 8
 #define S2K_CONSENSUS_STATS 8
+#define S2K_LONG_INS_MIN 2u  /* the shortest and the longest I run that gets a vote key (s2k_walks_pileup_ex) */
+#define S2K_LONG_INS_MAX 12u
+#define S2K_LONG_INS_POS_BITS 36 /* a vote key holds this many bits of the position: n_bases < 2^36 */
 typedef struct s2k_pile { /* device pointers, n_bases uint32_t each */
     uint32_t *match;
     uint32_t *del;
@@ -1003,6 +1006,32 @@ s2k_status s2k_walks_pileup(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_fi
                             const uint8_t *d_out, uint64_t n_bases, const uint32_t *d_overlap, uint64_t n_unitigs, const uint8_t *d_query,
                             uint64_t n_query_bytes, const uint64_t *d_q_begin, const uint32_t *d_align_flags, const uint64_t *d_ops_off,
                             const uint32_t *d_n_ops, const uint32_t *d_ops, uint64_t n_ops_total, uint32_t max_shift, const s2k_pile *pile, uint64_t *stats);
+/* Pile-up with the vote keys of long insertions.  The arguments, the checks, the pile written (bit for bit, ins_long
+ * counts every long run, keyed or not) and the stats words are those of s2k_walks_pileup.
+ * A keyed run is an I run of a voting walk of S2K_LONG_INS_MIN <= n <= S2K_LONG_INS_MAX bytes, every byte with a code, that the rule
+ * above neither drops (n_empty_ins, n_end_ins) nor skips.  With g, d and c (the inserted bytes in forward orientation) as above, the
+ * run is inserted before forward position at = g - d and reads there s[i] = c[(i - d) mod n], i = 0 .. n - 1 (c rotated right by
+ * d mod n).  Its key is
+ *     rev36(at) << 28 | n << 24 | sum_i code(s[i]) << (22 - 2 i)
+ * rev36 the reversal of the low 36 bits of at; unused code bits 0; codes on the forward strand.  All candidates of one position are
+ * one range of a sorted table; the reversed position spreads the top digits of the counter's radix partition; n is never 15, so no
+ * key is the counter's empty value 2^64 - 1.  The keys go to an s2k_counter (s2k_counter_add) batch by batch; the multiset of keys is
+ * a function of the multiset of walks, whatever the batch cut.
+ * *n_candidates (host, always set; 0 on a refusal by a check): the I runs of voting walks with 2 <= n <= 12, known from the run slots
+ * before anything is written.  d_long_keys NULL: no keys, *n_long_keys = 0.  d_long_keys given and capacity < *n_candidates:
+ * S2K_ERR_CAPACITY and nothing at all is written, the pile included.  Otherwise the keys of the keyed runs stand compact in
+ * d_long_keys[0 .. *n_long_keys), in run-slot order: a flag per run slot and a scan, no atomic cursor; two calls are bit-identical.
+ * S2K_ERR_INVALID_ARG on the host, before any launch: d_long_keys given with n_bases >= 2^36; n_candidates or n_long_keys NULL.
+ * One lane per run; the lane of a keyed run reads its at most 12 bytes.  Workspace: with d_long_keys 12 B more per run slot (flag, key).
+ * Not keyed, counted in ins_long only: runs above 12 bytes or with a byte without a code.  Not done: an insertion that the aligner
+ * split into two I runs is not merged. */
+s2k_status s2k_walks_pileup_ex(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_first_step, const uint32_t *d_n_steps, const uint64_t *d_path_start,
+                               const uint64_t *d_path_end, const uint32_t *d_flags, const uint32_t *d_step_unitig, uint64_t n_steps,
+                               const uint64_t *d_out_off, const uint8_t *d_out, uint64_t n_bases, const uint32_t *d_overlap, uint64_t n_unitigs,
+                               const uint8_t *d_query, uint64_t n_query_bytes, const uint64_t *d_q_begin, const uint32_t *d_align_flags,
+                               const uint64_t *d_ops_off, const uint32_t *d_n_ops, const uint32_t *d_ops, uint64_t n_ops_total, uint32_t max_shift,
+                               const s2k_pile *pile, uint64_t *stats, uint64_t *d_long_keys, uint64_t capacity, uint64_t *n_candidates,
+                               uint64_t *n_long_keys);
 /* Consensus, once per graph; the pile is only read, so more batches may be added afterwards.  Per position p of a unitig, cur = the code
  * of out[p] (none for another byte): tot[c] = sub[c][p] + (c == cur ? match[p] : 0); for a byte without a code match[p] counts for
  * the byte itself as a fifth candidate; depth = match + the four sub + del.  depth < min_cov: the byte is kept, nothing is inserted,
@@ -1010,7 +1039,7 @@ s2k_status s2k_walks_pileup(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_fi
  * 2 ins[best][p] > depth the letter ACGT[best] is emitted (n_ins).  Then the base: if del[p] is strictly above every candidate nothing
  * is emitted (n_del); otherwise, if the current byte's count equals the largest, the byte is kept as it is, case included; otherwise
  * the upper-case letter of the smallest code with the largest count is emitted (n_sub).  A position with 2 ins_long[p] > depth is
- * counted (n_long) and otherwise left alone.
+ * counted (n_long) and otherwise left alone (s2k_pileup_consensus_ex below calls it).
  * Outputs (each may be NULL): d_new_out_off (n_unitigs + 1); d_new_out (16-byte aligned; capacity in bytes; for s2k_walks_targets to
  * read it its allocation must be whole 8-byte words, as d_out's); d_pos_map (n_bases + 1): the new position of every old one, an
  * inserted letter belongs to the position it precedes, pos_map[n_bases] = *n_new_bases; d_new_overlap (2 n_unitigs): with ov' =
@@ -1027,6 +1056,23 @@ s2k_status s2k_walks_pileup(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_fi
 s2k_status s2k_pileup_consensus(s2k_ctx *ctx, const s2k_pile *pile, const uint64_t *d_out_off, const uint8_t *d_out, uint64_t n_bases,
                                 const uint32_t *d_overlap, uint64_t n_unitigs, uint32_t min_cov, uint64_t *d_new_out_off, uint8_t *d_new_out,
                                 uint64_t capacity, uint64_t *d_pos_map, uint32_t *d_new_overlap, uint64_t *n_new_bases, uint64_t *stats);
+/* Consensus that calls insertions of two or more bases from a table of vote keys: d_long_keys (strictly ascending) and
+ * d_long_counts, n_long_keys of each, as s2k_counter_finish writes them for the keys of s2k_walks_pileup_ex.  With n_long_keys == 0 it
+ * is s2k_pileup_consensus in every output and every stats word.  Otherwise, at a position p with depth >= min_cov, the insertion before
+ * p: cs = the count of the best single letter as above; the candidates of p are the entries with key >> 28 == rev36(p); L the candidate
+ * with the largest count, the smallest key among equals, cl its count (0 without a candidate).  cl > cs and 2 cl > depth: the n
+ * upper-case letters of L are emitted, stats[5] (n_ins_long) counts the position and stats[6] (n_ins_long_bases) gains n.  Otherwise, if
+ * 2 cs > depth, the single letter as above.  The base at p is decided as above.  n_long counts the positions with 2 ins_long[p] > depth
+ * at which no long insertion was called.  The counts are trusted; a lane searches the table only where 2 ins_long[p] > depth (cl <=
+ * ins_long[p]).  pos_map, new_out_off and new_overlap keep their definitions: inserted letters belong to the position they precede.
+ * Checked on the device before anything is written, S2K_ERR_INVALID_ARG otherwise: keys strictly ascending, every n field in
+ * S2K_LONG_INS_MIN .. S2K_LONG_INS_MAX.  On the host: a table with n_bases >= 2^36 or of 2^32 - 1 keys or more, a NULL table array.
+ * A position emits 0 to 13 bytes: the call leaves the candidate's index per position, the input-ordered write decodes its letters from
+ * the key.  Workspace: 18 B per base with a table, 14 B without. */
+s2k_status s2k_pileup_consensus_ex(s2k_ctx *ctx, const s2k_pile *pile, const uint64_t *d_out_off, const uint8_t *d_out, uint64_t n_bases,
+                                   const uint32_t *d_overlap, uint64_t n_unitigs, uint32_t min_cov, uint64_t *d_new_out_off, uint8_t *d_new_out,
+                                   uint64_t capacity, uint64_t *d_pos_map, uint32_t *d_new_overlap, uint64_t *n_new_bases, uint64_t *stats,
+                                   const uint64_t *d_long_keys, const uint32_t *d_long_counts, uint64_t n_long_keys);
 /* ---- segmented alignment: long walks cut at anchor k-min-mers, aligned piece by piece, joined --------------------------
  * s2k_align_pairs aligns at most S2K_ALIGN_MAX_EDITS edits per pair, and a walk of a long noisy read passes that.  Every solid item of
  * a threaded step is an exact anchor between the read and the walk's stitched path; s2k_walks_segments cuts a walk at a thinned,

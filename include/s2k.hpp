@@ -413,6 +413,37 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return t;
     }
+    // s2k_walks_pileup_ex: walks_pileup, and the vote keys of the batch's insertions of S2K_LONG_INS_MIN .. S2K_LONG_INS_MAX bases written
+    // compact to d_long_keys (capacity in keys; nullptr: none).  n_candidates bounds the keys and is set on S2K_ERR_CAPACITY too, which
+    // throws (nothing written, the pile included): size the buffer by a count of such I runs over al.ops, or retry with n_candidates.
+    struct PileupKeys {
+        PileupStats stats;
+        uint64_t n_candidates, n_long_keys;
+    };
+    PileupKeys walks_pileup_ex(const s2k_walk_out &walks, const uint32_t *d_step_unitig, uint64_t n_steps, const uint64_t *d_out_off, const uint8_t *d_out,
+                               uint64_t n_bases, const uint32_t *d_overlap, uint64_t n_unitigs, const Pool &query, const s2k_align_out &al, const s2k_pile &pile,
+                               uint64_t *d_long_keys, uint64_t capacity, uint32_t max_shift = S2K_PILEUP_MAX_SHIFT, uint64_t *n_candidates = nullptr) {
+        PileupKeys t{};
+        s2k_status st = s2k_walks_pileup_ex(ctx_, walks.capacity, walks.first_step, walks.n_steps, walks.path_start, walks.path_end, walks.flags, d_step_unitig,
+                                            n_steps, d_out_off, d_out, n_bases, d_overlap, n_unitigs, query.bytes, query.n_bytes, query.begin, al.flags,
+                                            al.ops_off, al.n_ops, al.ops, al.capacity, max_shift, &pile, t.stats.v, d_long_keys, capacity, &t.n_candidates,
+                                            &t.n_long_keys);
+        if (n_candidates) *n_candidates = t.n_candidates;
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
+    // s2k_pileup_consensus_ex: pileup_consensus with the counted vote keys (ascending, as s2k_counter_finish writes them); stats[5] and
+    // stats[6] are the positions and the bases of the long insertions called.  n_long_keys 0: pileup_consensus.
+    Consensus pileup_consensus_ex(const s2k_pile &pile, const uint64_t *d_out_off, const uint8_t *d_out, uint64_t n_bases, const uint32_t *d_overlap,
+                                  uint64_t n_unitigs, uint32_t min_cov, const uint64_t *d_long_keys, const uint32_t *d_long_counts, uint64_t n_long_keys,
+                                  uint64_t *d_new_out_off = nullptr, uint8_t *d_new_out = nullptr, uint64_t capacity = 0, uint64_t *d_pos_map = nullptr,
+                                  uint32_t *d_new_overlap = nullptr) {
+        Consensus t{};
+        s2k_status st = s2k_pileup_consensus_ex(ctx_, &pile, d_out_off, d_out, n_bases, d_overlap, n_unitigs, min_cov, d_new_out_off, d_new_out, capacity,
+                                                d_pos_map, d_new_overlap, &t.n_new_bases, t.stats, d_long_keys, d_long_counts, n_long_keys);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
     // s2k_walks_segments: every walk cut into segment pairs at a thinned, strictly increasing subset of its anchor k-min-mers (`walks`:
     // the records s2k_paths_walks wrote, walk_off included; `paths`: unitig, pos, count of the steps they were made on; `lift`: the
     // decomposition and its base coordinates as paths_walks takes them; d_q_begin, d_tgt_off, d_bad per walk; `source`: the paths

@@ -23,8 +23,8 @@ import os  # noqa: F401
 import numpy as np  # noqa: F401
 
 from ._abi import (ABI_SYMBOLS, ABI_VERSION, ALIGN_BAD_PATH, ALIGN_MAX_EDITS, ALIGN_OVER, ALIGN_WAVES, CIGAR_CHARS, CIGAR_D, CIGAR_EQ, CIGAR_I,  # noqa: F401
-                   CIGAR_X, CONSENSUS_STATS, CONSENSUS_STATS_WORDS, COUNT_SORTED, FLAG_FORCE_SERIAL, FLAG_LEGACY_PATH, FLAG_NO_PACK2, FLAG_WANT_MINIMIZERS,
-                   HPC_RLE_ALPHABET, LIB_PATH, NO_COPY, NO_EDGE, NO_PARTNER, NO_STEP, PILEUP_MAX_SHIFT, PILEUP_PLANES, PILEUP_STATS, PILEUP_STATS_WORDS,
+                   CIGAR_X, CONSENSUS_LONG_STATS, CONSENSUS_STATS, CONSENSUS_STATS_WORDS, COUNT_SORTED, FLAG_FORCE_SERIAL, FLAG_LEGACY_PATH, FLAG_NO_PACK2, FLAG_WANT_MINIMIZERS,
+                   HPC_RLE_ALPHABET, LIB_PATH, LONG_INS_MAX, LONG_INS_MIN, LONG_INS_POS_BITS, NO_COPY, NO_EDGE, NO_PARTNER, NO_STEP, PILEUP_MAX_SHIFT, PILEUP_PLANES, PILEUP_STATS, PILEUP_STATS_WORDS,
                    PROTOTYPES, SEGMENT_LEN, SEGMENT_MIN_LEN, SEGMENT_STATS, SEGMENT_STATS_WORDS, STEP_LINKED, WALK_CIRCULAR, AlignOut, Counts, DeviceOut,
                    HashMode, NodePlace, NodeSeqs, Params, Pile, Result, S2kError, SegmentOut, SolidOut, ThreadOut, UnitigOut, WalkOut, hash_bound,
                    load_library)
@@ -33,6 +33,6 @@ from .engine import Engine  # noqa: F401
 from .iterators import (KminmerHash, KminmersIterator, NtHashHPCIterator, NtHashHPCSIMDIterator, NtHashSIMDIterator, RegularMinimizers,  # noqa: F401
                         default_engine, encode_rle, encode_rle_simd, hpc)
 from .pipeline import (ContigLift, CountTable, KminmerCounter, KminmerGraph, NodeSequences, PathOrigin, Pileup, PolishedSequences, ReadPaths,  # noqa: F401
-                       ReadWalks, SpanTable, UnitigGraph, WalkAlignments, walk_query_intervals)
+                       ReadWalks, SpanTable, UnitigGraph, WalkAlignments, decode_long_keys, walk_query_intervals)
 from .writers import (FastxReader, alignment_block_len, cigar_string, revcomp, write_fasta, write_gaf_walks, write_gfa, write_read_paths,  # noqa: F401
                       write_spans, write_unitig_gfa)

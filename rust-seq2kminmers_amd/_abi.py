@@ -48,6 +48,9 @@ PILEUP_PLANES = ("match", "del", "sub0", "sub1", "sub2", "sub3", "ins0", "ins1",
 PILEUP_STATS = ("walks_used", "walks_skipped", "n_other", "n_end_ins", "n_shifted", "n_empty_ins")  # s2k_walks_pileup: stats[0 .. 6)
 CONSENSUS_STATS = ("n_low", "n_sub", "n_del", "n_ins", "n_long")  # s2k_pileup_consensus: stats[0 .. 5)
 PILEUP_STATS_WORDS = CONSENSUS_STATS_WORDS = 8
+CONSENSUS_LONG_STATS = CONSENSUS_STATS + ("n_ins_long", "n_ins_long_bases")  # s2k_pileup_consensus_ex: stats[0 .. 7)
+LONG_INS_MIN, LONG_INS_MAX = 2, 12  # s2k_walks_pileup_ex: the I runs that get a vote key
+LONG_INS_POS_BITS = 36  # the bits of the position a vote key holds
 NO_STEP = 0xFFFFFFFFFFFFFFFF  # s2k_walks_segments: d_src_step of a source step that went into no step of the walks' paths
 SEGMENT_LEN = 512  # s2k_walks_segments: the default seg_len, in query bases
 SEGMENT_MIN_LEN = 64  # s2k_walks_segments: the smallest seg_len
@@ -199,7 +202,10 @@ PROTOTYPES = {
     "s2k_align_pairs": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u32, _P(AlignOut), _n64]),
     "s2k_walks_pileup": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64,
                                 _u32, _P(Pile), _n64]),
+    "s2k_walks_pileup_ex": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64,
+                                   _u32, _P(Pile), _n64, _vp, _u64, _n64, _n64]),
     "s2k_pileup_consensus": (_int, [_vp, _P(Pile), _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _vp, _n64, _n64]),
+    "s2k_pileup_consensus_ex": (_int, [_vp, _P(Pile), _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _vp, _n64, _n64, _vp, _vp, _u64]),
     "s2k_walks_segments": (_int, [_vp, _u64, _P(WalkOut), _u64, _P(ThreadOut), _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _P(ThreadOut),
                                   _u64, _vp, _vp, _P(DeviceOut), _u32, _P(SegmentOut), _n64, _n64]),
     "s2k_align_join": (_int, [_vp, _u64, _vp, _vp, _u64, _P(AlignOut), _P(AlignOut), _n64]),

@@ -4,8 +4,8 @@ import os
 
 import numpy as np
 
-from ._abi import (ALIGN_MAX_EDITS, CONSENSUS_STATS, CONSENSUS_STATS_WORDS, COUNT_SORTED, FLAG_FORCE_SERIAL, FLAG_LEGACY_PATH, FLAG_NO_PACK2,
-                   FLAG_WANT_MINIMIZERS, HPC_RLE_ALPHABET, PILEUP_MAX_SHIFT, PILEUP_PLANES, PILEUP_STATS, PILEUP_STATS_WORDS, SEGMENT_LEN, SEGMENT_STATS,
+from ._abi import (ALIGN_MAX_EDITS, CIGAR_I, CONSENSUS_LONG_STATS, CONSENSUS_STATS, CONSENSUS_STATS_WORDS, COUNT_SORTED, FLAG_FORCE_SERIAL, FLAG_LEGACY_PATH, FLAG_NO_PACK2,
+                   FLAG_WANT_MINIMIZERS, HPC_RLE_ALPHABET, LONG_INS_MAX, LONG_INS_MIN, PILEUP_MAX_SHIFT, PILEUP_PLANES, PILEUP_STATS, PILEUP_STATS_WORDS, SEGMENT_LEN, SEGMENT_STATS,
                    SEGMENT_STATS_WORDS, STEP_FIELDS, AlignOut, Counts, DeviceOut, HashMode, Params, Pile, Result, S2kError, SegmentOut, ThreadOut, UnitigOut,
                    WalkOut, _Handle, load_library, torch)
 from ._args import (_align_out, _as_u8, _graph_arg, _outer_arg, _p, _paths_out, _paths_result, _paths_struct, _shaped, _stitch_arg, _walk_args,
@@ -705,45 +705,81 @@ class Engine(_Handle):
             p.sub[c], p.ins[c] = row[2 + c], row[6 + c]
         return p
 
+    def _pileup_args(self, name, walks, step_unitig, out_off, out, overlap, query, q_begin, alignments, planes, max_shift):
+        """what walks_pileup and walks_pileup_ex (name) share -> (device, the C arguments ctx .. max_shift, the pile, the tensors to keep alive)"""
+        nw, dev, wargs, keep = _walk_args(name, walks, step_unitig, out_off, out, overlap)
+        query, q_begin = query.contiguous(), q_begin.contiguous()
+        al = [getattr(alignments, f).contiguous() for f in ("flags", "ops_off", "n_ops", "ops")]
+        if (query.element_size() != 1 or q_begin.numel() != nw or q_begin.element_size() != 8 or [x.element_size() for x in al] != [4, 8, 4, 4]
+                or al[0].numel() < nw or al[2].numel() < nw or al[1].numel() != nw + 1):
+            raise ValueError(name + " wants the batch's bases, one 64-bit interval start per walk and the alignment arrays of these walks")
+        pile = self._pile_struct(planes, out.numel())
+        args = (self.ctx, *wargs, _p(query, query.numel()), query.numel(), _p(q_begin, nw), _p(al[0], nw), _p(al[1]), _p(al[2], nw), _p(al[3], al[3].numel()),
+                al[3].numel(), int(max_shift))
+        return dev, args, pile, (keep, query, q_begin, al)
+
+    def walks_pileup_ex(self, walks, step_unitig, out_off, out, overlap, query, q_begin, alignments, planes, max_shift=PILEUP_MAX_SHIFT):
+        """walks_pileup, and the vote keys of the batch's long insertions (s2k_walks_pileup_ex; the key is defined in include/s2k.h).
+        The key buffer is sized by a count of the I runs of 2 .. 12 bytes over all run words, which bounds n_candidates.  -> (dict
+        of the PILEUP_STATS counters, keys: 1-D int64 GPU tensor whose bits are the uint64 keys, in run-slot order, n_candidates)."""
+        dev, args, pile, keep = self._pileup_args("walks_pileup_ex", walks, step_unitig, out_off, out, overlap, query, q_begin, alignments, planes, max_shift)
+        ops = keep[3][3]
+        n = ops >> 4 & 0x0FFFFFFF  # (the run words are uint32 in an int32 tensor)
+        cap = int(((ops & 15) == CIGAR_I).logical_and(n >= LONG_INS_MIN).logical_and(n <= LONG_INS_MAX).sum()) if ops.numel() else 0
+        buf = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        stats, nc, nk = (C.c_uint64 * PILEUP_STATS_WORDS)(), C.c_uint64(0), C.c_uint64(0)
+        self._run(self.lib.s2k_walks_pileup_ex, dev, *args, C.byref(pile), stats, _p(buf), cap, C.byref(nc), C.byref(nk))
+        return {f: int(stats[i]) for i, f in enumerate(PILEUP_STATS)}, buf[:int(nk.value)], int(nc.value)
+
     def walks_pileup(self, walks, step_unitig, out_off, out, overlap, query, q_begin, alignments, planes, max_shift=PILEUP_MAX_SHIFT):
         """The votes of one batch's aligned walks added to a pile (s2k_walks_pileup; the rule is in include/s2k.h).  walks, step_unitig,
         out_off, out, overlap: as walks_targets takes them; query: the batch's bases (uint8 GPU tensor); q_begin: where every walk's
         read interval starts in them (int64); alignments: a WalkAlignments (or anything with flags, ops_off, n_ops, ops) of these
         walks; planes: the (11, n_bases) int32 GPU tensor of the pile, rows in the order of PILEUP_PLANES, zeroed before the first
         batch -- it gains the votes.  -> dict of the PILEUP_STATS counters of this call."""
-        nw, dev, wargs, keep = _walk_args("walks_pileup", walks, step_unitig, out_off, out, overlap)
-        query, q_begin = query.contiguous(), q_begin.contiguous()
-        al = [getattr(alignments, f).contiguous() for f in ("flags", "ops_off", "n_ops", "ops")]
-        if (query.element_size() != 1 or q_begin.numel() != nw or q_begin.element_size() != 8 or [x.element_size() for x in al] != [4, 8, 4, 4]
-                or al[0].numel() < nw or al[2].numel() < nw or al[1].numel() != nw + 1):
-            raise ValueError("walks_pileup wants the batch's bases, one 64-bit interval start per walk and the alignment arrays of these walks")
-        pile = self._pile_struct(planes, out.numel())
+        dev, args, pile, keep = self._pileup_args("walks_pileup", walks, step_unitig, out_off, out, overlap, query, q_begin, alignments, planes, max_shift)
         stats = (C.c_uint64 * PILEUP_STATS_WORDS)()
-        self._run(self.lib.s2k_walks_pileup, dev, self.ctx, *wargs, _p(query, query.numel()), query.numel(), _p(q_begin, nw), _p(al[0], nw), _p(al[1]),
-                  _p(al[2], nw), _p(al[3], al[3].numel()), al[3].numel(), int(max_shift), C.byref(pile), stats)
+        self._run(self.lib.s2k_walks_pileup, dev, *args, C.byref(pile), stats)
         return {f: int(stats[i]) for i, f in enumerate(PILEUP_STATS)}
+
+    def pileup_consensus_ex(self, planes, out_off, out, overlap, min_cov=3, long_keys=None, long_counts=None):
+        """pileup_consensus with a table of long-insertion vote keys (s2k_pileup_consensus_ex): long_keys (64-bit, strictly ascending as
+        uint64) and long_counts (32-bit), GPU tensors of one length as KminmerCounter.finish returns them; None or empty: pileup_consensus.
+        -> the same dict, stats with the CONSENSUS_LONG_STATS counters."""
+        return self._consensus(planes, out_off, out, overlap, min_cov, long_keys, long_counts, True)
 
     def pileup_consensus(self, planes, out_off, out, overlap, min_cov=3):
         """The polished bases of every unitig from a pile (s2k_pileup_consensus; the rule is in include/s2k.h).  planes: the pile, only
         read; out_off, out, overlap: the draft the pile was taken on.  Two calls: the size, then the bytes.  -> dict of GPU tensors
         out_off (int64, n_unitigs + 1), out (uint8), pos_map (int64, n_bases + 1), overlap (int32, 2 n_unitigs), the int n_bases and
         the CONSENSUS_STATS counters in stats."""
+        return self._consensus(planes, out_off, out, overlap, min_cov, None, None, False)
+
+    def _consensus(self, planes, out_off, out, overlap, min_cov, keys, counts, ex):
         out_off, out, overlap = (x.contiguous() for x in (out_off, out, overlap))
         t, nb, dev = out_off.numel() - 1, out.numel(), out_off.device
         if out_off.element_size() != 8 or out.element_size() != 1 or overlap.numel() != 2 * t or overlap.element_size() != 4:
-            raise ValueError("pileup_consensus wants the out_off, out and overlap of the unitig sequences")
+            raise ValueError("pileup_consensus%s wants the out_off, out and overlap of the unitig sequences" % ("_ex" if ex else ""))
         pile = self._pile_struct(planes, nb)
         args = (self.ctx, C.byref(pile), _p(out_off), _p(out, nb), nb, _p(overlap, t), t, int(min_cov))
         n, stats = C.c_uint64(0), (C.c_uint64 * CONSENSUS_STATS_WORDS)()
-        self._run(self.lib.s2k_pileup_consensus, dev, *args, None, None, 0, None, None, C.byref(n), stats)
+        fn, tail, names = self.lib.s2k_pileup_consensus, (), CONSENSUS_STATS
+        if ex:
+            nk = 0 if keys is None else keys.numel()
+            if nk:
+                keys, counts = keys.contiguous(), counts.contiguous()
+                if keys.element_size() != 8 or counts.element_size() != 4 or counts.numel() != nk:
+                    raise ValueError("pileup_consensus_ex wants 64-bit keys and as many 32-bit counts")
+            fn, tail, names = self.lib.s2k_pileup_consensus_ex, ((_p(keys), _p(counts), nk) if nk else (None, None, 0)), CONSENSUS_LONG_STATS
+        self._run(fn, dev, *args, None, None, 0, None, None, C.byref(n), stats, *tail)
         m = int(n.value)
         new_off = torch.zeros(t + 1, dtype=torch.int64, device=dev)
         new_out = torch.zeros((max(m, 1) + 7) // 8 * 8, dtype=torch.uint8, device=dev)  # whole 8-byte words: walks_targets can read it
         pos_map = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
         new_ov = torch.zeros(max(2 * t, 1), dtype=torch.int32, device=dev)
-        self._run(self.lib.s2k_pileup_consensus, dev, *args, _p(new_off), _p(new_out), m, _p(pos_map), _p(new_ov, t), C.byref(n), stats)
+        self._run(fn, dev, *args, _p(new_off), _p(new_out), m, _p(pos_map), _p(new_ov, t), C.byref(n), stats, *tail)
         return {"out_off": new_off, "out": new_out[:m], "pos_map": pos_map, "overlap": new_ov[:2 * t], "n_bases": m,
-                "stats": {f: int(stats[i]) for i, f in enumerate(CONSENSUS_STATS)}}
+                "stats": {f: int(stats[i]) for i, f in enumerate(names)}}
 
     def partition_device(self, d_hash, n, n_parts, d_out, d_part_off):
         """keys grouped by hash prefix into n_parts ranges (the send buffers of the all-to-all)"""

@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (ALIGN_BAD_PATH, ALIGN_MAX_EDITS, ALIGN_OVER, PILEUP_MAX_SHIFT, PILEUP_PLANES, PILEUP_STATS, SEGMENT_LEN, STEP_FIELDS, WALK_FIELDS, NodeSeqs,
+from ._abi import (ALIGN_BAD_PATH, ALIGN_MAX_EDITS, ALIGN_OVER, LONG_INS_POS_BITS, PILEUP_MAX_SHIFT, PILEUP_PLANES, PILEUP_STATS, SEGMENT_LEN, STEP_FIELDS, WALK_FIELDS, NodeSeqs,
                    S2kError, SolidOut, ThreadOut, _Handle, torch)
 from ._args import _p, extraction_struct
 from .writers import alignment_block_len, cigar_string, write_gaf_walks, write_gfa, write_read_paths, write_spans, write_unitig_gfa
@@ -559,13 +559,14 @@ class UnitigGraph:
         al.segments = dict(sg["stats"], n_segments=sg["n_segments"], n_over_segments=int((a["flags"] & ALIGN_OVER).ne(0).sum()))
         return al
 
-    def pileup(self, engine, sequences):
+    def pileup(self, engine, sequences, long_ins=False):
         """An empty pile over this graph's draft bases -> Pileup.  sequences: the pair self.sequences returned.  Pileup.add takes the
         walks and alignments of one batch after self.align; Pileup.consensus gives the polished bases.  It works as it is on
-        simplified graphs and on the contigs of untangle_map with lifted paths."""
+        simplified graphs and on the contigs of untangle_map with lifted paths.  long_ins: insertions of 2 .. 12 bases are voted by
+        key and called too; the Pileup then owns a KminmerCounter: close() it before the engine."""
         if getattr(self, "overlap", None) is None:
             raise ValueError("pileup wants the pair that self.sequences(engine, node_seqs) returned")
-        return Pileup(self, sequences)
+        return Pileup(self, sequences, engine if long_ins else None)
 
     def write_gfa(self, path, members=False, sequences=None):
         """GFA 1: an S line per unitig (name = its index, sequence *, LN:i: its number of members, KC:i: the summed count; with
@@ -735,20 +736,37 @@ class Pileup:
     """The votes of aligned read walks on the bases of a UnitigGraph's draft (UnitigGraph.pileup; include/s2k.h: s2k_walks_pileup,
     s2k_pileup_consensus): planes, an (11, n_bases) int32 GPU tensor with one row per plane of PILEUP_PLANES (match, del, sub0..3,
     ins0..3, ins_long), indexed by position in the draft `sequences` = (out_off, out); graph, the UnitigGraph.  add() once per batch,
-    from file to file; consensus() whenever wanted, the pile is only read."""
+    from file to file; consensus() whenever wanted, the pile is only read.  With long_ins (UnitigGraph.pileup(long_ins=True)) every add()
+    also feeds the vote keys of the batch's insertions of 2 .. 12 bases (s2k_walks_pileup_ex) to a KminmerCounter of its own, consensus()
+    calls them from its table (s2k_pileup_consensus_ex), and close() frees the counter."""
 
-    def __init__(self, graph, sequences):
+    def __init__(self, graph, sequences, long_ins_engine=None):
         self.graph, self.sequences = graph, sequences
         self.planes = torch.zeros((len(PILEUP_PLANES), max(sequences[1].numel(), 1)), dtype=torch.int32, device=sequences[1].device)
         self.stats = {f: 0 for f in PILEUP_STATS}
+        self.long_ins = long_ins_engine is not None
+        self.counter = KminmerCounter(long_ins_engine) if self.long_ins else None
+        self.n_long_keys = self.n_long_candidates = 0  # over all batches: keyed runs, and I runs of 2 .. 12 bytes
+
+    def close(self):
+        if self.counter is not None:
+            self.counter.close()
+            self.counter = None
 
     def add(self, engine, walks, alignments, bases, read_off, max_shift=PILEUP_MAX_SHIFT):
         """One batch's votes: walks, the ReadWalks graph.walks returned; alignments, the WalkAlignments graph.align returned for them;
         bases, read_off: the batch's bases and read offsets on the GPU.  -> the PILEUP_STATS counters of this batch (self.stats sums
         them)."""
         qb, _ = walk_query_intervals(walks, read_off)
-        st = engine.walks_pileup(walks, walks.paths.unitig, self.sequences[0], self.sequences[1], self.graph.overlap, bases, qb, alignments, self.planes,
-                                 max_shift)
+        if self.long_ins:
+            st, keys, nc = engine.walks_pileup_ex(walks, walks.paths.unitig, self.sequences[0], self.sequences[1], self.graph.overlap, bases, qb, alignments,
+                                                  self.planes, max_shift)
+            self.counter.add_tensor(keys)
+            self.n_long_keys += keys.numel()
+            self.n_long_candidates += nc
+        else:
+            st = engine.walks_pileup(walks, walks.paths.unitig, self.sequences[0], self.sequences[1], self.graph.overlap, bases, qb, alignments, self.planes,
+                                     max_shift)
         for f, v in st.items():
             self.stats[f] += v
         return st
@@ -768,11 +786,34 @@ class Pileup:
         """The polished bases (Engine.pileup_consensus) -> PolishedSequences"""
         import copy
 
-        c = engine.pileup_consensus(self.planes, self.sequences[0], self.sequences[1], self.graph.overlap, min_cov)
+        if self.long_ins:  # a called candidate has 2 count > depth >= min_cov: the cutoff drops none of them
+            keys, counts = self.counter.finish(min_count=int(min_cov) // 2 + 1)
+            c = engine.pileup_consensus_ex(self.planes, self.sequences[0], self.sequences[1], self.graph.overlap, min_cov, keys, counts)
+        else:
+            c = engine.pileup_consensus(self.planes, self.sequences[0], self.sequences[1], self.graph.overlap, min_cov)
         g = copy.copy(self.graph)
         g.overlap = c["overlap"]
         g._member_offsets = None  # member offsets are not remapped onto the polished coordinates
         return PolishedSequences((c["out_off"], c["out"]), c["overlap"], c["pos_map"], c["stats"], g)
+
+
+    def long_insertions(self, min_count=1):
+        """the candidates voted so far -> [(pos, letters, count)] ascending by draft position, then by length and letters; pos is the
+        position the letters would be inserted before"""
+        if not self.long_ins:
+            raise ValueError("long_insertions wants a Pileup made with long_ins=True")
+        keys, counts = self.counter.finish(min_count=min_count)
+        return decode_long_keys(keys.cpu().numpy().view(np.uint64), counts.cpu().numpy().view(np.uint32))
+
+
+def decode_long_keys(keys, counts):
+    """vote keys of long insertions (include/s2k.h: s2k_walks_pileup_ex) and their counts -> [(pos, letters, count)] sorted"""
+    out = []
+    for k, c in zip((int(x) for x in keys), (int(x) for x in counts)):
+        rev, n = k >> 28, k >> 24 & 15
+        pos = int(format(rev, "0%db" % LONG_INS_POS_BITS)[::-1], 2)
+        out.append((pos, bytes(b"ACGT"[k >> (22 - 2 * i) & 3] for i in range(n)), c))
+    return sorted(out)
 
 
 class PolishedSequences:

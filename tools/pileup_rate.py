@@ -6,7 +6,11 @@ median of --reps, HIP events on the engine's stream.
            the = and D pieces) and, when the library is a `make KNOBS=1` build loaded with S2K_LIB, by route B (S2K_PILEUP_ROUTE=B: one
            atomic add per matched base, consecutive lanes on consecutive positions); Pileup.consensus; and beside them Engine.align_pairs on
            the same walks: what the pile-up costs against the alignment it consumes.  Every add goes to a pile of its own that is zeroed
-           outside the timed region; the piles of the two routes are compared."""
+           outside the timed region; the piles of the two routes are compared.  Then the same add with the vote keys of long insertions
+           (UnitigGraph.pileup(long_ins=True): s2k_walks_pileup_ex, the count of the key buffer's size and the KminmerCounter's add,
+           DESIGN.md §3.23) and Pileup.consensus with the counter's table (s2k_counter_finish and s2k_pileup_consensus_ex).  The reads
+           carry substitutions only: the I runs they key are the aligner's equal-cost choices (about 45 000 keys).  --parent FILE: a JSON
+           that this tool wrote on the commit before §3.23, whose Pileup.add is set beside this one's."""
 import argparse
 import json
 import os
@@ -31,6 +35,7 @@ def main():
     ap.add_argument("--coverage", type=int, default=30)
     ap.add_argument("--rate", type=float, default=0.005)
     ap.add_argument("--min-cov", type=int, default=3)
+    ap.add_argument("--parent", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pileup_rate.json"))
     a = ap.parse_args()
     import torch
@@ -61,7 +66,7 @@ def main():
     _, ms_pairs = timed(torch, dev, lambda: eng.align_pairs(bases, t["tgt"], qb, qe, tb, te), a.reps, a.warmup)
     al = ug.align(eng, walks, bases, read_off, seqs)
 
-    def add_timed(route):
+    def add_timed(route, long_ins=False):
         """Pileup.add into a fresh pile per repetition, the zeroing outside the events -> (the last pile, its stats, the times)"""
         if route == "B":
             os.environ["S2K_PILEUP_ROUTE"] = "B"
@@ -69,7 +74,9 @@ def main():
             os.environ.pop("S2K_PILEUP_ROUTE", None)
         ms, pl, st = [], None, None
         for rep in range(a.warmup + a.reps):
-            pl = ug.pileup(eng, seqs)
+            if pl is not None and long_ins:
+                pl.close()
+            pl = ug.pileup(eng, seqs, long_ins=True) if long_ins else ug.pileup(eng, seqs)
             torch.cuda.synchronize(dev)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -88,6 +95,15 @@ def main():
         pile_b, stats_b, ms_b = add_timed("B")
         same = bool(torch.equal(pile_a.planes, pile_b.planes)) and stats == stats_b
     pol, ms_cons = timed(torch, dev, lambda: pile_a.consensus(eng, a.min_cov), a.reps, a.warmup)
+    pile_k, stats_k, ms_k = add_timed("A", long_ins=True)
+    same_k = bool(torch.equal(pile_a.planes, pile_k.planes)) and stats == stats_k
+    pol_k, ms_cons_k = timed(torch, dev, lambda: pile_k.consensus(eng, a.min_cov), a.reps, a.warmup)
+    long_keys = {"n_candidates": pile_k.n_long_candidates, "n_keys": pile_k.n_long_keys, "n_distinct": pile_k.counter.sizes(1)[0]}
+    pile_k.close()
+    parent = None
+    if a.parent:
+        with open(a.parent) as f:
+            parent = json.load(f)["genome"]["pileup_add_route_a"]
     n_walks, n_draft = walks.n_walks, int(seqs[1].numel())
     h = pile_a.planes.to(torch.int64)
     votes = {f: int(h[i].sum()) for i, f in enumerate(pkg.PILEUP_PLANES)}
@@ -102,7 +118,12 @@ def main():
                       "align_pairs": summary(ms_pairs), "pileup_add_route_a": dict(summary(ms_a), **rate(ms_a)),
                       "pileup_add_route_b": None if ms_b is None else dict(summary(ms_b), **rate(ms_b)), "routes_give_one_pile": same,
                       "pileup_consensus": dict(summary(ms_cons), draft_gbases_per_s=round(n_draft / (med(ms_cons) * 1e-3) / 1e9, 3)),
-                      "add_to_align_pairs": round(med(ms_a) / med(ms_pairs), 4)}}
+                      "add_to_align_pairs": round(med(ms_a) / med(ms_pairs), 4),
+                      "pileup_add_with_keys": dict(summary(ms_k), **rate(ms_k)), "keys_give_the_same_pile": same_k, "long_keys": long_keys,
+                      "pileup_consensus_with_table": dict(summary(ms_cons_k), draft_gbases_per_s=round(n_draft / (med(ms_cons_k) * 1e-3) / 1e9, 3)),
+                      "consensus_long_stats": pol_k.stats, "add_with_keys_to_align_pairs": round(med(ms_k) / med(ms_pairs), 4),
+                      "parent_pileup_add": parent,
+                      "add_with_keys_to_parent_add": None if parent is None else round(med(ms_k) / parent["ms_median"], 4)}}
     eng.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
