@@ -114,6 +114,9 @@ template <bool HPC> constexpr int jobcap() { return !HPC && S2K_TW_REG > 12 ? 16
 #endif
 constexpr int REG_LA = S2K_REG_LA;                     // seed look-ahead (positions) of the hash loop: the LDS round trip of a look-up is covered by
 constexpr int HPC_LA = S2K_HPC_LA;                     // LA positions of the lane's own arithmetic (4 registers per position of look-ahead)
+#ifndef S2K_PREVB_FLAT
+#define S2K_PREVB_FLAT 0 // 1 = the byte before the next tile comes by flat_load, as in rounds 1-9: every LDS wait of the Hpc kernel's tile loop is then lgkmcnt(0)
+#endif
 constexpr int NBL = 32;                                // read starts of a tile kept in LDS (hb / rs16); tiles with more search the read table
 // vector-memory operations one round of 64 hits issues: the counted vmcnt wait relies on it (tools/isa/check_vmcnt.py checks it).
 // Descriptor path: one store ({offset in the tile, span}); legacy path: three (j, jend, read index).
@@ -447,6 +450,8 @@ __device__ __forceinline__ void hash_loop_static(const uint8_t *D, uint32_t boun
     static_assert((CAPP == 16 || CAPP == 8) && LA <= 8, "capture pieces of 16 or 8 positions");
     uint32_t W[4 * ((T + L + 15) / 16)];
     const uint4 *src = reinterpret_cast<const uint4 *>(D + 16 * np * lane);
+    // (tools/isa/check_lgkmcnt.py follows every LDS read between the two marks to its first consumer: the waits in between must be counted ones)
+    asm volatile("; S2K_MARK hash_begin la=%0" ::"i"(LA));
     {
         const uint4 v0 = src[0], v1 = src[1];
         W[0] = v0.x; W[1] = v0.y; W[2] = v0.z; W[3] = v0.w;
@@ -465,6 +470,7 @@ __device__ __forceinline__ void hash_loop_static(const uint8_t *D, uint32_t boun
     for (int i = 0; i < LA; i++) EI[i] = (W2 && i % 2 == 0 && i + 1 < L) ? seed_pair<WARM_OFF>(A[i]) : seed_pair<0>(A[i]);
     uint32_t fh = 0, rh = 0, bits = 0;
     hash_steps<L, T, LA, W2, P4, 0>(src, W, A, EI, EO, fh, rh, caps, raw, bits, bound, np);
+    asm volatile("; S2K_MARK hash_end la=%0" ::"i"(LA));
 }
 
 // Same loop for a run-time l (1 .. 64; only l values without a static instantiation come here), unrolled like the static one.  The
@@ -1898,7 +1904,16 @@ __global__ __launch_bounds__(64 * tw<HPC>(), waves_per_simd<HPC>()) void tile_mi
         if (tn < n_tiles) {
             bposn = read_off[brin <= n_reads ? brin : n_reads];
             rs0n = read_off[(uint64_t)r0n + vzero];
+            // Through a GLOBAL pointer: `bases` is opaque to the compiler (see the top of the loop), so bases[i] is a flat_load, which counts in vmcnt
+            // AND lgkmcnt.  While one is in flight -- this one is, until after the hash loop -- the compiler takes lgkmcnt for out of order and turns
+            // every wait for an LDS read of the tile into lgkmcnt(0): the seed look-ahead of the hash loop was drained once per group.
+            // (S2K_PREVB_FLAT=1 builds rounds 1-9's flat_load again: tests/test_hash_loop_waits.py shows tools/isa/check_lgkmcnt.py the drained loop with it)
+#if S2K_PREVB_FLAT
             prevbn = (uint32_t)bases[tn * (uint64_t)TILE_BASES - 1 + vzero]; // tn > 0
+#else
+            typedef const __attribute__((address_space(1))) uint8_t *glb_cu8;
+            prevbn = (uint32_t)((glb_cu8)bases)[tn * (uint64_t)TILE_BASES - 1 + vzero]; // tn > 0
+#endif
             if (tnn < n_tiles) {
                 r0nn = cold_args().tile_read0[tnn + vzero];
                 r1nn = cold_args().tile_read0[tnn + 1 + vzero];
