@@ -421,6 +421,52 @@ s2k_status s2k_graph_induced(s2k_ctx *ctx, const uint64_t *d_keys, const uint32_
                              const uint8_t *d_remove, uint64_t n_unitigs, uint32_t *d_new_id, uint64_t *d_keys_out, uint32_t *d_counts_out,
                              uint64_t node_capacity, uint64_t *d_edge_keys_out, uint32_t *d_edge_counts_out, uint64_t edge_capacity,
                              uint64_t *n_nodes_out, uint64_t *n_edges_out);
+/* ---- bubbles that are not simple: bounded superbubbles popped on the unitig graph ---------------------------------
+ * Input and notation: the compacted graph of s2k_graph_simplify_mask above (the CSR over the 2 T oriented unitigs, len[t], cnt[t],
+ * succ, pred, in, out).
+ * Source: an oriented unitig S with out(S) >= 2.
+ * Traversal from S, a bounded Kahn walk (the shape of miniasm's asg_bub_pop1).  A list of discovered oriented unitigs is kept in
+ * slots, in order of first discovery; S is in slot 0.  An entry W holds r, the in-edges of W not yet seen (it starts at in(W); S
+ * starts at 0 whatever in(S) is); best, the largest sum of cnt over the interior unitigs of a path from S that reaches W, W itself not
+ * included (sums are taken modulo 2^64); and bp, the predecessor that gave best, on equal sums the smaller oriented id.  An entry is
+ * ready when r == 0 and it has not been expanded.  Repeat: expand the ready entry in the lowest slot, V: walk succ(V) in row order
+ * with sum = best[V] + cnt[V] (best[S] + 0 for V == S), and for each W: a new W takes the next slot with r = in(W) - 1, best = sum,
+ * bp = V; a W already in the list gets r -= 1 and, when sum > best[W] or (sum == best[W] and V < bp[W]), best = sum and bp = V.
+ * Failure -- S has no bubble -- when: the expanded entry has out == 0 (a dead end inside); W >> 1 == S >> 1 (a cycle, or a hairpin
+ * back); W ^ 1 is in the list (an inversion); W is new and the list already holds max_nodes + 2 entries; no entry is ready (some
+ * entry still has r > 0: an in-edge from outside the list, or a cycle inside); an edge arrives at an entry whose r is already 0
+ * (in(W) == 0 for a new W included: only a graph that is not twin-symmetric has such an edge).
+ * Success: the first time that, after an expansion, exactly one entry is ready and every other entry is expanded; that entry is
+ * the sink T, and it is not expanded.  The interior is the list without S and T.  The bubble exists iff the interior is not empty
+ * (then 1 <= |interior| <= max_nodes by the bound on the list) and the sum of len over the interior is <= max_bubble (members, like
+ * max_tip).  The kept path is T, bp[T], bp[bp[T]], ... back to S; the removable set is the interior unitigs not on it.  A bubble
+ * whose removable set is empty (a direct edge S -> T beside one detour, say) does nothing and claims nothing.
+ * Claims: two bubbles may share interior unitigs (a bubble and its twin seen from T ^ 1, a bubble inside another, bubbles that
+ * overlap).  Every bubble with a non-empty removable set claims each of its interior unitigs t (the unitig, not the oriented
+ * unitig): owner[t] = min(owner[t], S), S the oriented id of its source.  A bubble is applied iff owner[t] == S for its whole
+ * interior; the others wait for a later round.  The smallest claiming source owns everything it claimed, so a round that finds a
+ * bubble applies one and removes a unitig; a minimum does not depend on the order of the claims, so the outputs are a function of the
+ * input.
+ * Removal: unitig t is removed iff it is in the removable set of an applied bubble.
+ * Invariants: a kept oriented unitig with out >= 1 keeps a successor (no new dead end); the kept graph is twin-symmetric (removal
+ * is by unitig); the interior of an applied bubble has no edge to or from anything outside the bubble (an in-edge from outside keeps
+ * its target from becoming ready, an out-edge puts its target into the list).
+ *
+ * s2k_graph_bubble_mask: d_remove[t] (one byte per unitig, 0 / 1; NULL: the totals only), *n_sources = the oriented unitigs with
+ * out >= 2, *n_found = the sources whose bubble has a non-empty removable set, *n_applied = those of them that were applied,
+ * *n_removed = the bytes set.  max_nodes from 1 to S2K_BUBBLE_MAX_NODES (0 or a larger value: S2K_ERR_INVALID_ARG, decided on the host);
+ * max_bubble == 0 finds nothing.  One wave per source, a lane per list slot, at most S2K_BUBBLE_WAVES waves in a bounded grid; a row
+ * is walked entry by entry (a hub is slow, never wrong: it fails once the list is full).  The traversal runs twice, for the claims
+ * and again to apply.  Checked on the device before anything is written, as for s2k_graph_simplify_mask and with the same refusals
+ * (n_unitigs >= 2^31; n_unitigs == 0 needs n_edges == 0 and reads nothing; d_dst may be NULL when n_edges == 0); twin symmetry is
+ * trusted, and a graph without it gets an answer by the rules above, not a fault.  The totals are integer sums: bit-identical from
+ * call to call.  Workspace (the context's grow-only count workspace): 14.4 B per unitig (the sources, their found bytes, owner, the
+ * compaction's masks).  Runs on the context's stream; returns when the outputs are written. */
+#define S2K_BUBBLE_MAX_NODES 62u
+#define S2K_BUBBLE_WAVES 8192u
+s2k_status s2k_graph_bubble_mask(s2k_ctx *ctx, const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs,
+                                 const uint64_t *d_uni_off, const uint64_t *d_uni_count, uint32_t max_nodes, uint32_t max_bubble,
+                                 uint8_t *d_remove, uint64_t *n_sources, uint64_t *n_found, uint64_t *n_applied, uint64_t *n_removed);
 /* ---- base-space sequences of the nodes and unitigs -----------------------------------------------------------
  * What rust-mdbg keeps per solid k-min-mer: the bases of one occurrence and two shifts; a unitig's sequence is each member's first
  * `shift` bases, then the whole last member.  Inputs per batch: what s2k_extract_device wrote WITH S2K_FLAG_WANT_MINIMIZERS (km_off,

@@ -178,6 +178,19 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return t;
     }
+    // s2k_graph_bubble_mask: one round of bounded superbubble popping on the same unitig graph (the rule is in s2k.h): an interior of at
+    // most max_nodes unitigs (1 .. S2K_BUBBLE_MAX_NODES) and max_bubble members; d_remove (one byte per unitig) may be nullptr: the totals only.
+    struct BubbleTotals {
+        uint64_t sources, found, applied, removed;
+    };
+    BubbleTotals graph_bubble_mask(const uint64_t *d_row_off, const uint32_t *d_dst, uint64_t n_edges, uint64_t n_unitigs, const uint64_t *d_uni_off,
+                                   const uint64_t *d_uni_count, uint32_t max_nodes, uint32_t max_bubble, uint8_t *d_remove) {
+        BubbleTotals t{};
+        s2k_status st = s2k_graph_bubble_mask(ctx_, d_row_off, d_dst, n_edges, n_unitigs, d_uni_off, d_uni_count, max_nodes, max_bubble, d_remove,
+                                              &t.sources, &t.found, &t.applied, &t.removed);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return t;
+    }
     // s2k_graph_induced: the subgraph of the kept nodes.  Kept = d_node_keep[i] != 0, or (d_node_keep nullptr) !d_remove[d_node_unitig[i]].
     // Every output may be nullptr (all: the sizes only).  Returns {nodes, edges} kept; throws on S2K_ERR_CAPACITY too (nothing written).
     struct InducedSizes {

@@ -22,7 +22,7 @@ import os  # noqa: F401
 
 import numpy as np  # noqa: F401
 
-from ._abi import (ABI_SYMBOLS, ABI_VERSION, ALIGN_BAD_PATH, ALIGN_MAX_EDITS, ALIGN_OVER, ALIGN_WAVES, CIGAR_CHARS, CIGAR_D, CIGAR_EQ, CIGAR_I,  # noqa: F401
+from ._abi import (ABI_SYMBOLS, ABI_VERSION, ALIGN_BAD_PATH, ALIGN_MAX_EDITS, ALIGN_OVER, ALIGN_WAVES, BUBBLE_MAX_NODES, BUBBLE_WAVES, CIGAR_CHARS, CIGAR_D, CIGAR_EQ, CIGAR_I,  # noqa: F401
                    CIGAR_X, CONSENSUS_LONG_STATS, CONSENSUS_STATS, CONSENSUS_STATS_WORDS, COUNT_SORTED, FLAG_FORCE_SERIAL, FLAG_LEGACY_PATH, FLAG_NO_PACK2, FLAG_WANT_MINIMIZERS,
                    HPC_RLE_ALPHABET, LIB_PATH, LONG_INS_MAX, LONG_INS_MIN, LONG_INS_POS_BITS, NO_COPY, NO_EDGE, NO_PARTNER, NO_STEP, PILEUP_MAX_SHIFT, PILEUP_PLANES, PILEUP_STATS, PILEUP_STATS_WORDS,
                    PROTOTYPES, SEGMENT_LEN, SEGMENT_MIN_LEN, SEGMENT_STATS, SEGMENT_STATS_WORDS, STEP_LINKED, WALK_CIRCULAR, AlignOut, Counts, DeviceOut,

@@ -41,6 +41,8 @@ ALIGN_OVER = 1  # s2k_align_out.flags: the distance exceeds max_edits
 ALIGN_BAD_PATH = 2  # WalkAlignments.flags: s2k_walks_targets called the walk's path bad; it was not aligned
 ALIGN_MAX_EDITS = 255  # s2k_align_pairs: the largest max_edits
 ALIGN_WAVES = 2048  # s2k_align_pairs: the waves of its persistent grid
+BUBBLE_MAX_NODES = 62  # s2k_graph_bubble_mask: the largest max_nodes
+BUBBLE_WAVES = 8192  # s2k_graph_bubble_mask: the waves of its bounded grid
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # s2k_align_out.ops: len << 4 | op, the BAM codes
 CIGAR_CHARS = {CIGAR_I: "I", CIGAR_D: "D", CIGAR_EQ: "=", CIGAR_X: "X"}
 PILEUP_MAX_SHIFT = 64  # s2k_walks_pileup: the largest max_shift
@@ -179,6 +181,7 @@ PROTOTYPES = {
     "s2k_graph_unitig_edges": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _n64]),
     "s2k_graph_unitigs_last_steps": (None, [_P(C.c_double), _P(_u32)]),
     "s2k_graph_simplify_mask": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u32, _u32, _vp, _n64, _n64, _n64]),
+    "s2k_graph_bubble_mask": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u32, _u32, _vp, _n64, _n64, _n64, _n64]),
     "s2k_graph_induced": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _n64, _n64]),
     "s2k_table_representatives": (_int, [_vp, _u64, _P(DeviceOut), _u64, _vp]),
     "s2k_table_node_sequences": (_int, [_vp, _u64, _P(DeviceOut), _u32, _vp, _vp, _u64, _vp, _P(NodeSeqs), _u64, _n64]),

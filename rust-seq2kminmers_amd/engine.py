@@ -282,6 +282,20 @@ class Engine(_Handle):
                   int(max_bubble), _p(remove), C.byref(nt), C.byref(nb), C.byref(nr))
         return {"remove": remove[:t], "n_tips": int(nt.value), "n_bubbles": int(nb.value), "n_removed": int(nr.value)}
 
+    def graph_bubble_mask(self, unitig_graph, max_nodes, max_bubble):
+        """One round of bounded superbubble popping (s2k_graph_bubble_mask; the rule is in include/s2k.h) on a UnitigGraph: a bubble's
+        interior holds at most max_nodes unitigs (1 .. BUBBLE_MAX_NODES) and at most max_bubble members in all -> dict: remove (uint8 GPU
+        tensor, one byte per unitig) and the ints n_sources (oriented unitigs with out >= 2), n_found (bubbles with something to
+        remove), n_applied (those that owned their whole interior), n_removed."""
+        g = _graph_arg(unitig_graph, ("csr", "uni_off", "counts"),
+                       "graph_bubble_mask wants a UnitigGraph: 64-bit counts, one per unitig, and the CSR over its oriented unitigs")
+        t, ne, dev = g.t, g.ne, g.row_off.device
+        remove = torch.zeros(max(t, 1), dtype=torch.uint8, device=dev)
+        ns, nf, na, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._run(self.lib.s2k_graph_bubble_mask, dev, self.ctx, _p(g.row_off), _p(g.dst, ne), ne, t, _p(g.uni_off), _p(g.counts, t), int(max_nodes),
+                  int(max_bubble), _p(remove), C.byref(ns), C.byref(nf), C.byref(na), C.byref(nr))
+        return {"remove": remove[:t], "n_sources": int(ns.value), "n_found": int(nf.value), "n_applied": int(na.value), "n_removed": int(nr.value)}
+
     def graph_induced(self, graph, node_keep=None, node_unitig=None, remove=None):
         """The subgraph of a KminmerGraph that its kept nodes induce (s2k_graph_induced).  Kept: node_keep (uint8 GPU tensor, one byte per
         node, non-zero = kept), or, without it, the nodes whose unitig is not removed: node_unitig (UnitigGraph.node_unitig) and remove

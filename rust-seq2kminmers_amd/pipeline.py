@@ -337,13 +337,18 @@ class KminmerGraph:
         return ug
 
 
-    def simplify(self, engine, max_tip, max_bubble, max_rounds=16):
+    def simplify(self, engine, max_tip, max_bubble, max_rounds=16, bubble_nodes=0):
         """Clips tips of at most max_tip members and pops simple bubbles whose removed branch holds at most max_bubble members (the rules
         are in include/s2k.h; 0 switches one off), round by round on the device -- unitigs, Engine.graph_simplify_mask,
         Engine.graph_induced, Engine.graph_adjacency -- until a round removes nothing or max_rounds rounds have run.
+        bubble_nodes > 0: a round in which those two rules remove nothing runs Engine.graph_bubble_mask(bubble_nodes, max_bubble) on the
+        same unitig graph -- bubbles that are not simple, an interior of at most bubble_nodes unitigs and max_bubble members -- and
+        applies its mask instead; the loop then ends when both remove nothing.  The two masks are never applied in one round: their
+        orders differ (mean count there, summed count here), and their union could remove both branches of one bubble.
         -> (graph, node_map, stats): a new KminmerGraph over the kept nodes (self is untouched); node_map, an int32 GPU tensor with the
         final id of every node of self, -1 for a removed one; stats, one dict per round (nodes and unitigs the round started from, tips,
-        bubbles and unitigs it removed), the last of which removed nothing when a fixed point was reached."""
+        bubbles and unitigs it removed; a round that ran the bubble mask also sources, found and applied, and its removed is that
+        mask's), the last of which removed nothing when a fixed point was reached."""
         g = KminmerGraph(self.keys, self.counts, self.edge_keys, self.edge_counts, self.row_off, self.dst)
         node_map = torch.arange(self.n_nodes, dtype=torch.int32, device=self.keys.device)
         stats = []
@@ -351,6 +356,9 @@ class KminmerGraph:
             ug = g.unitigs(engine)
             m = engine.graph_simplify_mask(ug, max_tip, max_bubble)
             stats.append({"nodes": g.n_nodes, "unitigs": ug.n_unitigs, "tips": m["n_tips"], "bubbles": m["n_bubbles"], "removed": m["n_removed"]})
+            if m["n_removed"] == 0 and bubble_nodes > 0:
+                m = engine.graph_bubble_mask(ug, bubble_nodes, max_bubble)
+                stats[-1].update(sources=m["n_sources"], found=m["n_found"], applied=m["n_applied"], removed=m["n_removed"])
             if m["n_removed"] == 0:
                 break
             ind = engine.graph_induced(g, node_unitig=ug.node_unitig, remove=m["remove"])

@@ -78,6 +78,53 @@ def rounds_leg(eng, pkg, torch, dev, graph, max_tip, max_bubble, max_rounds, rep
     return {"rounds": out, "fixed_point": out[-1]["removed"] == 0, "totals": tot}
 
 
+def genome_graph(eng, pkg, torch, dev, rate):
+    """the genome-sampled set with substitutions -> (KminmerGraph, substitutions made)"""
+    bases, read_off, n_reads = genome_reads(torch, dev, 50_000_000, 10_000, 30, 7)
+    n_bases = n_reads * 10_000
+    n_subst = inject_substitutions(torch, dev, bases, n_bases, rate, 11)
+    cap = int(n_bases * 0.03)
+    out = {"km_off": torch.empty(n_reads + 1, dtype=torch.int64, device=dev), "hash": torch.empty(cap, dtype=torch.int64, device=dev),
+           "rev": torch.empty(cap, dtype=torch.uint8, device=dev)}
+    o = pkg.DeviceOut()
+    o.km_capacity = cap
+    o.km_off, o.hash, o.rev = (out[x].data_ptr() for x in ("km_off", "hash", "rev"))
+    torch.cuda.synchronize(dev)
+    eng.extract_device(bases.data_ptr(), read_off.data_ptr(), n_reads, n_bases, 31, 10, 0.01, int(pkg.HashMode.Regular), o)
+    del bases
+    graph = pkg.KminmerGraph.build(eng, [out], min_count=2)
+    del out
+    torch.cuda.empty_cache()
+    return graph, n_subst
+
+
+def config1_graph(eng, pkg, torch, dev):
+    """configs[1] against a table of every second key -> KminmerGraph"""
+    items, n_reads, n = config1(eng, torch, dev, pkg)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    nd, nk = eng.count_device_ex(items["hash"].data_ptr(), n, 1, True, keys.data_ptr(), counts.data_ptr(), n)
+    half_k, half_c = keys[:nk:2].contiguous(), counts[:nk:2].contiguous()
+    del keys, counts
+    half = pkg.CountTable(eng, half_k, half_c)
+    e = half.edges(items, n_reads, 1)
+    half.close()
+    del items
+    ne = e.numel()
+    dk = torch.empty(ne, dtype=torch.int64, device=dev)
+    dc = torch.empty(ne, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    _, n_distinct = eng.count_device_ex(e.data_ptr(), ne, 1, True, dk.data_ptr(), dc.data_ptr(), ne)
+    del e
+    ek, ec = dk[:n_distinct].clone(), dc[:n_distinct].clone()
+    del dk, dc
+    row_off, dst = eng.graph_adjacency(ek, half_k.numel())
+    graph = pkg.KminmerGraph(half_k, half_c, ek, ec, row_off, dst)
+    torch.cuda.empty_cache()
+    return graph
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -95,21 +142,7 @@ def main():
     eng.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     res = {"tool": "simplify_rate", "reps": a.reps, "k": K, "max_tip": 2 * K, "max_bubble": 4 * K}
 
-    bases, read_off, n_reads = genome_reads(torch, dev, 50_000_000, 10_000, 30, 7)
-    n_bases = n_reads * 10_000
-    n_subst = inject_substitutions(torch, dev, bases, n_bases, a.rate, 11)
-    cap = int(n_bases * 0.03)
-    out = {"km_off": torch.empty(n_reads + 1, dtype=torch.int64, device=dev), "hash": torch.empty(cap, dtype=torch.int64, device=dev),
-           "rev": torch.empty(cap, dtype=torch.uint8, device=dev)}
-    o = pkg.DeviceOut()
-    o.km_capacity = cap
-    o.km_off, o.hash, o.rev = (out[x].data_ptr() for x in ("km_off", "hash", "rev"))
-    torch.cuda.synchronize(dev)
-    eng.extract_device(bases.data_ptr(), read_off.data_ptr(), n_reads, n_bases, 31, 10, 0.01, int(pkg.HashMode.Regular), o)
-    del bases
-    graph = pkg.KminmerGraph.build(eng, [out], min_count=2)
-    del out
-    torch.cuda.empty_cache()
+    graph, n_subst = genome_graph(eng, pkg, torch, dev, a.rate)
     gen = rounds_leg(eng, pkg, torch, dev, graph, 2 * K, 4 * K, a.max_rounds, a.reps, a.warmup)
     gen.update(substitution_rate=a.rate, substitutions=n_subst)
     res["genome"] = gen
@@ -118,28 +151,7 @@ def main():
     torch.cuda.empty_cache()
 
     if not a.skip_config1:
-        items, n_reads, n = config1(eng, torch, dev, pkg)
-        keys = torch.empty(n, dtype=torch.int64, device=dev)
-        counts = torch.empty(n, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)
-        nd, nk = eng.count_device_ex(items["hash"].data_ptr(), n, 1, True, keys.data_ptr(), counts.data_ptr(), n)
-        half_k, half_c = keys[:nk:2].contiguous(), counts[:nk:2].contiguous()
-        del keys, counts
-        half = pkg.CountTable(eng, half_k, half_c)
-        e = half.edges(items, n_reads, 1)
-        half.close()
-        del items
-        ne = e.numel()
-        dk = torch.empty(ne, dtype=torch.int64, device=dev)
-        dc = torch.empty(ne, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)
-        _, n_distinct = eng.count_device_ex(e.data_ptr(), ne, 1, True, dk.data_ptr(), dc.data_ptr(), ne)
-        del e
-        ek, ec = dk[:n_distinct].clone(), dc[:n_distinct].clone()
-        del dk, dc
-        row_off, dst = eng.graph_adjacency(ek, half_k.numel())
-        graph = pkg.KminmerGraph(half_k, half_c, ek, ec, row_off, dst)
-        torch.cuda.empty_cache()
+        graph = config1_graph(eng, pkg, torch, dev)
         res["config1"] = rounds_leg(eng, pkg, torch, dev, graph, 2 * K, 4 * K, min(a.max_rounds, 4), a.reps, a.warmup)
     eng.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
