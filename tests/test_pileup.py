@@ -599,6 +599,19 @@ def query_pool(queries, seed=0):
     return np.frombuffer(bytes(buf), dtype=np.uint8), np.array(begin, dtype=np.uint64)
 
 
+def pileup_args(P, n_walks, n_steps_all, n_bases, T, nq, n_ops_total, max_shift, pile, stats):
+    """the arguments of s2k_walks_pileup behind the context, in the prototype's order (s2k_walks_pileup_ex takes four more); P: name ->
+    device pointer"""
+    return (n_walks, P("first_step"), P("n_steps"), P("path_start"), P("path_end"), P("flags"), P("unitig"), n_steps_all, P("out_off"), P("out"), n_bases,
+            P("overlap"), T, P("query"), nq, P("q_begin"), P("aflags"), P("ops_off"), P("n_ops"), P("ops"), n_ops_total, max_shift, pile, stats)
+
+
+def consensus_args(pile, d_off, d_out, n_bases, d_ov, T, min_cov, R, capacity, n_new, stats):
+    """the arguments of s2k_pileup_consensus behind the context, in the prototype's order (s2k_pileup_consensus_ex takes three more); R:
+    output name -> device pointer or None"""
+    return (pile, d_off, d_out, n_bases, d_ov, T, min_cov, R("out_off"), R("out"), capacity, R("pos_map"), R("overlap"), n_new, stats)
+
+
 def raw_pileup(eng, walks, su, strings, overlap, queries, flags, runs, max_shift=MAX_SHIFT, pile=None, ctx=True, null=(), stats=True, **over):
     """s2k_walks_pileup through ctypes, guards behind every plane -> (status, stats list, host planes with guards).  over: any input array
     replaced by name; n_walks, n_steps_all, T, n_bases, nq, n_ops_total given"""
@@ -625,10 +638,8 @@ def raw_pileup(eng, walks, su, strings, overlap, queries, flags, runs, max_shift
     st = (ctypes.c_uint64 * pkg.PILEUP_STATS_WORDS)(*([777] * pkg.PILEUP_STATS_WORDS))
     P = lambda k: _ptr(dv[k], k in null)  # noqa: E731
     torch.cuda.synchronize()
-    s = eng.lib.s2k_walks_pileup(eng.ctx if ctx else None, nw, P("first_step"), P("n_steps"), P("path_start"), P("path_end"), P("flags"), P("unitig"), ns,
-                                 P("out_off"), P("out"), nb, P("overlap"), T, P("query"), over.get("nq", len(pool)), P("q_begin"), P("aflags"), P("ops_off"),
-                                 P("n_ops"), P("ops"), over.get("n_ops_total", len(ops)), max_shift, None if "pile" in null else ctypes.byref(p),
-                                 st if stats else None)
+    s = eng.lib.s2k_walks_pileup(eng.ctx if ctx else None, *pileup_args(P, nw, ns, nb, T, over.get("nq", len(pool)), over.get("n_ops_total", len(ops)), max_shift,
+                                                                        None if "pile" in null else ctypes.byref(p), st if stats else None))
     torch.cuda.synchronize()
     return s, list(st), {f: _host(t, np.uint32) for f, t in zip(PLANES, planes)}
 
@@ -1028,9 +1039,9 @@ def raw_consensus(eng, pile, strings, overlap, min_cov=3, capacity=None, want=("
     st = (ctypes.c_uint64 * pkg.CONSENSUS_STATS_WORDS)(*([777] * pkg.CONSENSUS_STATS_WORDS))
     R = lambda f: _ptr(res[f]) if f in res else None  # noqa: E731
     torch.cuda.synchronize()
-    s = eng.lib.s2k_pileup_consensus(eng.ctx if ctx else None, None if "pile" in null else ctypes.byref(p), _ptr(d_off, "out_off" in null), _ptr(d_out, "out" in null),
-                                     over.get("n_bases", n), _ptr(d_ov, "overlap" in null), over.get("T", T), min_cov, R("out_off"), R("out"), cap, R("pos_map"),
-                                     R("overlap"), ctypes.byref(nn), st if stats else None)
+    s = eng.lib.s2k_pileup_consensus(eng.ctx if ctx else None, *consensus_args(None if "pile" in null else ctypes.byref(p), _ptr(d_off, "out_off" in null),
+                                                                               _ptr(d_out, "out" in null), over.get("n_bases", n), _ptr(d_ov, "overlap" in null),
+                                                                               over.get("T", T), min_cov, R, cap, ctypes.byref(nn), st if stats else None))
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(before, planes)), "the pile is only read"
     return s, nn.value, list(st), {f: _host(x, C_OUT[f]) for f, x in res.items()}
