@@ -586,6 +586,8 @@ s2k_status enqueue(s2k_ctx *ctx) {
     if (tm) S2K_TRY(hipEventRecord(ctx->ev[0], sp), "event");
     S2K_TRY(hipMemsetAsync(ctx->d_counts, 0, CTRL_CURSORS_OFF + (size_t)CURSOR_WORDS * (use_desc ? n_chunks : 1) * sizeof(uint64_t), sp),
             "memset counters, xor shards, cursors");
+    // (tests, S2K_POISON_WS: the call's workspace is never cleared either -- tile words, TileMeta, states and records must all be written before they are read)
+    if (ctx->poison_ws) S2K_TRY(hipMemsetAsync(ctx->ws.p, ctx->poison_byte, a.off, sp), "workspace poison");
     // P -> sk after the minimizer work of a whole call (serial and legacy paths)
     auto hand_over = [&]() -> s2k_status {
         S2K_TRY(hipEventRecord(ctx->tiles_done, sp), "event");
@@ -687,6 +689,9 @@ s2k_status enqueue(s2k_ctx *ctx) {
                 static const bool nokm = getenv("S2K_DEBUG_NOKM") != nullptr;
                 if (nokm) continue;
 #endif
+                // Hpc family: the chunk's tile words are provisional until this kernel has counted the hits of every read segment: on sk, beside the next
+                // chunk's minimizer kernel.  (The Regular family's tiled kernel writes final words: nothing runs beside it, dense_phase has the numbers.)
+                if (c.sem.hpc) S2K_TRY(launch_desc_words(T0, T1, dz, rec, ctx->d_counts, sk), "tile word kernel");
                 S2K_TRY(launch_desc_scan(T0, T1, dz, d_scan, ctx->d_counts, sk), "tile word scan");
                 // (staged stores for the last chunk's k-min-mer kernel when nothing runs beside it: +0.3 % for an unchained call,
                 // profiles/r06_chunks_prio_sweep.txt.  A chained Hpc call's runs beside the next call's first minimizer kernel; the Regular family's

@@ -11,6 +11,7 @@
 //     before it.  Read positions: j = (tile start + offset) - (start of the read segment), from the tile's own list of read
 //     starts; km_off (and mn_off) of the reads that start in the tile are written here too.  No per-read table is read.
 #include "s2k_dev.h"
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 
@@ -75,6 +76,84 @@ __device__ inline AggF wave_scan_agg(AggF a, int lane, uint32_t K1) {
 // (s2k_api.hip: finish()), so (3) no output of a call in which a flag was raised is ever consumed -- kernels of one chunk that disagree about
 // scan_off leave garbage states and partly written outputs, which the re-run overwrites.
 __device__ inline bool scan_off(const Counts *counts) { return counts->need_legacy || counts->need_runs || counts->bad_input || counts->pool_overflow; }
+
+// ---- the tiles' final words ------------------------------------------------------------------------------------------------
+// ONE LANE per tile, Hpc family (the Regular family's tiled kernel writes final words itself: its k-min-mer stage runs behind it, not beside it).
+// The tiled kernel leaves a provisional word (agg_provisional_hi, s2k_dev.h: N, nb, dep, "a read starts at the tile's end", the first two read starts), the
+// tile's records in ascending order of their 14-bit tile offset, and the raw offsets rs16[1 .. nb] of the read starts inside the tile.  A hit
+// lies before read segment s iff its offset is below rs16[s] (dense_phase, s2k_tile_impl.h, has the argument for hash space vs raw space), so
+// segstart[s] is a lower bound over the records, and the rest is the arithmetic the tiled kernel used to spend a wave on:
+//   mine[s] = segstart[s+1] - segstart[s] (the last segment: up to N),   m_f = mine[0],   m_l = mine[nb],
+//   C = sum of max(mine[s] - (k-1), 0) over the segments that start a read -- all but the first one when a read continues into the tile (dep):
+//       that one's windows depend on p --,   q = 0 when a read starts at the tile's end, else min(m_l, k-1),   pass = dep, no read start, none at the end.
+// Tiles with N = 0 and dropped tiles (N = 0 as well) get their final word like any other: the scan reads every word of its range.  A word
+// without the mark is left alone: the identity of a tile that was not worked on (a flagged call), or a word that is final already.
+// Traffic is what this kernel costs (per tile: its word, one or two lines of its records, 8 bytes of its TileMeta): the word itself carries N, nb and
+// the first two read starts, so TileMeta is only read for a third start and for records in the overflow region; the search starts where a uniform
+// spread of the hits puts the boundary and gallops from there, so its probes stay within a cache line or two of the records as a rule.
+constexpr int DW_BLOCK = 256;
+// first index in [lo, hi) whose record's tile offset is >= lim (records ascend), looked for around `guess`
+__device__ inline uint32_t dw_lower_bound(const uint32_t *__restrict__ pj, uint32_t lo, uint32_t hi, uint32_t lim, uint32_t guess) {
+    if (lo >= hi) return lo;
+    const uint32_t g = guess < lo ? lo : (guess >= hi ? hi - 1u : guess);
+    uint32_t step = 1;
+    if ((pj[g] & 0x3FFFu) < lim) { // everything up to g lies below: gallop upwards
+        lo = g + 1u;
+        while (lo < hi) {
+            const uint32_t p = hi - lo > step ? lo + step - 1u : hi - 1u;
+            if ((pj[p] & 0x3FFFu) < lim) lo = p + 1u, step <<= 1;
+            else { hi = p; break; }
+        }
+    } else { // g and everything behind it does not: downwards
+        hi = g;
+        while (lo < hi) {
+            const uint32_t p = hi - lo > step ? hi - step : lo;
+            if ((pj[p] & 0x3FFFu) >= lim) hi = p, step <<= 1;
+            else { lo = p + 1u; break; }
+        }
+    }
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((pj[mid] & 0x3FFFu) < lim) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(DW_BLOCK) void desc_word_kernel(uint64_t tile_begin, uint64_t tile_end, Desc dz, Records rec, const Counts *__restrict__ counts) {
+    if (scan_off(counts)) return;
+    const uint32_t K1 = dz.k - 1;
+    for (uint64_t t = tile_begin + (uint64_t)blockIdx.x * DW_BLOCK + threadIdx.x; t < tile_end; t += (uint64_t)gridDim.x * DW_BLOCK) {
+        const unsigned long long w = dz.agg[t];
+        const uint32_t hi32 = (uint32_t)(w >> 32);
+        if (!(hi32 & AGGP_MARK)) continue;
+        const uint32_t N = hi32 & 0x3FFFu, nb = (hi32 >> 14) & (uint32_t)(META_SEGS - 1);
+        const bool dep = (hi32 & AGGP_DEP) != 0, ext_at_end = (hi32 & AGGP_EXT_AT_END) != 0;
+        TileMeta *m = &dz.meta[t];
+        // (N <= the records the tile owns: in its slab, or -- more than a slab holds -- in the piece of the overflow region TileMeta names)
+        const uint32_t *pj = rec.j + (nb && N ? ((uint64_t)N <= rec.slab_cap ? t * rec.slab_cap : m->rec_base) : 0ull);
+        uint32_t prev = 0, C = 0, m_first = 0;
+        unsigned long long seg4 = 0; // segstart[0 .. 3], stored as one word
+        for (uint32_t s = 1; s <= nb; s++) {
+            const uint32_t lim = s == 1 ? (uint32_t)w & 0xFFFFu : (s == 2 ? (uint32_t)(w >> 16) & 0xFFFFu : m->rs16[s]);
+            // rs16 ascends: the records before segment s - 1 are before segment s too
+            const uint32_t lo = dw_lower_bound(pj, prev, N, lim, (lim * N) / (uint32_t)TILE_BASES);
+            if (s < 4u) seg4 |= (unsigned long long)lo << (16u * s);
+            else m->segstart[s] = (uint16_t)lo;
+            const uint32_t mine = lo - prev; // segment s - 1
+            if (s == 1) m_first = mine;
+            if (!(s == 1 && dep) && mine > K1) C += mine - K1;
+            prev = lo;
+        }
+        *reinterpret_cast<unsigned long long *>(m->segstart) = seg4; // (entries beyond nb: nobody reads them)
+        const uint32_t m_last = N - prev; // segment nb
+        if (nb == 0) m_first = m_last;
+        if (!(nb == 0 && dep) && m_last > K1) C += m_last - K1;
+        const bool pass = dep && nb == 0 && !ext_at_end;
+        const uint32_t q_out = ext_at_end ? 0u : (m_last < K1 ? m_last : K1);
+        dz.agg[t] = agg_pack(m_first, C, N, q_out, dep, pass);
+    }
+}
+static_assert(offsetof(TileMeta, segstart) % 8 == 0 && sizeof(TileMeta) % 8 == 0, "segstart[0 .. 3] are stored as one 64-bit word");
 
 // one wave per 64 entries of a level: what the 64 together do (coalesced loads, log-step scan)
 template <bool PACKED>
@@ -706,6 +785,15 @@ __global__ __launch_bounds__(64 * DK_WAVES, 8) void desc_kminmer_kernel(uint64_t
 size_t desc_scan_tmp_words(uint64_t n_tiles) {
     const uint64_t n1 = (n_tiles + 63) / 64, n2 = (n1 + 63) / 64;
     return 7 * n1 + 7 * n2 + 16;
+}
+
+hipError_t launch_desc_words(uint64_t tile_begin, uint64_t tile_end, Desc dz, Records rec, const Counts *counts, hipStream_t st) {
+    if (tile_end <= tile_begin) return hipSuccess;
+    if (dz.k == 0) return hipErrorInvalidValue;
+    const uint64_t blocks = (tile_end - tile_begin + DW_BLOCK - 1) / DW_BLOCK;
+    // (no LDS and a few registers: eight blocks per CU of 256 CUs hold every lane a chunk of two million tiles needs; more tiles take further trips)
+    hipLaunchKernelGGL(desc_word_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(DW_BLOCK), 0, st, tile_begin, tile_end, dz, rec, counts);
+    return hipGetLastError();
 }
 
 hipError_t launch_desc_scan(uint64_t tile_begin, uint64_t tile_end, Desc dz, unsigned long long *scan_tmp, const Counts *counts, hipStream_t st) {

@@ -171,6 +171,18 @@ __host__ __device__ inline AggF agg_unpack(unsigned long long w) {
     return a;
 }
 __host__ __device__ inline AggF agg_identity() { return AggF{0, 0, 0, 0, true, true}; }
+// Hpc family: what the tiled kernel itself leaves in a tile's word is PROVISIONAL, in a layout of its own: everything desc_word_kernel (s2k_desc.hip) needs to
+// count the hits of the tile's read segments from its records, so that a tile with at most two read starts inside (all but tiles of short reads)
+// costs that kernel no look at the tile's TileMeta:
+//   bits [0,16) rs16[1], [16,32) rs16[2]  (16-bit stores of the lanes that hold those read starts; not written, and not read, beyond nb),
+//   upper half (one 32-bit store): N [0,14) -- 0 for a tile that had to drop its records: the call is flagged and run again --, nb [14,19), dep bit 19,
+//   "a read starts exactly where the tile ends" (q = 0 then) bit 20, and in bit 31 (bit 63 of the word) the mark that tells the word from a final one
+//   and from the identity the array starts as, which a tile that was not worked on keeps (nothing to count there, and no TileMeta to count from).
+// The word kernel replaces it by the final word (agg_pack), in which bit 63 is never set.
+constexpr uint32_t AGGP_MARK = 1u << 31, AGGP_DEP = 1u << 19, AGGP_EXT_AT_END = 1u << 20;
+__host__ __device__ inline uint32_t agg_provisional_hi(uint32_t N, uint32_t nb, bool dep, bool ext_at_end) {
+    return N | (nb << 14) | (dep ? AGGP_DEP : 0u) | (ext_at_end ? AGGP_EXT_AT_END : 0u) | AGGP_MARK;
+}
 __host__ __device__ inline uint64_t agg_windows(const AggF &a, uint32_t p, uint32_t K1) {
     uint64_t v = a.C;
     if (a.dep && a.m_f + p > K1) v += a.m_f + p - K1;
@@ -201,12 +213,12 @@ __host__ __device__ inline AggF agg_then(const AggF &A, const AggF &B, uint32_t 
     return R;
 }
 constexpr int META_SEGS = 32; // read segments of a tile whose start is kept (NBL of s2k_tile_impl.h); tiles with more take the legacy path
-struct TileMeta {            // written by the tiled kernel, read by the k-min-mer kernel
+struct TileMeta {            // written by the tiled kernel (Hpc family: segstart by desc_word_kernel), read by the k-min-mer kernel
     unsigned long long rec_base; // the tile's first record in the pool (its slab, or a piece of the overflow region)
     unsigned long long rs0;      // stream position where read r0 (the one that holds the tile's first base) starts
     uint32_t r0;                 // index of that read
     uint16_t nb, nrd;            // read starts strictly inside the tile; reads that start in (t0, end of the tile]
-    uint16_t segstart[META_SEGS]; // minimizers of the tile before read segment s (s = 0 .. nb)
+    uint16_t segstart[META_SEGS]; // minimizers of the tile before read segment s (s = 0 .. nb): records whose tile offset is below rs16[s]
     uint16_t rs16[META_SEGS];     // read_off[r0 + s] - t0 for s = 1 .. nb
 };
 struct TileState { // written by the scan
@@ -301,6 +313,9 @@ hipError_t launch_tile_minimizers(const uint8_t *bases, const uint64_t *read_off
                                   uint64_t n_tiles, const uint32_t *tile_read0, Sem sem, uint32_t mode, Records rec,
                                   uint64_t *pool_cursor, uint64_t *tile_rec_off, uint32_t *tile_cnt, uint32_t *mn_cnt,
                                   Counts *counts, const Desc *desc, uint64_t tile_begin, hipStream_t st);
+// descriptor path, Hpc family, for the tiles [tile_begin, tile_end), behind their minimizer kernel and in front of the scan: one lane per tile counts the hits
+// of the tile's read segments from its records and turns the tile's provisional word into the final one (+ TileMeta::segstart)
+hipError_t launch_desc_words(uint64_t tile_begin, uint64_t tile_end, Desc dz, Records rec, const Counts *counts, hipStream_t st);
 // descriptor path, for the tiles [tile_begin, tile_end): (G, p) of every tile from the tile words -- starting from state[tile_begin]
 // (the totals a previous call for the tiles before left there; zeros for tile_begin == 0) and leaving the totals in state[tile_end] --
 // then the k-min-mers of those tiles

@@ -1066,6 +1066,10 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
     //     same read, src/nthash_hpc.rs:265-267).  The first read start at or after the tile end (or the
     //     end of the stream) is the one external boundary.
     constexpr int LISTCAP = listcap<HPC>();
+    // Descriptor path, Hpc family: the per-segment counts and the tile's final word are made LATER, by desc_word_kernel with one lane per tile, beside the
+    // next chunk's minimizer kernel (below).  The Regular family keeps them here: its k-min-mer stage runs behind this kernel, not beside it (the
+    // kernel leaves no LDS), so the word kernel's time would be added to the call, and measured it cost more than the tile kernel gained.
+    constexpr bool WORD_LATER = DESC && HPC;
     const uint32_t wclr = HPC ? (sem.keep_last ? l - 1 : l) : l - 1; // Hpc drops the last l-mer of a read (src/nthash_hpc.rs:265-267)
     // rcpTq = 65536 / (Tq / 16) + 1 for Tq / 16 in {7, 3, 5, 9, 1}: see div_tq (a division costs ~25 instructions per tile); chosen by the kernel together with Tq
     const uint32_t tql = __umul24(Tq, (uint32_t)lane); // first hash position of this lane
@@ -1216,9 +1220,14 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
                 }
                 chunk_prev = ((uint64_t)bcast((uint32_t)(bpos >> 32), 63) << 32) | bcast((uint32_t)bpos, 63);
             }
-            if (!many && internal && c0 + lane < (uint32_t)(NBL - 1)) { // remembered for the per-hit read lookup
-                S.hb[c0 + lane] = (int16_t)HB;
-                S.rs16[c0 + lane + 1] = (uint16_t)(bpos - t0);
+            if (!many && internal && c0 + lane < (uint32_t)(NBL - 1)) {
+                if constexpr (WORD_LATER) { // the tile's list of read starts, straight to its TileMeta: desc_word_kernel counts the hits of every segment from it
+                    d_meta[t].rs16[c0 + lane + 1] = (uint16_t)(bpos - t0);
+                    if (c0 + lane < 2u) reinterpret_cast<uint16_t *>(d_agg + t)[c0 + lane] = (uint16_t)(bpos - t0); // (the first two: in the provisional word as well, s2k_dev.h)
+                } else { // remembered for the per-segment counts below (and the legacy path's per-hit read lookup)
+                    S.hb[c0 + lane] = (int16_t)HB;
+                    S.rs16[c0 + lane + 1] = (uint16_t)(bpos - t0);
+                }
             }
             nb += (uint32_t)__popcll(__ballot(internal));
             if (em) {
@@ -1262,51 +1271,69 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
     // per-read minimizer counts, once per tile: read r0+i owns the hits in [HB[i-1], HB[i]) -- lane i keeps the count of
     // segment i (`mine`) and the number of hits before it (`segstart`)
     uint32_t mine = 0, segstart = 0;
-    if (!many) {
-        uint32_t below_prev = 0;
-        for (uint32_t i = 0; i <= nb; i++) { // wave-uniform trip count
-            uint32_t below = N;
-            if (i < nb) {
-                const int lim = S.hb[i] - (int)tql; // lane-local bits [0, lim) lie below boundary i
-                uint32_t c = 0;
+    if constexpr (!WORD_LATER) {
+        if (!many) {
+            uint32_t below_prev = 0;
+            for (uint32_t i = 0; i <= nb; i++) { // wave-uniform trip count
+                uint32_t below = N;
+                if (i < nb) {
+                    const int lim = S.hb[i] - (int)tql; // lane-local bits [0, lim) lie below boundary i
+                    uint32_t c = 0;
 #pragma unroll
-                for (int d = 0; d < 5; d++) {
-                    c += __popc(vm[d] & bits_below(lim - 32 * d));
+                    for (int d = 0; d < 5; d++) {
+                        c += __popc(vm[d] & bits_below(lim - 32 * d));
+                    }
+                    // lanes left of the boundary's lane count everything, lanes right of it nothing: the total is the
+                    // exclusive offset of that lane plus its own share -- one v_readlane instead of a wave scan
+                    const int hbi = S.hb[i];
+                    const int lb = hbi <= 0 ? 0 : ((uint32_t)hbi >= Tq * 64u ? 63 : (int)div_tq((uint32_t)hbi, rcpTq));
+                    below = bcast(myoff + c, lb);
                 }
-                // lanes left of the boundary's lane count everything, lanes right of it nothing: the total is the
-                // exclusive offset of that lane plus its own share -- one v_readlane instead of a wave scan
-                const int hbi = S.hb[i];
-                const int lb = hbi <= 0 ? 0 : ((uint32_t)hbi >= Tq * 64u ? 63 : (int)div_tq((uint32_t)hbi, rcpTq));
-                below = bcast(myoff + c, lb);
+                if ((uint32_t)lane == i) {
+                    mine = below - below_prev;
+                    segstart = below_prev;
+                }
+                below_prev = below;
             }
-            if ((uint32_t)lane == i) {
-                mine = below - below_prev;
-                segstart = below_prev;
-            }
-            below_prev = below;
+            if constexpr (!DESC)
+                if ((uint32_t)lane <= nb && mine) atomicAdd(&mn_cnt[r0 + lane], mine);
         }
-        if constexpr (!DESC)
-            if ((uint32_t)lane <= nb && mine) atomicAdd(&mn_cnt[r0 + lane], mine);
     }
     if constexpr (DESC) {
-        // ---- the tile's descriptor word and its read segments (see s2k_dev.h) ---------------------------------------------
+        // ---- the tile's descriptor word and its list of read starts (see s2k_dev.h); WORD_LATER: a PROVISIONAL word --------------
+        // What a tile does to (G, p) follows from the hits of each of its read segments.  Counting them is bookkeeping that is scalar
+        // per tile: here a whole wave does it for one tile (five masked popcounts, an LDS read, a division and a readlane per
+        // segment, then the window sums: 47 vector and 80 scalar instructions per Hpc tile), desc_word_kernel (s2k_desc.hip) does it
+        // with ONE LANE per tile, off this kernel's stream.  It needs nothing the tile does not leave in HBM anyway:
+        //   a hit belongs to the reads before boundary i iff its hash position is below HB[i].  Regular: hash positions ARE raw
+        //   offsets and HB[i] = rs16[i].  Hpc: HB[i] is the rank of the forced run head at raw offset rs16[i], a hit's position the
+        //   rank of the run head its l-mer starts at, and ranks ascend with raw offsets: rank < HB[i] iff raw offset < rs16[i].
+        //   Either way the test is "the record's 14-bit tile offset < rs16[i]", and the records are stored in ascending order, so
+        //   the hits before segment s are a lower bound over the tile's records.
+        // So a WORD_LATER tile only says how many records it has (0 when it had to drop them), how many read starts, whether a read
+        // continues into it and whether one starts exactly at its end; the word kernel turns that into the final word and TileMeta::segstart.
         if (many) { // more read starts than the lists hold (reads shorter than ~300 bases): the whole call takes the legacy path
             if (lane == 0) counts->need_legacy = 1;
             issue_next(0u, base);
             return 0;
         }
         const bool dep = !(t0 == 0 || rs0 == t0); // a read that began before the tile continues into it
-        const uint32_t m_first = bcast(mine, 0), m_last = bcast(mine, (int)nb);
-        uint32_t wfix = (uint32_t)lane <= nb && mine > K1 ? mine - K1 : 0u; // windows of a segment that starts a read in (or at the start of) the tile
-        if (lane == 0 && dep) wfix = 0;                                         // (the first segment's depend on p)
-        // (only lanes 0 .. nb hold a window count: one read start per tile as a rule -- two readlanes instead of a scan over the wave)
-        uint32_t Cfix;
-        if (nb <= 2u) Cfix = bcast(wfix, 0) + (nb >= 1u ? bcast(wfix, 1) : 0u) + (nb >= 2u ? bcast(wfix, 2) : 0u);
-        else Cfix = bcast(wave_incl_scan(wfix, lane), 63);
-        const bool pass = dep && nb == 0 && !ext_at_end;
-        const uint32_t q_out = ext_at_end ? 0u : (m_last < K1 ? m_last : K1);
+        unsigned long long word = 0; // (lane 0's)
+        if constexpr (!WORD_LATER) { // the final word (see s2k_dev.h)
+            const uint32_t m_first = bcast(mine, 0), m_last = bcast(mine, (int)nb);
+            uint32_t wfix = (uint32_t)lane <= nb && mine > K1 ? mine - K1 : 0u; // windows of a segment that starts a read in (or at the start of) the tile
+            if (lane == 0 && dep) wfix = 0;                                         // (the first segment's depend on p)
+            // (only lanes 0 .. nb hold a window count: one read start per tile as a rule -- two readlanes instead of a scan over the wave)
+            uint32_t Cfix;
+            if (nb <= 2u) Cfix = bcast(wfix, 0) + (nb >= 1u ? bcast(wfix, 1) : 0u) + (nb >= 2u ? bcast(wfix, 2) : 0u);
+            else Cfix = bcast(wave_incl_scan(wfix, lane), 63);
+            const bool pass = dep && nb == 0 && !ext_at_end;
+            const uint32_t q_out = ext_at_end ? 0u : (m_last < K1 ? m_last : K1);
+            word = agg_pack(m_first, Cfix, dropped ? 0u : N, q_out, dep, pass);
+        }
         if (lane == 0) {
-            d_agg[t] = agg_pack(m_first, Cfix, dropped ? 0u : N, q_out, dep, pass);
+            if constexpr (WORD_LATER) reinterpret_cast<uint32_t *>(d_agg + t)[1] = agg_provisional_hi(dropped ? 0u : N, nb, dep, ext_at_end); // (the lower half: rs16[1], rs16[2], stored above)
+            else d_agg[t] = word;
             TileMeta *m = &d_meta[t];
             m->rec_base = base;
             m->rs0 = rs0;
@@ -1314,9 +1341,11 @@ __device__ __forceinline__ uint32_t dense_phase(IssueNext &&issue_next, WL &S, c
             m->nb = (uint16_t)nb;
             m->nrd = (uint16_t)(r1 - r0);
         }
-        if ((uint32_t)lane <= nb) {
-            d_meta[t].segstart[lane] = (uint16_t)segstart;
-            if (lane) d_meta[t].rs16[lane] = S.rs16[lane];
+        if constexpr (!WORD_LATER) {
+            if ((uint32_t)lane <= nb) {
+                d_meta[t].segstart[lane] = (uint16_t)segstart;
+                if (lane) d_meta[t].rs16[lane] = S.rs16[lane];
+            }
         }
         if (N == 0 || dropped || (sem.dbg_skip & 128)) { // (KNOBS builds, 128: everything after the tile's word ablated)
             issue_next(0u, base);

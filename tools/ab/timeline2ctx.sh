@@ -11,7 +11,7 @@ f=glob.glob("$out/*/*kernel_trace.csv")[0]
 ev=[]
 for r in csv.DictReader(open(f)):
     n=r['Kernel_Name']
-    k='MIN' if 'tile_minimizer' in n else 'KMM' if 'desc_kminmer' in n else 'FIN' if 'finalize' in n else 'RT' if 'read_table' in n else None
+    k='MIN' if 'tile_minimizer' in n else 'KMM' if 'desc_kminmer' in n else 'WRD' if 'desc_word' in n else 'FIN' if 'finalize' in n else 'RT' if 'read_table' in n else None
     if k: ev.append((int(r['Start_Timestamp']),int(r['End_Timestamp']),k,r.get('Stream_Id','?')))
 ev.sort()
 mins=[e for e in ev if e[2]=='MIN']
