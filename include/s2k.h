@@ -1226,6 +1226,42 @@ s2k_status s2k_walks_segments(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out
  * when the outputs are written. */
 s2k_status s2k_align_join(s2k_ctx *ctx, uint64_t n_walks, const uint64_t *d_seg_off, const uint8_t *d_bad, uint64_t n_segments,
                           const s2k_align_out *seg, const s2k_align_out *out, uint64_t *n_ops_total);
+/* ---- GAF text on the device: one line per walk -----------------------------------------------------------------------
+ * Inputs: the walk records s2k_paths_walks wrote (walk_off, first_step, n_steps, items, qstart, qend, path_len, path_start, path_end;
+ * flags and edge are not read) for n_reads reads and n_walks walks; d_step_unitig, the oriented unitig of every one of the n_steps
+ * steps; optionally the reads' names, d_names (n_name_bytes bytes) and d_name_off (n_reads + 1 entries: the name of read r is
+ * d_names[name_off[r], name_off[r + 1])), both NULL or both given; first_read; optionally d_read_len (n_reads entries); optionally al,
+ * the alignments of the walks as s2k_align_pairs or s2k_align_join wrote them (edits, flags, ops_off, n_ops, matches, ops;
+ * al->capacity = the runs ops holds).
+ * The line of walk w of read r, fields separated by tabs, unsigned decimal numbers without padding:
+ *   name (the bytes as they are, or the decimal first_read + r), the read's length (or *), qstart, qend, +, the path -- per step s in
+ *   [first_step, first_step + n_steps) the token >t for d_step_unitig[s] = 2 t and <t for 2 t + 1 --, path_len, path_start, path_end,
+ *   matches, block, 255, km:i:<items>, ns:i:<n_steps>, and a newline.  Without al, or with al->flags[w] != 0, matches = items and block =
+ *   max(qend - qstart, path_end - path_start).  With al->flags[w] == 0, matches = al->matches[w], block = the sum of the lengths of the
+ *   walk's runs ops[ops_off[w] .. ops_off[w] + n_ops[w]), and \tNM:i:<edits>\tcg:Z:<runs> stands before the newline, a run len << 4 | op
+ *   as <len> and I, D, =, X for S2K_CIGAR_I, _D, _EQ, _X; n_ops[w] == 0 gives an empty cg:Z:.  The slots behind a walk's n_ops, which
+ *   s2k_align_pairs leaves untouched, and every slot of a flagged walk are never read.  Walks may share steps and stand in any order.
+ * Outputs: *n_bytes = the bytes of all lines, always set (0 on a refusal); d_line_off (n_walks + 1 entries, may be NULL): line_off[w] =
+ * the first byte of walk w's line, line_off[n_walks] = *n_bytes, written whenever the call returns S2K_OK; d_text (may be NULL: the sizes
+ * only): the lines back to back in walk order, written only when *n_bytes <= capacity, otherwise S2K_ERR_CAPACITY and nothing at all is
+ * written.  n_walks == 0 reads no input and writes line_off[0] = 0 alone.  Outputs must not overlap inputs.
+ * Checked on the device before anything is written, one flag word read by the host, S2K_ERR_INVALID_ARG otherwise: walk_off runs from 0
+ * to n_walks without decreasing; every walk's steps lie inside the n_steps steps; qstart <= qend and path_start <= path_end; name_off
+ * runs from 0 without decreasing and ends inside n_name_bytes; with al: ops_off does not decrease and ends inside al->capacity, ops_off[w]
+ * + n_ops[w] <= al->capacity, n_ops[w] <= ops_off[w + 1] - ops_off[w] for a walk with flags 0, and every run of such a walk has one of
+ * the four codes (a length of 0 is printed as it is); no line has 2^32 bytes or more.  On the host: names without offsets or offsets
+ * without names; n_walks >= 2^31; walks without reads; n_reads, n_steps, al->capacity or the sum of the walks' n_steps >= 2^39;
+ * first_read + n_reads past 2^64.
+ * Lengths first, bytes second: one lane per step (its token's length), per run slot (whether it is live, its token's length, its run
+ * length) and per walk (the line's length from the digits of its fields and differences of the two prefixes), a scan for line_off, one
+ * host wait; then one lane per walk (the fields), per path token and per live run slot (its token, at the place the prefixes give).
+ * No lane loops over a walk (only over its own digits or a name's bytes: a very long name is slow, never wrong).  No atomic touches
+ * an output: two calls are bit-identical.  Workspace (the context's grow-only count workspace): 12 B per step, 24 B per run slot, 28 B
+ * per walk.  Runs on the context's stream; returns when the outputs are written. */
+s2k_status s2k_walks_gaf(s2k_ctx *ctx, uint64_t n_reads, const s2k_walk_out *walks, uint64_t n_walks, const uint32_t *d_step_unitig,
+                         uint64_t n_steps, const uint8_t *d_names, const uint64_t *d_name_off, uint64_t n_name_bytes, uint64_t first_read,
+                         const uint64_t *d_read_len, const s2k_align_out *al, uint8_t *d_text, uint64_t capacity, uint64_t *d_line_off,
+                         uint64_t *n_bytes);
 /* Send buffers of the multi-GPU version: d_out = the keys grouped into n_parts ranges of the hash space (part p holds the
  * hashes h with floor(h * n_parts / 2^64) == p, i.e. split by hash prefix), d_part_off[n_parts + 1] = group starts.  After
  * an all-to-all of the groups, rank p owns every occurrence of its range and counts locally. */

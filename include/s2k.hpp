@@ -502,6 +502,24 @@ class Engine { // one per thread and device (like one KminmersIterator per threa
         if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
         return n_ops_total;
     }
+    // s2k_walks_gaf: the GAF lines of the walks (`walks`: walk_off and the record arrays s2k_paths_walks wrote) as bytes on the device.
+    // names.bytes / names.off nullptr: the decimal first_read + r; d_read_len nullptr: *; al nullptr: no alignment columns (al->capacity
+    // = the runs al->ops holds).  d_text nullptr: the sizes only.  Returns the bytes of all lines; throws on S2K_ERR_CAPACITY too
+    // (nothing written).
+    struct Names {
+        const uint8_t *bytes;
+        const uint64_t *off; // n_reads + 1
+        uint64_t n_bytes;
+    };
+    uint64_t walks_gaf(uint64_t n_reads, const s2k_walk_out &walks, uint64_t n_walks, const uint32_t *d_step_unitig, uint64_t n_steps, const Names &names = {},
+                       uint64_t first_read = 0, const uint64_t *d_read_len = nullptr, const s2k_align_out *al = nullptr, uint8_t *d_text = nullptr,
+                       uint64_t capacity = 0, uint64_t *d_line_off = nullptr) {
+        uint64_t n_bytes = 0;
+        s2k_status st = s2k_walks_gaf(ctx_, n_reads, &walks, n_walks, d_step_unitig, n_steps, names.bytes, names.off, names.n_bytes, first_read, d_read_len, al,
+                                      d_text, capacity, d_line_off, &n_bytes);
+        if (st != S2K_OK) throw Error(st, std::string(s2k_strerror(st)) + ": " + s2k_last_error(ctx_));
+        return n_bytes;
+    }
     s2k_ctx *raw() { return ctx_; }
 
   private:

@@ -212,6 +212,7 @@ PROTOTYPES = {
     "s2k_walks_segments": (_int, [_vp, _u64, _P(WalkOut), _u64, _P(ThreadOut), _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _P(ThreadOut),
                                   _u64, _vp, _vp, _P(DeviceOut), _u32, _P(SegmentOut), _n64, _n64]),
     "s2k_align_join": (_int, [_vp, _u64, _vp, _vp, _u64, _P(AlignOut), _P(AlignOut), _n64]),
+    "s2k_walks_gaf": (_int, [_vp, _u64, _P(WalkOut), _u64, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _P(AlignOut), _vp, _u64, _vp, _n64]),
     "s2k_partition_device": (_int, [_vp, _vp, _u64, _u32, _vp, _vp]),
     "s2k_synth_bases_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "s2k_synth_hifi_lengths": (None, [_u64, _u64, _u64, _vp]),

@@ -707,6 +707,63 @@ class Engine(_Handle):
         self._run(self.lib.s2k_align_join, dev, *args, C.byref(o), C.byref(total))
         return {**cut(), "n_ops_total": m}
 
+    def walks_gaf(self, walks, step_unitig, names=None, read_lengths=None, first_read=0, alignments=None):
+        """The GAF lines of the walks, formatted on the device (s2k_walks_gaf; the format is in include/s2k.h and is what
+        write_gaf_walks writes).  walks: a ReadWalks (or anything with walk_off and the record arrays but flags); step_unitig: the oriented
+        unitig of every step of its paths; names: one str (encoded as UTF-8) or bytes per read, None: the index first_read + r;
+        read_lengths: one length per read (a sequence or a tensor), None: *; alignments: a WalkAlignments or the dict align_pairs /
+        align_join returned for the walks.  Two calls: the sizes, then the bytes.  -> dict of GPU tensors text (uint8), line_off (int64,
+        n_walks + 1) and the int n_bytes."""
+        rec = {f: getattr(walks, f) for f in ("walk_off", "first_step", "n_steps", "items", "qstart", "qend", "path_len", "path_start", "path_end")}
+        if rec["qstart"] is None or rec["qend"] is None:
+            raise ValueError("walks_gaf wants walks whose paths carry start and end")
+        rec = {f: x.contiguous() for f, x in rec.items()}
+        step_unitig = step_unitig.contiguous()
+        nr, nw, ns, dev = rec["walk_off"].numel() - 1, rec["first_step"].numel(), step_unitig.numel(), rec["walk_off"].device
+        if (any(rec[f].numel() != nw for f in rec if f != "walk_off") or [rec[f].element_size() for f in rec] != [8, 8, 4, 8, 4, 4, 8, 8, 8]
+                or step_unitig.element_size() != 4):
+            raise ValueError("walks_gaf wants walk_off, the walk records and one 32-bit unitig per step")
+        wo = WalkOut()
+        wo.capacity = nw
+        for f, x in rec.items():
+            setattr(wo, f, x.data_ptr() if x.numel() else 0)
+        pool = name_off = lens = None
+        n_pool = 0
+        if names is not None:
+            enc = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in names]
+            if len(enc) != nr:
+                raise ValueError("walks_gaf wants one name per read")
+            off = np.zeros(nr + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in enc], out=off[1:])
+            n_pool = int(off[-1])
+            pool = torch.from_numpy(np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8).copy()).to(dev)
+            name_off = torch.from_numpy(off).to(dev)
+        if read_lengths is not None:
+            lens = read_lengths.to(device=dev, dtype=torch.int64).contiguous() if torch.is_tensor(read_lengths) else \
+                torch.from_numpy(np.asarray(read_lengths).astype(np.uint64).view(np.int64).copy()).to(dev)
+            if lens.numel() != nr:
+                raise ValueError("walks_gaf wants one length per read")
+        ao, keep = None, None
+        if alignments is not None:
+            get = alignments.get if isinstance(alignments, dict) else lambda f: getattr(alignments, f)
+            keep = {f: get(f).contiguous() for f in ("edits", "flags", "ops_off", "n_ops", "matches", "ops")}
+            if (keep["ops_off"].numel() != nw + 1 or keep["ops_off"].element_size() != 8 or keep["ops"].element_size() != 4
+                    or any(keep[f].element_size() != 4 or keep[f].numel() < nw for f in ("edits", "flags", "n_ops", "matches"))):
+                raise ValueError("walks_gaf wants the arrays align_pairs or align_join wrote for the walks")
+            ao = AlignOut()
+            ao.capacity = keep["ops"].numel()
+            for f, x in keep.items():
+                setattr(ao, f, x.data_ptr() if x.numel() else 0)
+        args = (self.ctx, nr, C.byref(wo), nw, _p(step_unitig, ns), ns, _p(pool, names is not None), _p(name_off, names is not None), n_pool, int(first_read),
+                _p(lens, lens is not None), C.byref(ao) if ao is not None else None)
+        nb = C.c_uint64(0)
+        self._run(self.lib.s2k_walks_gaf, dev, *args, None, 0, None, C.byref(nb))
+        n = int(nb.value)
+        text = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        line_off = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
+        self._run(self.lib.s2k_walks_gaf, dev, *args, _p(text), n, _p(line_off), C.byref(nb))
+        return {"text": text[:n], "line_off": line_off, "n_bytes": n}
+
     @staticmethod
     def _pile_struct(planes, n_bases):
         """the s2k_pile over an (11, n_bases) int32 GPU tensor, rows in the order of PILEUP_PLANES"""

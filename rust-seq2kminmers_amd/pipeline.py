@@ -680,13 +680,27 @@ class ReadWalks:
                 d[f] = x.cpu().numpy().view(np.uint64 if x.element_size() == 8 else np.uint32)
         return d
 
-    def write_gaf(self, path, graph=None, names=None, read_lengths=None, first_read=0, alignments=None):
+    def gaf_text(self, engine, graph=None, names=None, read_lengths=None, first_read=0, alignments=None):
+        """The GAF lines of write_gaf as bytes on the device (Engine.walks_gaf; include/s2k.h: s2k_walks_gaf), arguments as write_gaf
+        -> dict of GPU tensors text (uint8), line_off (int64, n_walks + 1: where every walk's line starts) and the int n_bytes.  What
+        a loop over batches appends to one file."""
+        if self.qstart is None or self.qend is None:
+            raise ValueError("gaf_text wants paths that carry start and end (extract with start / end kept)")
+        return engine.walks_gaf(self, self.paths.unitig, names=names, read_lengths=read_lengths, first_read=first_read, alignments=alignments)
+
+    def write_gaf(self, path, graph=None, names=None, read_lengths=None, first_read=0, alignments=None, engine=None):
         """One GAF line per walk (write_gaf_walks).  graph: the UnitigGraph the walks were taken on (only its naming is used: unitig t
         is segment t, as in write_unitig_gfa; may be None); names: one name per read (the index first_read + r when None);
         read_lengths: one length per read (* when None); alignments: the WalkAlignments UnitigGraph.align returned for these walks
-        (residue matches, block length, NM:i: and cg:Z: on every walk it aligned)."""
+        (residue matches, block length, NM:i: and cg:Z: on every walk it aligned).  engine: an Engine formats the lines on the device
+        (gaf_text), then one copy to the host and one write of the bytes; None: the host writer.  The file is the same."""
         if self.qstart is None or self.qend is None:
             raise ValueError("write_gaf wants paths that carry start and end (extract with start / end kept)")
+        if engine is not None:
+            text = self.gaf_text(engine, graph, names=names, read_lengths=read_lengths, first_read=first_read, alignments=alignments)["text"]
+            with open(path, "wb") as out:
+                out.write(text.cpu().numpy().data)
+            return
         h = self.host()
         write_gaf_walks(path, h, self.paths.unitig.cpu().numpy().view(np.uint32), names=names, read_lengths=read_lengths, first_read=first_read,
                         alignments=None if alignments is None else alignments.host())

@@ -1,4 +1,5 @@
-"""The text formats (paths, GAF, spans, FASTA, GFA) on host arrays, and the FASTX reader."""
+"""The text formats (paths, GAF, spans, FASTA, GFA) on host arrays, and the FASTX reader.  The GAF lines are also formatted on the
+device (Engine.walks_gaf, ReadWalks.gaf_text): write_gaf_walks is the specification of that text."""
 import ctypes as C
 import os
 
@@ -30,7 +31,7 @@ def write_gaf_walks(path, walks, step_unitig, names=None, read_lengths=None, fir
     circular unitig path_end may pass path_len (include/s2k.h).  alignments: the dict WalkAlignments.host() returns (edits, matches,
     n_ops, ops_off, ops, flags per walk); a walk whose flags are 0 then has the residue matches in the matches column, the sum of its
     run lengths as the block length, and NM:i:<edits> and cg:Z:<runs with = X I D> after the two tags; a flagged walk keeps the line
-    it has without alignments."""
+    it has without alignments.  s2k_walks_gaf (include/s2k.h) writes the same bytes on the device."""
     off = np.asarray(walks["walk_off"]).astype(np.int64).tolist()
     w = {f: np.asarray(walks[f]).astype(np.int64).tolist() for f in WALK_FIELDS}
     u = np.asarray(step_unitig).astype(np.int64).tolist()
